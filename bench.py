@@ -4,7 +4,11 @@ K1 translate/pack -> K2-K4 seeds/candidates -> K5 banded Smith-Waterman -> K6 tr
 hit table to the host -> (N>1: RCCL all-gather of the shard hit tables + top-k merge) -> K10 union-find.
 Inputs (nucleotides) are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--genes G] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--genes G] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-e2e] [--no-workloads]]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, ...).  --full adds everything else the line
+and bench_detail.json can hold: the CPU baseline and the parity check against the CPU oracle, the phase split with every timer on, the
+rooflines, and the loops and legs behind the timed region (secondary workloads, end-to-end calls, the configs[4] legs).
 
 N>1: one rank per GPU on an R x C grid of (query range, reference range) shards (peppan_amd/dist.py).  Either the launcher provides
 RANK / WORLD_SIZE (torch.distributed.run), or - when RANK is unset - this script starts the N ranks itself and relays rank 0's line.
@@ -934,6 +938,27 @@ def emit(detail):
     sys.stdout.flush()
 
 
+DUMP_LIMIT = 64 * 10 ** 6       # bytes of all the files --dump-outputs writes together
+
+
+def dump_outputs(path, hits, cigar, labels):
+    """--dump-outputs: what the last timed step handed its caller - every field of the hit table (hits_<field>.npy), the CIGAR runs (cigar.npy) and the
+    cluster label of every gene (labels.npy) - in float64, which holds every value exactly (integers below 2^53).  Above DUMP_LIMIT the hit rows and
+    the CIGAR runs are cut to a sample each, positions drawn with a fixed seed and kept in order."""
+    hits, cigar, labels = np.array(hits), np.array(cigar), np.array(labels)       # (copies: the arguments may be views of the staging area)
+    names = list(hits.dtype.names)
+    budget = DUMP_LIMIT - 8 * len(labels) - 256 * (len(names) + 2)              # (256: more than an .npy header)
+    total = 8 * (len(hits) * len(names) + len(cigar))
+    if total > budget:
+        rng = np.random.default_rng(355)
+        pick = lambda n: np.sort(rng.choice(n, int(n * budget / total), replace=False))
+        hits, cigar = hits[pick(len(hits))], cigar[pick(len(cigar))]
+    out = dict([('hits_' + f, hits[f]) for f in names] + [('cigar', cigar), ('labels', labels)])
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a, dtype=np.float64))
+
+
 def main_map(args, rank, local_rank, world):
     import torch
     import torch.distributed as dist
@@ -1013,7 +1038,14 @@ def main():
     ap.add_argument('--map-workers', type=int, default=0, help='--workload map --map-scaling strong: worker processes per rank (peppan_amd.mapworkers; 0 = the rank maps its genomes itself)')
     ap.add_argument('--grid', default=None, help='RxC: query shards x reference shards of the all-vs-all (default: peppan_amd.dist.choose_grid); R*C must equal --gpus')
     ap.add_argument('--no-workloads', action='store_true', help='skip the configs[4] legs behind the headline (50k x 50k search step, 50k-exemplar mapping step)')
+    ap.add_argument('--full', action='store_true', help='everything beside the headline: CPU baseline + parity check, phase timers and rooflines, the loops and legs '
+                    'behind the timed region (--no-cpu-baseline / --no-e2e / --no-workloads leave parts out).  Without it a run sets up, warms up, times the '
+                    'steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (hit table fields, CIGAR runs, cluster labels) '
+                    'as DIR/<name>.npy in float64')
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != 'search':
+        ap.error('--dump-outputs writes the outputs of --workload search')
     os.environ.setdefault('PEPPAN_LOG', '0')          # the reference-style progress lines of the legs (configure.logger) stay out of the bench's stderr
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -1031,7 +1063,7 @@ def main():
     nts = [seqs[i] for i in order]
     min_id, min_qcov = 45.0, 25.0                                  # PEPPAN.py:229-230 with defaults (match_identity 0.5 - 0.05, match_frag_prop 0.25)
     cpu_line = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_line = cpu_baseline([names[i] for i in order], nts, min(args.cpu_sample, len(nts)), min_id, min_qcov)
 
     import torch
@@ -1102,17 +1134,21 @@ def main():
             acc[k] += st[k]
     sync()
     dt = time.perf_counter() - t0
-    # the same K steps once more with every phase timer on (outside the timed region)
-    ctx.set_timing(2)
-    step()
-    sync()
-    t_ph = time.perf_counter()
-    for _ in range(args.steps):
-        st = step()[0]
-        for k in ('ms_sw_trace', 'ms_seed', 'ms_seed_match', 'ms_trace', 'ms_k1', 'ms_total'):
-            acc[k] += st[k]
-    sync()
-    ms_step_all_timers = (time.perf_counter() - t_ph) / args.steps * 1e3
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, allh, allc, labels)       # (before any other step reuses the staging area the views point into)
+    ms_step_all_timers = None
+    if args.full:
+        # the same K steps once more with every phase timer on (outside the timed region)
+        ctx.set_timing(2)
+        step()
+        sync()
+        t_ph = time.perf_counter()
+        for _ in range(args.steps):
+            st = step()[0]
+            for k in ('ms_sw_trace', 'ms_seed', 'ms_seed_match', 'ms_trace', 'ms_k1', 'ms_total'):
+                acc[k] += st[k]
+        sync()
+        ms_step_all_timers = (time.perf_counter() - t_ph) / args.steps * 1e3
     ctx.set_timing(0)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -1139,7 +1175,7 @@ def main():
 
     hits_last, clusters_last = float(len(allh)), int(len(np.unique(labels)))      # (allh / labels are views of the context's pinned staging area)
     extras = {}
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         # what a caller sees who synchronises the whole device and then searches: the same K steps right behind a torch.cuda.synchronize(),
         # once more (the runtime's one-time 5.6 ms copy-queue stall behind a device-wide synchronisation, DESIGN.md section 6, lands in one of the two loops if it occurs)
         torch.cuda.synchronize()
@@ -1148,7 +1184,7 @@ def main():
             step()
         torch.cuda.synchronize()
         extras['ms_per_step_after_device_sync'] = (time.perf_counter() - t9) / args.steps * 1e3
-    if world == 1 and rank == 0 and not args.no_e2e:
+    if world == 1 and rank == 0 and args.full and not args.no_e2e:
         # Independent searches in flight together (NOT the headline: `value` is one search at a time).  A second context - stream and work space of
         # its own - runs the same step from a second host thread: the seed stage waits for memory (VALU issue 0.2) while the alignment passes wait for
         # nothing but the VALU (0.9), so two searches overlap.  This is what the mapping path's worker processes get out of one GPU.
@@ -1200,7 +1236,7 @@ def main():
         shard.params = keep
         extras['same_unit_as_round1'] = {'ungapped_min': 45, 'value': c45 / d45, 'unit': 'gene-pairs/s', 'ms_per_step': d45 / args.steps * 1e3,
                                          'candidates_per_step': c45 / args.steps}
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.no_e2e:
         # (a) the step with the host buffers handed over inside it (H2D of the nucleotides): what the C boundary costs a caller
         reps = max(3, min(args.steps, 10))
         packed = N._pack(nts)                 # what the C boundary takes: one byte buffer + offsets (pep_set_query_nt / pep_set_ref_nt); packing Python strings is not its cost
@@ -1285,7 +1321,7 @@ def main():
                                                              '(first_pass_s: the first one, with every worker\'s first search). python bench.py --workload map --map-scaling strong --map-workers 8'}
         except Exception as e:                                  # never lose the headline over the secondary leg
             extras.setdefault('map_workload', {})['error'] = repr(e)
-    if rank == 0 and world == 1 and not args.no_e2e and not args.no_workloads and args.genes == 10000:
+    if rank == 0 and world == 1 and args.full and not args.no_e2e and not args.no_workloads and args.genes == 10000:
         # (e) the call the reference makes - both tools - on the headline's genes; then BASELINE configs[4] at the size one GPU holds: the 50k x 50k
         # search step and a 50k-exemplar mapping step
         try:
@@ -1300,16 +1336,6 @@ def main():
 
     if rank == 0:
         K = args.steps
-        counters, cyc4 = _profile_tables()
-        headline = args.genes == 10000 and args.gene_len == 1002 and world == 1      # the workload the tracked counters were collected on
-        Lq = (args.gene_len // 3) if args.gene_len else int(acc['query_residues'] / K / max(1, shard.q1 - shard.q0))
-        hits_step = acc['hits'] / K
-        n_shapes = params.n_shapes
-
-        rl = roofline_kernels(counters if headline else {}, cyc4, os.path.basename(PROFILE_COUNTERS), {k: acc[k] / K for k in acc}, Lq, n_shapes)
-        top = dict(rl[0])
-        top['note'] = ('the kernel with the largest share of the STEP (live HIP-event time x launches per step); the Smith-Waterman passes in roofline_kernels are '
-                       'integer-VALU bound (SURVEY 8d): their `bound` is "valu", their `frac` the issue fraction, their HBM side sits under `hbm`')
         line = {
             'metric': 'gene_pairs_aligned_per_s', 'value': total_pairs / dt, 'unit': 'gene-pairs/s',
             'n_gpus': world, 'steps': K, 'warmup': args.warmup, 'ms_per_step': dt / K * 1e3,
@@ -1331,16 +1357,27 @@ def main():
                                 'the pre-filter in front of that stage decides how many there are - see same_unit_as_round1; hits_per_s and '
                                 'gene_pairs_all_vs_all_per_s (query genes x reference genes per second) do not depend on it. The timed region starts right behind the barrier + '
                                 'torch.cuda.synchronize() the contract asks for (no settle calls in between since round 4); ms_per_step_after_device_sync is a second such loop',
-            'phase_ms': {k: acc[k] / K for k in ('ms_k1', 'ms_seed', 'ms_seed_match', 'ms_sw', 'ms_sw_trace', 'ms_trace', 'ms_total')},
-            'phase_timers': {'in_timed_region': ['ms_sw'], 'ms_per_step_with_every_phase_timer': ms_step_all_timers,
-                             'note': 'pep_set_timing: the timed region records the two HIP events around the score pass (the roofline kernel) only; the other phase_ms '
-                                     'entries and the durations of the second and third roofline_kernels come from a loop of the same K steps behind it with all '
-                                     'sixteen events per search on - each costs about 6 us of idle GPU between the kernels it separates'},
             'host_phase_ms_rank0': dict({k: acc[k] / K for k in ('ms_host_translate', 'ms_host_search', 'ms_host_exchange', 'ms_host_merge')}, ms_host_union_find=t_uf / K),
-            'roofline': top, 'roofline_kernels': rl,
+            'roofline': None,
             'cpu_baseline': cpu_line if world == 1 else None,
             'parity_check': parity,
         }
+        if args.full:
+            # the phase split and the rooflines: phase times from the loop with every timer on, traffic from the tracked counters under profiles/
+            counters, cyc4 = _profile_tables()
+            headline = args.genes == 10000 and args.gene_len == 1002 and world == 1      # the workload the tracked counters were collected on
+            Lq = (args.gene_len // 3) if args.gene_len else int(acc['query_residues'] / K / max(1, shard.q1 - shard.q0))
+            rl = roofline_kernels(counters if headline else {}, cyc4, os.path.basename(PROFILE_COUNTERS), {k: acc[k] / K for k in acc}, Lq, params.n_shapes)
+            top = dict(rl[0])
+            top['note'] = ('the kernel with the largest share of the STEP (live HIP-event time x launches per step); the Smith-Waterman passes in roofline_kernels are '
+                           'integer-VALU bound (SURVEY 8d): their `bound` is "valu", their `frac` the issue fraction, their HBM side sits under `hbm`')
+            line.update({
+                'phase_ms': {k: acc[k] / K for k in ('ms_k1', 'ms_seed', 'ms_seed_match', 'ms_sw', 'ms_sw_trace', 'ms_trace', 'ms_total')},
+                'phase_timers': {'in_timed_region': ['ms_sw'], 'ms_per_step_with_every_phase_timer': ms_step_all_timers,
+                                 'note': 'pep_set_timing: the timed region records the two HIP events around the score pass (the roofline kernel) only; the other phase_ms '
+                                         'entries and the durations of the second and third roofline_kernels come from a loop of the same K steps behind it with all '
+                                         'sixteen events per search on - each costs about 6 us of idle GPU between the kernels it separates'},
+                'roofline': top, 'roofline_kernels': rl})
         line.update(extras)
         emit(line)
     if world > 1:

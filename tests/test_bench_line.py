@@ -101,3 +101,30 @@ def test_compact_line_with_a_valu_bound_kernel_on_top():
     d = _check(bench.compact_line(detail))
     assert d['roofline']['unit'] == 'GB/s' and d['roofline']['peak'] == 8000.0 and 0 < d['roofline']['frac'] < 0.05
     assert 0.5 < d['roofline_valu_issue_frac'] <= 1.01
+
+
+def test_dump_outputs_writes_float64_and_keeps_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: every hit field, the CIGAR runs and the labels as float64 .npy; over the size limit a seeded sample of the rows, the same on every call"""
+    import numpy as np
+    dt = np.dtype([('q', '<u4'), ('t', '<u4'), ('score', '<i4'), ('cigar_off', '<u8')])
+    rng = np.random.default_rng(1)
+    hits = np.zeros(5000, dtype=dt)
+    for f in dt.names:
+        hits[f] = rng.integers(0, 2 ** 31 - 1, len(hits))
+    cigar, labels = rng.integers(0, 2 ** 32, 20000).astype(np.uint32), np.arange(300, dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / 'a'), hits, cigar, labels)
+    a = {f: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert sorted(a) == ['cigar.npy', 'hits_cigar_off.npy', 'hits_q.npy', 'hits_score.npy', 'hits_t.npy', 'labels.npy']
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a['hits_q.npy'], hits['q']) and np.array_equal(a['cigar.npy'], cigar) and np.array_equal(a['labels.npy'], labels)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 100000)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), hits, cigar, labels)
+    sizes = [os.path.getsize(str(tmp_path / 'b' / f)) for f in os.listdir(str(tmp_path / 'b'))]
+    assert sum(sizes) <= 100000
+    for f in os.listdir(str(tmp_path / 'b')):
+        b, c = np.load(str(tmp_path / 'b' / f)), np.load(str(tmp_path / 'c' / f))
+        assert np.array_equal(b, c)
+    b = {f: np.load(str(tmp_path / 'b' / f)) for f in os.listdir(str(tmp_path / 'b'))}
+    assert 0 < len(b['hits_q.npy']) < len(hits) and len(b['hits_q.npy']) == len(b['hits_t.npy']) and np.array_equal(b['labels.npy'], labels)
+    assert np.isin(b['hits_score.npy'], hits['score']).all() and np.isin(b['cigar.npy'], cigar).all()

@@ -926,7 +926,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PEPPAN_BENCH_SHARE_GPU='1', PEPPAN_BENCH_DETAIL=str(tmp_path / 'detail.json'))
     env.pop('RANK', None); env.pop('WORLD_SIZE', None)
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--genes', '400', '--steps', '2', '--warmup', '1', '--no-e2e'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--genes', '400', '--steps', '2', '--warmup', '1', '--full', '--no-e2e'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
@@ -935,7 +935,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert line['n_gpus'] == 2 and line['value'] > 0 and line['steps'] == 2
     assert line['parity_check']['gpu_hits_identical'] is True and line['parity_check']['hits_compared'] > 400
     assert line['cpu_baseline'] is None                         # the CPU baseline figure belongs to the N = 1 line
-    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--genes', '400', '--steps', '2', '--warmup', '1'],
+    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--genes', '400', '--steps', '2', '--warmup', '1', '--full'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert one.returncode == 0, one.stderr.decode()[-2000:]
     assert one.stdout.decode().count('\n') == 1 and len(one.stdout) < 4096          # ONE compact line on stdout, the rest in the detail file
@@ -948,12 +948,24 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert l1['cpu_baseline']['kind'] == 'port' and set(l1['cpu_baseline']['reference_binaries']) == {'diamond', 'blastn', 'makeblastdb', 'mmseqs'}
     assert l1['cpu_baseline']['phase_s']['seed'] > 0 and l1['cpu_baseline']['sw_cells_per_s_vectorised'] > l1['cpu_baseline']['sw_cells_per_s']
     # --grid: the reference side split too, so that the exact top-k merge runs behind the exchange; the line says how many ranks the collective connected
-    grid = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--grid', '1x2', '--genes', '400', '--steps', '2', '--warmup', '1', '--no-e2e'],
+    grid = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--grid', '1x2', '--genes', '400', '--steps', '2', '--warmup', '1', '--full', '--no-e2e'],
                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert grid.returncode == 0, grid.stderr.decode()[-2000:]
     lg = json.loads([l for l in grid.stdout.decode().splitlines() if l.startswith('{')][0])
     assert lg['rccl_ranks_seen'] == 2 and 'grid 1 query shards x 2 reference shards' in lg['config']['parallelism']
     assert lg['parity_check']['gpu_hits_identical'] is True and lg['hits_per_step'] == line['hits_per_step'] and lg['clusters'] == line['clusters']
+    # a plain run (no --full): the timed steps and the line only; --dump-outputs writes what its last timed step computed
+    plain = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--genes', '400', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / 'dump')],
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert plain.returncode == 0, plain.stderr.decode()[-2000:]
+    assert plain.stdout.decode().count('\n') == 1
+    lp = json.loads(plain.stdout.decode())
+    assert lp['metric'] == 'gene_pairs_aligned_per_s' and lp['value'] > 0 and lp['steps'] == 3 and lp['ms_per_step'] > 0 and lp['dtype'] == 'int16'
+    assert lp['cpu_baseline'] is None and lp['roofline'] is None and lp['hits_per_step'] == line['hits_per_step'] and lp['clusters'] == line['clusters']
+    dump = {f[:-4]: np.load(str(tmp_path / 'dump' / f)) for f in os.listdir(str(tmp_path / 'dump'))}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert len(dump['hits_q']) == lp['hits_per_step'] and len(dump['labels']) == 400 and len(np.unique(dump['labels'])) == lp['clusters']
+    assert dump['cigar'].sum() > 0 and set('hits_' + f for f in ('q', 't', 'q_start', 'q_end', 't_start', 't_end', 'score', 'cigar_runs')) <= set(dump)
     # the mapping stage as strong scaling: ONE fixed set of genomes dealt to the two ranks, rank 0 writes the stores
     ms = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'map', '--map-scaling', 'strong', '--genes', '600', '--map-genomes', '5'],
                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
