@@ -222,77 +222,6 @@ __global__ __launch_bounds__(256) void idx_slab(SeedShapeSet shs, const uint8_t 
     }
 }
 
-#ifdef PEP_PROBES
-// MEASUREMENT ONLY, compiled with -DPEP_PROBES (make PROBES=1; params.reserved[0] = 7, tools/partition_probe.py): the first pass of a PARTITIONED join - the target positions whose key
-// passes the filter are scattered into the coarse buckets of the query index, exactly as idx_slab scatters the query positions (same chunking,
-// same LDS counting, same slab reservation), 8 bytes (key << 29 | position) each.  Its duration against seed_match's is what decides whether a
-// partitioned join can pay; nothing reads what it writes.
-template <int W>
-__global__ __launch_bounds__(256) void tgt_slab_probe(SeedShape sh, const uint8_t *__restrict__ res, uint64_t total, int bucket_bits, int fine_bits,
-                                                      const unsigned long long *__restrict__ filter, uint32_t *__restrict__ coarse_cnt, uint64_t *__restrict__ part,
-                                                      uint32_t cap, int tiles, unsigned long long *__restrict__ kept)
-{
-    extern __shared__ uint32_t part_lds[];
-    uint32_t *h = part_lds;
-    const uint32_t n_coarse = 1u << (bucket_bits - fine_bits);
-    uint8_t *red = reinterpret_cast<uint8_t *>(h + n_coarse);
-    unsigned long long mine = 0;
-    for (int t0 = 0; t0 < tiles; t0 += PART_TILES) {
-        for (uint32_t x = threadIdx.x; x < n_coarse; x += 256) h[x] = 0;
-        uint64_t ent[PART_TILES];
-        uint32_t cb[PART_TILES], fetched[PART_TILES];
-#pragma unroll
-        for (int t = 0; t < PART_TILES; ++t) {
-            const uint64_t tile = (uint64_t)blockIdx.x * tiles + t0 + t;
-            fetched[t] = (t0 + t < tiles && tile * TILE < total) ? fetch_tile(res, tile, total) : 0u;
-        }
-#pragma unroll
-        for (int t = 0; t < PART_TILES; ++t) {
-            const uint64_t base = ((uint64_t)blockIdx.x * tiles + t0 + t) * TILE;
-            ent[t] = ~0ull; cb[t] = 0;
-            __syncthreads();
-            if (t0 + t < tiles && base < total) {
-                red[threadIdx.x] = reduce_letter(sh, fetched[t]);
-                if (threadIdx.x < TILE_HALO) red[TILE + threadIdx.x] = reduce_letter(sh, fetched[t] >> 8);
-                __syncthreads();
-                const uint64_t p = base + threadIdx.x;
-                uint64_t key;
-                if (p + 32 <= total && tile_key<W>(sh, red, threadIdx.x, key)) {
-                    uint32_t word;
-                    const uint64_t m = filter_mask(key, bucket_bits, word);
-                    if ((filter[word] & m) == m) {
-                        ent[t] = (key << POS_BITS) | p;
-                        cb[t] = hash_u64(key, bucket_bits) >> fine_bits;
-                        atomicAdd(&h[cb[t]], 1u);
-                        ++mine;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        for (uint32_t x0 = threadIdx.x; x0 < n_coarse; x0 += 8 * 256) {
-            uint32_t c8[8], at8[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const uint32_t x = x0 + 256u * k; c8[k] = x < n_coarse ? h[x] : 0u; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) at8[k] = x0 + 256u * k < n_coarse ? atomicAdd(&coarse_cnt[x0 + 256u * k], c8[k]) : 0u;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) if (c8[k]) h[x0 + 256u * k] = at8[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < PART_TILES; ++t)
-            if (ent[t] != ~0ull) {
-                const uint32_t slot = atomicAdd(&h[cb[t]], 1u);
-                if (slot < cap) part[(uint64_t)cb[t] * cap + slot] = ent[t];
-            }
-        __syncthreads();
-    }
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(kept, mine);
-}
-#endif  // PEP_PROBES
-
 // one block per coarse bucket c: its slab -> entries[] ordered by fine bucket (dense: after the entries of the coarse buckets before it),
 // start[c << F .. (c + 1) << F), filter slice
 __global__ __launch_bounds__(256) void idx_finish(const uint64_t *__restrict__ part, const uint32_t *__restrict__ coarse_cnt, int bucket_bits,
@@ -408,7 +337,7 @@ struct JoinArgs {
     uint64_t *hits;          // raw seed hits (qpos << 32 | tpos)
     unsigned long long *hit_count;
     uint64_t hit_cap;
-    int debug;               // profiling aid (params.reserved[0]): 1 = keys only, 2 = keys + bucket lookup, 3 = + entry compare (no extension), 9 = no wave-level de-duplication
+    int debug;               // params.reserved[0]: 1 = keys only, 2 = keys + bucket lookup, 3 = + entry compare (no extension) - profiling aids; 8 / 10 = reference paths of the tests
     unsigned int *tile_ctr;      // the matchers' tile claims (TileClaims): tile_groups counters, 128 bytes apart, zero when the launch starts
     uint32_t tile_groups;        // 8 (a launch of 64 blocks and more: block b claims from counter b mod 8 - neighbouring blocks go to different XCCs, a counter a group keeps the
                                  // atomics of one word at a tenth of what it sustains) or 1
@@ -498,23 +427,9 @@ struct TileClaims {
 // query index and every equal-key pair is appended as a raw seed hit (qpos << 32 | tpos).  Hits are staged in an
 // LDS buffer and flushed with ONE global atomic per flush (a single global counter word only sustains ~90
 // atomics/us).  Every memory operation of this phase is independent across lanes: high memory-level parallelism.
-#ifndef PEP_HIT_BUF
-#define PEP_HIT_BUF 2048
-#endif
-#ifdef PEP_PROBES
-// MEASUREMENT ONLY (make PROBES=1; tools/ab/block_times.py): when and where every block of the last seed_match launch ran - start and end on the device's wall clock,
-// the hardware id of the wavefront that wrote them (compute unit, shader engine, XCC)
-__device__ unsigned long long g_block_probe[4 * 2048];
-#endif
-#ifndef PEP_ENTRY_TRIP
-#define PEP_ENTRY_TRIP 4
-#endif
-#ifndef PEP_STRIDE_ENTRY_TRIP
-#define PEP_STRIDE_ENTRY_TRIP 2
-#endif
-constexpr int STRIDE_ENTRY_TRIP = PEP_STRIDE_ENTRY_TRIP;      // ... and of seed_match_stride's
-constexpr int ENTRY_TRIP = PEP_ENTRY_TRIP;      // entries of a bucket per trip of seed_match's walk (make EXTRA=-DPEP_ENTRY_TRIP=4: a measurement build)
-constexpr int HIT_BUF = PEP_HIT_BUF;          // (make EXTRA=-DPEP_HIT_BUF=1024: a measurement build - how many of the matcher's blocks a CU holds at once is a matter of this buffer)
+constexpr int ENTRY_TRIP = 4;                 // entries of a bucket per trip of seed_match's walk ...
+constexpr int STRIDE_ENTRY_TRIP = 2;          // ... and of seed_match_stride's
+constexpr int HIT_BUF = 2048;                 // staged hits per block (how many of the matcher's blocks a CU holds at once is a matter of this buffer)
 template <int W>
 __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
 {
@@ -523,12 +438,6 @@ __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
     __shared__ uint32_t nbuf, blk_stats[2];
     __shared__ unsigned long long gbase;
     if (threadIdx.x == 0) { nbuf = 0; blk_stats[0] = blk_stats[1] = 0; }
-#ifdef PEP_PROBES
-    if (threadIdx.x == 0 && blockIdx.x < 2048) {
-        g_block_probe[4 * blockIdx.x] = wall_clock64();
-        g_block_probe[4 * blockIdx.x + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 20) << 32) | __builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);      // XCC_ID | HW_ID
-    }
-#endif
     __syncthreads();
     uint32_t n_seed = 0, n_hit = 0;
     const uint64_t n_tiles = (a.t_total + 255) / 256;
@@ -565,11 +474,10 @@ __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
                 uint32_t word;
                 const uint64_t m = filter_mask(key, a.bucket_bits, word);
                 // (a position inside a stretch that repeats a query holds that query's key: it is in the index, the filter's word need not be asked - the filter only ever
-                // saves look-ups, so a block that is marked beyond the stretch's end costs a look-up and nothing else; debug 11: ask anyway, for comparison)
-                if ((sd != PEP_SELF_NO_DELTA && a.debug != 11) || (a.filter[word] & m) == m) {
-                    // (both ends of the bucket with ONE 8-byte request - the two words lie side by side, and what this kernel pays for is requests; debug 12: two loads, for comparison)
-                    if (a.debug == 12) { e0 = a.start[b]; e1 = a.start[b + 1]; }
-                    else { uint32_t ends[2]; __builtin_memcpy(ends, a.start + b, 8); e0 = ends[0]; e1 = ends[1]; }
+                // saves look-ups, so a block that is marked beyond the stretch's end costs a look-up and nothing else)
+                if (sd != PEP_SELF_NO_DELTA || (a.filter[word] & m) == m) {
+                    // (both ends of the bucket with ONE 8-byte request - the two words lie side by side, and what this kernel pays for is requests)
+                    uint32_t ends[2]; __builtin_memcpy(ends, a.start + b, 8); e0 = ends[0]; e1 = ends[1];
                 }
                 if (a.debug == 2) { n_hit += e1 - e0; e1 = e0; }
             }
@@ -619,17 +527,7 @@ __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
     if ((threadIdx.x & 63) == 0) { atomicAdd(&blk_stats[0], n_seed); atomicAdd(&blk_stats[1], n_hit); }
     __syncthreads();
     if (threadIdx.x < 2 && blk_stats[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)blk_stats[threadIdx.x]);
-#ifdef PEP_PROBES
-    if (threadIdx.x == 0 && blockIdx.x < 2048) g_block_probe[4 * blockIdx.x + 1] = wall_clock64();
-#endif
 }
-
-#ifdef PEP_PROBES
-extern "C" int pep_probe_block_times(unsigned long long *out)          // 4 words per block of the last seed_match launch: start, end, XCC_ID << 32 | HW_ID, unused
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_block_probe), sizeof(g_block_probe)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 // ---- the nucleotide tool's matcher (round 6): BLAST's lookup stride (blastn -word_size 17 looks up shorter words at a stride and verifies them,
 // uberBlast.py:294).  The seeds are exact NW-mers over the four bases.  Every NW-mer holds exactly one NK-mer that starts at a packed position
@@ -713,9 +611,8 @@ __global__ __launch_bounds__(256) void seed_match_stride(JoinArgs a)
             const uint32_t b = hash_u64(key, a.bucket_bits);
             uint32_t word;
             const uint64_t m = filter_mask(key, a.bucket_bits, word);
-            if ((sd != PEP_SELF_NO_DELTA && a.debug != 11) || (a.filter[word] & m) == m) {      // (as in seed_match: a self stretch's keys are in the index; one request for both ends of the bucket)
-                if (a.debug == 12) { e0 = a.start[b]; e1 = a.start[b + 1]; }
-                else { uint32_t ends[2]; __builtin_memcpy(ends, a.start + b, 8); e0 = ends[0]; e1 = ends[1]; }
+            if (sd != PEP_SELF_NO_DELTA || (a.filter[word] & m) == m) {      // (as in seed_match: a self stretch's keys are in the index; one request for both ends of the bucket)
+                uint32_t ends[2]; __builtin_memcpy(ends, a.start + b, 8); e0 = ends[0]; e1 = ends[1];
             }
         }
         const uint32_t tl = d0, tr = (d4 >> 16) | (d5 << 16);           // target bytes p - 4 .. p - 1 and p + 14 .. p + 17
@@ -880,7 +777,7 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
             for (int u = 0; u < RUN_TRIP; ++u) {
                 const uint32_t lo = (uint32_t)key[u], hi = (uint32_t)(key[u] >> 32);
                 const uint32_t lo_prev = __shfl_up(lo, 1, 64), hi_prev = __shfl_up(hi, 1, 64);     // unconditional: every lane must take part in the shuffles
-                leader[u] = valid[u] && !(a.debug != 9 && lane > 0 && lo_prev == lo && hi_prev == hi);
+                leader[u] = valid[u] && !(lane > 0 && lo_prev == lo && hi_prev == hi);
                 const unsigned long long leaders = __ballot(leader[u]), valid_m = __ballot(valid[u]);
                 const unsigned long long above = lane == 63 ? 0ull : (leaders & (~0ull << (lane + 1)));          // the next run starts at its lowest set bit
                 rlen[u] = (above ? __builtin_ctzll(above) : __popcll(valid_m)) - lane;                            // valid lanes are a prefix
@@ -1194,7 +1091,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
     // count -> scan -> fill build, as does a coarse bucket that overflows LDS)
     const int fine_bits = std::min(12, bucket_bits - 8);
     // the nucleotide tool (exact 17-mers over the four bases, one shape): look-up words at a stride (seed_match_stride); reserved[0] = 8 keeps the plain matcher
-    bool stride_lookup = P.n_shapes == 1 && P.base == 4 && P.weight[0] == NW && (P.reserved[0] == 0 || P.reserved[0] == 11 || P.reserved[0] == 12);
+    bool stride_lookup = P.n_shapes == 1 && P.base == 4 && P.weight[0] == NW && P.reserved[0] == 0;
     for (int i = 0; i < NW && stride_lookup; ++i) stride_lookup = P.offs[0][i] == i;
     for (int c = 0; c < 32 && stride_lookup; ++c) stride_lookup = P.reduce[c] == (c < 4 ? c : 0xFF);
     bool use_partition = P.reserved[2] == 0 && bucket_bits >= 16 && bucket_bits - fine_bits <= 13;
@@ -1307,7 +1204,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
             a.q_res = Q.res.as<const uint8_t>(); a.sub = ctx->d_params.as<const int8_t>();
             a.debug = P.reserved[0]; a.ungapped_min = P.ungapped_min; a.stage1_min = P.stage1_min; a.xdrop = P.xdrop; a.ext_right = P.ext_right; a.ext_left = P.ext_left;
             a.self_delta = nullptr;
-            if (s == 0 && P.ungapped_min > 0 && (P.reserved[0] == 0 || P.reserved[0] == 11 || P.reserved[0] == 12)) PEP_TRY(pep_self_map(ctx, &self_on));     // (reserved[0] = 10 / 8: the plain stream, for comparison)
+            if (s == 0 && P.ungapped_min > 0 && P.reserved[0] == 0) PEP_TRY(pep_self_map(ctx, &self_on));     // (reserved[0] = 10 / 8: the plain stream, for comparison)
             if (self_on) a.self_delta = ctx->d_self_delta.as<const int32_t>();
             unsigned long long *hit_count = reinterpret_cast<unsigned long long *>(zero + PEP_ZERO_SHAPE) + 2 * s;      // per shape, cleared by the one fill
             a.hits = ctx->ws[8].as<uint64_t>(); a.hit_count = hit_count; a.hit_cap = hit_cap;
@@ -1331,22 +1228,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
                 PEP_SEED_DISPATCH(seed_match, dim3(grid), sh, a);
             }
             pep_timer_end(ctx, TM_MATCH0 + s);
-#ifdef PEP_PROBES
-            if (P.reserved[0] == 7 && use_partition && sh.weight == 10) {
-                // measurement only: the scatter pass of a partitioned join over the same targets, behind the matcher it would replace
-                static DevBuf probe_part, probe_cnt;
-                const uint32_t n_coarse = 1u << (bucket_bits - fine_bits), cap = 16384;
-                PEP_TRY(dev_reserve(ctx, probe_part, (uint64_t)n_coarse * cap * 8));
-                PEP_TRY(dev_reserve(ctx, probe_cnt, (uint64_t)n_coarse * 4 + 64));
-                PEP_HIP(ctx, hipMemsetAsync(probe_cnt.p, 0, (uint64_t)n_coarse * 4 + 64, ctx->stream));
-                const int tiles = (int)std::max<uint64_t>(PART_TILES, ceil_div(T.total, (uint64_t)TILE * 8192));
-                const unsigned pb = (unsigned)ceil_div(T.total, (uint64_t)tiles * TILE);
-                hipLaunchKernelGGL(tgt_slab_probe<10>, dim3(pb), dim3(256), (size_t)n_coarse * 4 + TILE + TILE_HALO, ctx->stream, sh, T.res.as<const uint8_t>(), T.total, bucket_bits, fine_bits,
-                                   (const unsigned long long *)filter, probe_cnt.as<uint32_t>(), probe_part.as<uint64_t>(), cap, tiles,
-                                   reinterpret_cast<unsigned long long *>(probe_cnt.as<uint32_t>() + n_coarse));
-            }
-#endif
-            // (same-box A/B, tools/ab/phase2_ab.sh: four trips of 64 hits per strip; 8 blocks per CU at 10 k genes - 122 us against 126 with 16 -, 16 at 50 k - 1.71 ms against 1.86)
+            // (same-box A/B: four trips of 64 hits per strip; 8 blocks per CU at 10 k genes - 122 us against 126 with 16 -, 16 at 50 k - 1.71 ms against 1.86)
             hipLaunchKernelGGL(seed_runs_extend, dim3(256u * (T.total > (48ull << 20) ? 16u : 8u)), dim3(256), 0, ctx->stream, a);
             PEP_HIP(ctx, hipGetLastError());
         }

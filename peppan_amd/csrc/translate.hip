@@ -815,9 +815,7 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
         ctx->k1_upper = upper;
         PEP_TRY(dev_reserve(ctx, ctx->d_k1_base, (nw + 1) * 8));
         PEP_HIP(ctx, hipMemcpy(ctx->d_k1_base.p, base.data(), (nw + 1) * 8, hipMemcpyHostToDevice));
-        // the long frames' tables (k1_stop_mask / k1_ref_chunks_mask / k1_ref_desc_fill): a function of the lengths as well (PEPPAN_K1_PLAIN_CHUNKS=1: every frame by
-        // the one-wavefront walk over the nucleotides, for comparison)
-        static const bool plain_chunks = [] { const char *e = getenv("PEPPAN_K1_PLAIN_CHUNKS"); return e && atoi(e) != 0; }();
+        // the long frames' tables (k1_stop_mask / k1_ref_chunks_mask / k1_ref_desc_fill): a function of the lengths as well
         std::vector<K1Seg> segs, tiles;                 // tiles of 4 096 characters of the stop mask / of 256 chunk slots
         std::vector<K1Long> longs;
         std::vector<uint32_t> long_of_w;
@@ -827,7 +825,7 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
             for (int f = 1; f <= nf; ++f) {
                 const uint64_t shift = (uint64_t)(f <= 3 ? f - 1 : f - 4);
                 const uint64_t na = L > shift ? (L - shift + 2) / 3 : 0;
-                if (na + 1 <= (uint64_t)K1_LONG || plain_chunks) continue;
+                if (na + 1 <= (uint64_t)K1_LONG) continue;
                 const uint32_t w = g * (uint32_t)nf + (uint32_t)(f - 1);
                 if (long_of_w.empty()) long_of_w.assign(nw, 0u);
                 long_of_w[w] = (uint32_t)longs.size();

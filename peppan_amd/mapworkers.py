@@ -359,8 +359,6 @@ class MapWorkers(object):
             env['PEPPAN_HIP_DEVICE'] = str(int(device))
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         env['PYTHONPATH'] = os.pathsep.join([root] + [p for p in sys.path if p] + [env.get('PYTHONPATH', '')])     # a search function of the caller's must be importable
-        if os.environ.get('PEPPAN_POOL_GATE'):               # (experiment: at most that many workers inside their batched searches at once)
-            env['PEPPAN_GPU_GATE'] = '%s,%d' % (self._dir, int(os.environ['PEPPAN_POOL_GATE']))
         self._env = env
         self._procs, self._conns, started = [], [], {}
         self._setup_msg, self._spawn_lock = None, threading.Lock()

@@ -95,43 +95,6 @@ def _prepare_side(seqs, key, names=None):
     return side
 
 
-class _gpu_gate(object):
-    """Worker processes of one pool share one GPU (mapworkers.py).  Their batched searches are chains of short launches with host round trips in
-    between; more than a few of them in flight at once and every one of them crawls (eight at once: 2 - 3 times a search's time alone).  The pool
-    therefore hands out PEPPAN_GPU_GATE="<directory>,<M>": a batch's searches run while the process holds one of M lock files - the other workers
-    do their host work (groups, members) meanwhile.  Nothing set: no gate."""
-
-    def __enter__(self):
-        self.f = None
-        spec = os.environ.get('PEPPAN_GPU_GATE')
-        if spec:
-            import fcntl
-            where, m = spec.rsplit(',', 1)
-            m = max(1, int(m))
-            files = [open(os.path.join(where, 'gate%d' % i), 'a') for i in range(m)]
-            first = os.getpid() % m
-            for k in range(m):
-                f = files[(first + k) % m]
-                try:
-                    fcntl.flock(f, fcntl.LOCK_EX | fcntl.LOCK_NB)
-                    self.f = f
-                    break
-                except OSError:
-                    pass
-            if self.f is None:
-                self.f = files[first]
-                fcntl.flock(self.f, fcntl.LOCK_EX)
-            for f in files:
-                if f is not self.f:
-                    f.close()
-        return self
-
-    def __exit__(self, *exc):
-        if self.f is not None:
-            self.f.close()                      # (closing gives the lock back)
-        return False
-
-
 def get_context(device=None):
     """one HIP context per (process, device), created lazily so that forked workers make their own
     (the reference forks pool workers before calling uberBlast, PEPPAN.py:922)"""
@@ -428,15 +391,14 @@ class RunBlast(object):
             # Whose turn the GPU is.  The two searches together take the GPU as long side by side as one after the other (6.0 ms of kernels at 10 000 genes either
             # way), so what counts is which tool's host chain starts first: the nucleotide tool has the longer one behind its search (table 1.6 + K7 1.1 ms against
             # 0.55 + 1.0), so its search goes first and the translated search starts when it is back - the nucleotide table is then built while the translated search
-            # has the GPU to itself.  PEPPAN_TOOL_TURNS=0: both searches at once (round 5).
-            turn = self._nucl_searched = threading.Event() if os.environ.get('PEPPAN_TOOL_TURNS', '1') != '0' else None
+            # has the GPU to itself.
+            turn = self._nucl_searched = threading.Event()
 
             def side_tool():
                 try:
                     outcomes[k_side] = attempt(todo[k_side])
                 finally:
-                    if turn is not None:
-                        turn.set()                # (also when the tool failed before or inside its search)
+                    turn.set()                    # (also when the tool failed before or inside its search)
             side = threading.Thread(target=side_tool)
             # (a thread that comes back from the library waits for the interpreter lock until the other one gives it up: at the default 5 ms
             # between such requests the two tools cost more side by side than one after the other - 30.5 against 29.1 ms per call; at 0.1 ms 24.0)
@@ -559,8 +521,7 @@ class RunBlast(object):
                 groups.append(g)
         self.refSeq, self._batch = combined, (names, groups)
         genome_of = dict(zip(names, groups))
-        with _gpu_gate():
-            tables = self._run_tools(methods, None, None, nt_match=re_score == 1)
+        tables = self._run_tools(methods, None, None, nt_match=re_score == 1)
         # mode-1 rescoring is a function of the row alone: K7 once per tool over the rows of ALL genomes (a launch and a round trip per genome
         # otherwise: 84 us of GPU and a synchronisation each, sixteen times per batch), the identity cut stays with the genome's table (_post)
         batch_rescore = re_score == 1
