@@ -30,6 +30,7 @@
  *   pep_ovl_filter          RunBlast.ovlFilter (host C++)                    uberBlast.py:417-452
  *   pep_linear_merge        RunBlast.linearMerge + _linearMerge (host C++)   uberBlast.py:100-218, 453-460
  *   pep_alleles             aligned-allele strings + base-5 packing of iter_map_bsn   PEPPAN.py:812-835, 846-848
+ *   pep_allele_diff         numba compare_seq / compare_seqX of filt_per_group over the rows of the .seq store   PEPPAN.py:296-316, 332-333
  *   pep_store_mat_member / pep_store_seq_member   the 1000-group members of the .mat / .seq stores get_map_bsn writes (host C++:
  *                           the .npy pickle stream emitted from the numeric hit table)   PEPPAN.py:950-966
  *   pep_table_from_hits / pep_cols_fix_end / pep_cols_order / pep_cols_gather   RunBlast.run's numeric chain between a search and the caller (host C++:
@@ -46,7 +47,7 @@
 extern "C" {
 #endif
 
-#define PEP_ABI_VERSION 16
+#define PEP_ABI_VERSION 17
 
 #define PEP_OK 0
 #define PEP_ERR_HIP (-1)       /* a HIP runtime call failed */
@@ -299,6 +300,29 @@ typedef struct {
 int pep_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *nt_off, uint32_t n_contigs, uint64_t n_rows, const pep_locus *rows,
                 const uint32_t *cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_qlen, int gtable,
                 int64_t *in_frame, int64_t *orf, uint8_t *packed, uint64_t packed_cap);
+
+/* K15: pairwise allele differences of gene groups (compare_seq / compare_seqX, PEPPAN.py:296-316, over rows as filt_per_group
+ * reads and masks them, :332-333).  Row r is bytes [row_off[r], row_off[r+1]) of `packed` in the .seq store's form - ceil(row_len[r] / 3)
+ * bytes c[j] * 25 + c[s + j] * 5 + c[2 s + j], codes 0 = not comparable, 1..4 = ACGT - and counts with its first row_len[r] columns only
+ * (digits past them are ignored).  Group g is the list of row indices grp_rows[grp_off[g] .. grp_off[g+1]) into that one table (a row may
+ * serve several groups, so the sub-groups of :354-360 need no second upload); all its rows have the same row_len.  With
+ * comparable(a, b) = columns where both rows are non-zero and mismatch(a, b) = those of them where the rows differ, a group of n rows
+ * writes to out[out_off[g] ...], as int32 pairs (mismatch + 1, comparable + 2) and in this order:
+ *   grp_mode[g] bit 0: the n (n - 1) / 2 pairs a < b in row-major order (the packed upper triangle compare_seq fills);
+ *   grp_mode[g] bit 1: [2, n, 2] - the first and the last row of the group against every row, itself included (compare_seqX).
+ * out_off[g] and out_cap count int32 values.  Empty batches, empty groups and groups of one row are legal.  PEP_ERR_ARG: a row that does
+ * not hold ceil(row_len / 3) bytes, a group that mixes row_len, a row index >= n_rows, a byte above 124, outputs that overlap or run
+ * past out_cap.  PEP_ERR_LIMIT: the call's output or its bit planes (24 B per 64 columns of a row) exceed PEP_ALLELE_DIFF_MAX_BYTES each;
+ * the message says how much was asked for, and the caller splits the batch.  After an error `out` holds nothing usable.
+ * (The output limit is reported at the first group that crosses it, with the bytes counted up to that group.)
+ * pep_allele_diff_times: of the context's newest pep_allele_diff, in ms: the kernel times - bit planes, pairs - when pep_set_timing is 2
+ * (else zeros; at that level the host waits between the two kernels), and the host's wall time from the end of the kernels until the
+ * output lies in `out` (always). */
+#define PEP_ALLELE_DIFF_MAX_BYTES (1ull << 31)
+int pep_allele_diff(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows,
+                    uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_rows, const uint8_t *grp_mode,
+                    int32_t *out, const uint64_t *out_off, uint64_t out_cap);
+int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back);
 
 /* K14 and its two host passes: the consumer of the all-vs-all table (get_similar_pairs, PEPPAN.py:194-294).
  *

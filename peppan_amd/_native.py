@@ -8,13 +8,14 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpeppan_hip.so')
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_SEQ_LEN = (1 << 23) - 256          # PEP_MAX_SEQ_LEN: longest single sequence of a packed set
+ALLELE_DIFF_MAX_BYTES = 1 << 31        # PEP_ALLELE_DIFF_MAX_BYTES: output (and bit planes) of one pep_allele_diff call
 EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy', 'pep_last_error', 'pep_default_params', 'pep_set_sensitivity',
            'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
            'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
            'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
-           'pep_merge_hits', 'pep_rescore_nt', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
+           'pep_merge_hits', 'pep_rescore_nt', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
            'pep_similar_classify', 'pep_similar_scan', 'pep_pair_support', 'pep_similar_resolve', 'pep_fasta_keep', 'pep_fasta_scan', 'pep_fasta_records', 'pep_store_mat_member', 'pep_store_seq_member', 'pep_store_tab_members', 'pep_store_tab_archive', 'pep_deflate_literals', 'pep_deflate_fast', 'pep_crc32', 'pep_pack_member', 'pep_argsort_object_order',
            'pep_set_nt_match', 'pep_result_nt_match', 'pep_table_from_hits', 'pep_cols_fix_end', 'pep_cols_order', 'pep_cols_gather', 'pep_lex_order', 'pep_set_host_threads']
 
@@ -1074,6 +1075,89 @@ class Context(object):
                                           C.c_uint32(ng), _ptr(grp_off), _ptr(grp_qlen) if ng else None, C.c_int(gtable), _ptr(in_frame), _ptr(orf),
                                           _ptr(packed), C.c_uint64(total)), 'pep_alleles')
         return in_frame[:n], orf[:n], packed[:total]
+
+    # ---- K15
+    def allele_diff(self, packed, row_off, row_len, groups, modes, out_budget=1 << 30):
+        """compare_seq / compare_seqX (PEPPAN.py:296-316) for many groups of base-5 packed rows at once.  packed: uint8 concatenation of the
+        rows (row r = packed[row_off[r]:row_off[r+1]], ceil(row_len[r] / 3) bytes as the .seq store holds them); groups: one array of row
+        indices per group; modes: per group (or one int for all) bit 0 = all pairs a < b, bit 1 = first and last row against all rows.
+        -> list of (tri int32[n(n-1)/2, 2] or None, edge int32[2, n, 2] or None), values (mismatch + 1, comparable + 2).
+        A batch whose output exceeds `out_budget` bytes (at most the library's PEP_ALLELE_DIFF_MAX_BYTES), or whose bit planes exceed the
+        library's budget, goes to the library in several calls, each with the rows its groups use; PepError when one group alone exceeds a
+        budget.  The arrays of one library call are views into ONE output buffer: holding any of them keeps that whole buffer alive
+        (copy what is to be kept for long)."""
+        out_budget = min(int(out_budget), ALLELE_DIFF_MAX_BYTES)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64).reshape(-1)
+        row_len = np.ascontiguousarray(row_len, dtype=np.uint32).reshape(-1)
+        if len(row_off) != len(row_len) + 1:
+            raise ValueError('allele_diff: row_off needs one entry more than row_len')
+        groups = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+        modes = np.full(len(groups), modes, dtype=np.uint8) if np.isscalar(modes) else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
+        if len(modes) != len(groups):
+            raise ValueError('allele_diff: one mode per group')
+        n = np.array([len(g) for g in groups], dtype=np.int64)
+        tri = np.where((modes & 1) > 0, n * (n - 1) // 2, 0)
+        edge = np.where((modes & 2) > 0, 2 * n, 0)
+        need = 2 * (tri + edge)                                       # int32 values per group
+        # bytes of bit planes per row (24 per 64 digits); per group an upper bound of what its rows add to a call (a row shared by two groups counts twice)
+        row_planes = 24 * ((3 * ((row_len.astype(np.int64) + 2) // 3) + 63) // 64)
+        if any(len(g) and int(g.max()) >= len(row_len) for g in groups):
+            # a row index out of range: the whole batch goes to the library as it is, whose check reports it (the same text, split or not)
+            return self._allele_diff_call(packed, row_off, row_len, groups, modes, n, tri, need, int(need.sum()), True)
+        planes = np.array([int(row_planes[g].sum()) for g in groups], dtype=np.int64)
+        over = np.flatnonzero(need * 4 > out_budget)
+        if len(over):
+            raise PepError('allele_diff: group %d (%d rows) needs %d bytes of output, the budget is %d' % (over[0], n[over[0]], need[over[0]] * 4, out_budget))
+        over = np.flatnonzero(planes > ALLELE_DIFF_MAX_BYTES)
+        if len(over):
+            raise PepError('allele_diff: group %d (%d rows) needs %d bytes of bit planes, the budget is %d' % (over[0], n[over[0]], planes[over[0]], ALLELE_DIFF_MAX_BYTES))
+        results, lo = [], 0
+        while lo < len(groups):
+            hi, total, pl = lo, 0, 0
+            while hi < len(groups) and (total + need[hi]) * 4 <= out_budget and pl + planes[hi] <= ALLELE_DIFF_MAX_BYTES:
+                total += int(need[hi])
+                pl += int(planes[hi])
+                hi += 1
+            whole = lo == 0 and hi == len(groups) and int(row_planes.sum()) <= ALLELE_DIFF_MAX_BYTES      # (else: only the rows the groups use)
+            results += self._allele_diff_call(packed, row_off, row_len, groups[lo:hi], modes[lo:hi], n[lo:hi], tri[lo:hi], need[lo:hi], total, whole)
+            lo = hi
+        return results
+
+    def _allele_diff_call(self, packed, row_off, row_len, groups, modes, n, tri, need, total, whole):
+        if not whole and len(groups):
+            # part of a split batch: upload the rows these groups use, not the whole table
+            idx = np.concatenate(groups)                 # (indices are in range: allele_diff sends a batch with a bad one whole)
+            used, inv = np.unique(idx, return_inverse=True)
+            lens = (row_off[1:] - row_off[:-1])[used].astype(np.int64)
+            new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+            src = np.repeat(row_off[used].astype(np.int64) - new_off[:-1].astype(np.int64), lens) + np.arange(int(new_off[-1]), dtype=np.int64)
+            packed, row_off, row_len = packed[src], new_off, row_len[used]
+            cuts = np.cumsum(n)[:-1]
+            groups = np.split(inv.astype(np.uint32), cuts)
+        grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
+        grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if len(groups) and grp_off[-1] else np.zeros(1, np.uint32)
+        out_off = np.concatenate([[0], np.cumsum(need)]).astype(np.uint64)
+        out = np.empty(max(total, 1), dtype=np.int32)
+        pk = packed if len(packed) else np.zeros(1, np.uint8)
+        rl = row_len if len(row_len) else np.zeros(1, np.uint32)
+        md = modes if len(modes) else np.zeros(1, np.uint8)
+        self._check(self._lib.pep_allele_diff(self._h, _ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off),
+                                              _ptr(grp_rows), _ptr(md), _ptr(out), _ptr(out_off), C.c_uint64(total)), 'pep_allele_diff')
+        res = []
+        for g in range(len(groups)):
+            a, ng = int(out_off[g]), int(n[g])
+            t = out[a:a + 2 * int(tri[g])].reshape(-1, 2) if modes[g] & 1 else None
+            e = out[a + 2 * int(tri[g]):int(out_off[g + 1])].reshape(2, ng, 2) if modes[g] & 2 else None
+            res.append((t, e))
+        return res
+
+    def allele_diff_times(self):
+        """of the newest allele_diff library call, in ms: (allele_planes, allele_diff) kernel times when set_timing(2) is on, else zeros, and the
+        host's wall time from the end of the kernels until the output lay in the caller's buffer"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._check(self._lib.pep_allele_diff_times(self._h, C.byref(a), C.byref(b), C.byref(c)), 'pep_allele_diff_times')
+        return a.value, b.value, c.value
 
     # ---- K13
     def sha1(self, seqs):

@@ -1115,6 +1115,28 @@ int pep_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *nt_off, uint32_
     return pep_k12_alleles(ctx, nt, nt_off, n_contigs, n_rows, rows, cigar, n_cigar, n_groups, grp_off, grp_qlen, gtable, in_frame, orf, packed, packed_cap);
 }
 
+int pep_allele_diff(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows,
+                    uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_rows, const uint8_t *grp_mode,
+                    int32_t *out, const uint64_t *out_off, uint64_t out_cap)
+{
+    if (!ctx) return PEP_ERR_ARG;
+    if (!row_off || (n_rows && !row_len) || (n_groups && (!grp_off || !grp_mode || !out_off)) || (out_cap && !out))
+        return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    if (n_groups && grp_off[n_groups] && !grp_rows) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    if (n_rows && row_off[n_rows] && !packed) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return pep_k15_allele_diff(ctx, packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_mode, out, out_off, out_cap);
+}
+
+int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back)
+{
+    if (!ctx || !ms_planes || !ms_pairs || !ms_copy_back) return PEP_ERR_ARG;
+    *ms_planes = ctx->k15_ms[0];
+    *ms_pairs = ctx->k15_ms[1];
+    *ms_copy_back = ctx->k15_ms[2];
+    return PEP_OK;
+}
+
 int pep_sha1(pep_ctx *ctx, const uint8_t *bytes, const uint64_t *off, uint32_t n, uint8_t *digest)
 {
     if (!ctx || (n && (!off || !digest))) return PEP_ERR_ARG;

@@ -194,6 +194,7 @@ struct pep_ctx {
                                             // zero_ok flag still set the next search needs no fill
     DevBuf d_mail_copy;                     // the alignment stage's counter block outside d_zero (trace.hip: emit -> pack_out, K10)
     bool zero_ok[4] = {false, false, false, false};     // which consumer regions of d_zero are still untouched since that fill (PEP_ZC_*)
+    double k15_ms[3] = {0., 0., 0.};         // the newest pep_allele_diff: kernel times (planes, pairs) when pep_set_timing is 2, host time of the output's way back (allelediff.hip)
     // stats of the last search
     pep_stats stats;
 };
@@ -342,6 +343,10 @@ int pep_k11_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *h_contig, const in
 int pep_k12_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off, uint32_t n_contigs, uint64_t n, const pep_locus *h_rows,
                     const uint32_t *h_cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_qlen,
                     int gtable, int64_t *h_in_frame, int64_t *h_orf, uint8_t *h_packed, uint64_t packed_cap);
+// ---- allelediff.hip (K15)
+int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
+                        uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
+                        int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap);
 // ---- dedup.hip (K13)
 int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest);
 int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep);
