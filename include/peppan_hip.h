@@ -31,6 +31,7 @@
  *   pep_linear_merge        RunBlast.linearMerge + _linearMerge (host C++)   uberBlast.py:100-218, 453-460
  *   pep_alleles             aligned-allele strings + base-5 packing of iter_map_bsn   PEPPAN.py:812-835, 846-848
  *   pep_allele_diff         numba compare_seq / compare_seqX of filt_per_group over the rows of the .seq store   PEPPAN.py:296-316, 332-333
+ *   pep_group_verdicts      checkDiv over the edge rows, the distances test and the leader grouping of filt_per_group   PEPPAN.py:335-344, 352-366, 371-392
  *   pep_store_mat_member / pep_store_seq_member   the 1000-group members of the .mat / .seq stores get_map_bsn writes (host C++:
  *                           the .npy pickle stream emitted from the numeric hit table)   PEPPAN.py:950-966
  *   pep_table_from_hits / pep_cols_fix_end / pep_cols_order / pep_cols_gather   RunBlast.run's numeric chain between a search and the caller (host C++:
@@ -47,6 +48,8 @@
 extern "C" {
 #endif
 
+/* 17 gained, additively, the K16 entry points: pep_group_verdicts, pep_group_verdicts_check, pep_verdict_detail_size, pep_verdict_detail_copy,
+ * pep_verdict_result_free, pep_group_verdicts_times. */
 #define PEP_ABI_VERSION 17
 
 #define PEP_OK 0
@@ -64,6 +67,7 @@ extern "C" {
 
 typedef struct pep_ctx pep_ctx;
 typedef struct pep_result pep_result;
+typedef struct pep_verdict_result pep_verdict_result;
 
 /* search parameters; pep_default_params fills the protein defaults that mirror the reference's
  * diamond command line (uberBlast.py:550): BLOSUM62, gap 11/1, --evalue 1, --dbsize 5000000, -k 10, 5 splits */
@@ -323,6 +327,42 @@ int pep_allele_diff(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off
                     uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_rows, const uint8_t *grp_mode,
                     int32_t *out, const uint64_t *out_off, uint64_t out_cap);
 int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back);
+
+/* K16: divergence verdicts of gene groups - what filt_per_group decides from the pairs of K15 before it looks at any of them on the host
+ * (checkDiv over the first and last row, PEPPAN.py:335-344, 346-351; over the first and last row of every genome's sub-group for in-paralog
+ * groups, :352-366; the distances test :371-382; the leader grouping :383-392).  Rows and groups as for pep_allele_diff; grp_genome holds the
+ * genome id (column 1 of the group's table) of every entry of grp_rows, grp_inparalog one 0 / 1 per group.  With (mut, aln) = K15's pair
+ * (mismatch + 1, comparable + 2) as doubles and, per pair of rows, (gd0, denX, den) = the row of the table below for the two genomes
+ * (gd_default when the pair is not in it), or gd0 = denX = den = fmax(self_id, 2 / aln) when both rows are of one genome:
+ *   divergent   mut / aln / denX > 1 for a pair (a, b), a != b, a the first or last row of the group / of a sub-group, b any row of it;
+ *   beyond      (mut / aln / den) / gd0 > 1 / gd0 for a pair a < b of a divergent group;
+ *   leaders     rows in order: row j joins the FIRST leader l with mut(l, j) <= 0.01 * aln(l, j), else it becomes a leader.
+ * verdict[g]: 0 = not divergent (the reference returns at :368; also every group of fewer than two rows), 1 = divergent, no pair beyond
+ * (returns at :484), 2 = a pair beyond its bound (goes on at :383).  Every operation is a single correctly rounded double operation, so
+ * the verdicts equal numpy's bit for bit.  The table is made by the caller (peppan_amd.orthofilter.gd_table): gd_key[i] = g1 << 32 | g2
+ * with g1 <= g2, strictly increasing; gd_val[i] = (gd0, gd0 * exp(gd1 * sqrt(allowed_sigma)), gd0 * exp(gd1 * allowed_sigma)).
+ * All tables are checked on the host before anything is launched.  PEP_ERR_ARG: what pep_allele_diff names, a key with g1 > g2 or out of
+ * order, a value that is not finite or not > 0, self_id not finite or not > 0, grp_inparalog above 1.  PEP_ERR_LIMIT: the packed
+ * triangles of all groups of two rows and more (reserved for every group, its verdict is not known in advance) or the bit planes exceed
+ * PEP_ALLELE_DIFF_MAX_BYTES; the message names the first group that crosses it, and the caller splits the batch.
+ * pep_group_verdicts_check runs those checks alone: no context, no device; the message goes to msg (msg_cap bytes, 0-terminated).
+ * The verdicts cost the host n_groups bytes plus one word.  *detail keeps the triangles and leaders of the verdict-2 groups ON THE DEVICE,
+ * until the next pep_group_verdicts of the context (pep_verdict_detail_copy then fails with PEP_ERR_STATE); free it with
+ * pep_verdict_result_free before the context is destroyed.  pep_verdict_detail_size: pairs of group g's triangle, 0 unless its verdict is 2.
+ * pep_verdict_detail_copy: tri (int32 pairs, packed upper triangle as pep_allele_diff's bit 0) and leader (uint32[n]: the row that leads
+ * row j, leader[j] == j for a leader); either may be NULL; nothing is written for verdict 0 / 1.
+ * pep_group_verdicts_times: of the newest call, the kernel times in ms - bit planes, edge, pairs, leaders - when pep_set_timing is 2 (else
+ * zeros), and the bytes that call and the detail copies of its result have sent to the host. */
+int pep_group_verdicts(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,
+                       const uint64_t *grp_off, const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key,
+                       const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *verdict, pep_verdict_result **detail);
+int pep_group_verdicts_check(const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *grp_off,
+                             const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key, const double *gd_val,
+                             uint64_t n_gd, const double *gd_default, double self_id, char *msg, uint64_t msg_cap);
+int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs);
+int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *tri, uint32_t *leader);
+void pep_verdict_result_free(pep_verdict_result *res);
+int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host);
 
 /* K14 and its two host passes: the consumer of the all-vs-all table (get_similar_pairs, PEPPAN.py:194-294).
  *

@@ -15,7 +15,7 @@ EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy
            'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
            'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
            'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
-           'pep_merge_hits', 'pep_rescore_nt', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
+           'pep_merge_hits', 'pep_rescore_nt', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
            'pep_similar_classify', 'pep_similar_scan', 'pep_pair_support', 'pep_similar_resolve', 'pep_fasta_keep', 'pep_fasta_scan', 'pep_fasta_records', 'pep_store_mat_member', 'pep_store_seq_member', 'pep_store_tab_members', 'pep_store_tab_archive', 'pep_deflate_literals', 'pep_deflate_fast', 'pep_crc32', 'pep_pack_member', 'pep_argsort_object_order',
            'pep_set_nt_match', 'pep_result_nt_match', 'pep_table_from_hits', 'pep_cols_fix_end', 'pep_cols_order', 'pep_cols_gather', 'pep_lex_order', 'pep_set_host_threads']
 
@@ -117,6 +117,8 @@ def load_library():
     lib.pep_ctx_destroy.restype = None
     lib.pep_result_free.argtypes = [C.c_void_p]
     lib.pep_result_free.restype = None
+    lib.pep_verdict_result_free.argtypes = [C.c_void_p]
+    lib.pep_verdict_result_free.restype = None
     if lib.pep_version() != ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch')
     _lib = lib
@@ -234,6 +236,65 @@ def _count(seqs):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _rows_of_groups(packed, row_off, row_len, groups, n):
+    """the row table cut down to the rows `groups` (index arrays of n[g] entries, all in range) use -> (packed, row_off, row_len, groups re-indexed)"""
+    idx = np.concatenate(groups)
+    used, inv = np.unique(idx, return_inverse=True)
+    lens = (row_off[1:] - row_off[:-1])[used].astype(np.int64)
+    new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    src = np.repeat(row_off[used].astype(np.int64) - new_off[:-1].astype(np.int64), lens) + np.arange(int(new_off[-1]), dtype=np.int64)
+    return packed[src], new_off, row_len[used], np.split(inv.astype(np.uint32), np.cumsum(n)[:-1])
+
+
+def _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd):
+    """the arrays of one pep_group_verdicts / pep_group_verdicts_check call, in the order of their leading arguments, + the list that keeps them alive"""
+    n = np.array([len(g) for g in groups], dtype=np.int64)
+    grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
+    total = int(grp_off[-1])
+    grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if total else np.zeros(1, np.uint32)
+    grp_genome = np.ascontiguousarray(np.concatenate(genomes), dtype=np.uint32) if total else np.zeros(1, np.uint32)
+    keys, vals, default = gd[:3]
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    vals = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1, 3)
+    default = np.ascontiguousarray(default, dtype=np.float64).reshape(3)
+    if len(keys) != len(vals):
+        raise ValueError('group_verdicts: one row of values per key')
+    pk = packed if len(packed) else np.zeros(1, np.uint8)
+    rl = row_len if len(row_len) else np.zeros(1, np.uint32)
+    ip = inparalog if len(inparalog) else np.zeros(1, np.uint8)
+    kk = keys if len(keys) else np.zeros(1, np.uint64)
+    vv = vals if len(vals) else np.zeros((1, 3), np.float64)
+    keep = [pk, row_off, rl, grp_off, grp_rows, grp_genome, ip, kk, vv, default]
+    args = [_ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off), _ptr(grp_rows), _ptr(grp_genome), _ptr(ip),
+            _ptr(kk), _ptr(vv), C.c_uint64(len(keys)), _ptr(default)]
+    return args, keep
+
+
+def _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog):
+    packed = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.uint64).reshape(-1)
+    row_len = np.ascontiguousarray(row_len, dtype=np.uint32).reshape(-1)
+    if len(row_off) != len(row_len) + 1:
+        raise ValueError('group_verdicts: row_off needs one entry more than row_len')
+    groups = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+    genomes = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in genomes]
+    inparalog = np.ascontiguousarray(inparalog, dtype=np.uint8).reshape(-1)
+    if len(genomes) != len(groups) or len(inparalog) != len(groups) or any(len(a) != len(b) for a, b in zip(groups, genomes)):
+        raise ValueError('group_verdicts: one genome id per row of every group and one inparalog flag per group')
+    return packed, row_off, row_len, groups, genomes, inparalog
+
+
+def group_verdicts_check(packed, row_off, row_len, groups, genomes, inparalog, gd, self_id):
+    """the host checks of pep_group_verdicts alone (no context, no device): PepError with the library's code and text, else None"""
+    lib = load_library()
+    packed, row_off, row_len, groups, genomes, inparalog = _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog)
+    args, keep = _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd)
+    msg = C.create_string_buffer(512)
+    rc = lib.pep_group_verdicts_check(*args, C.c_double(self_id), msg, C.c_uint64(len(msg)))
+    if rc != 0:
+        raise PepError('pep_group_verdicts_check failed (%d): %s' % (rc, msg.value.decode()))
 
 
 def ovl_filter(q, r, qs, qe, ss, se, score, iden, coverage, delta):
@@ -1127,14 +1188,7 @@ class Context(object):
     def _allele_diff_call(self, packed, row_off, row_len, groups, modes, n, tri, need, total, whole):
         if not whole and len(groups):
             # part of a split batch: upload the rows these groups use, not the whole table
-            idx = np.concatenate(groups)                 # (indices are in range: allele_diff sends a batch with a bad one whole)
-            used, inv = np.unique(idx, return_inverse=True)
-            lens = (row_off[1:] - row_off[:-1])[used].astype(np.int64)
-            new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-            src = np.repeat(row_off[used].astype(np.int64) - new_off[:-1].astype(np.int64), lens) + np.arange(int(new_off[-1]), dtype=np.int64)
-            packed, row_off, row_len = packed[src], new_off, row_len[used]
-            cuts = np.cumsum(n)[:-1]
-            groups = np.split(inv.astype(np.uint32), cuts)
+            packed, row_off, row_len, groups = _rows_of_groups(packed, row_off, row_len, groups, n)       # (indices are in range: allele_diff sends a batch with a bad one whole)
         grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
         grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if len(groups) and grp_off[-1] else np.zeros(1, np.uint32)
         out_off = np.concatenate([[0], np.cumsum(need)]).astype(np.uint64)
@@ -1158,6 +1212,79 @@ class Context(object):
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self._check(self._lib.pep_allele_diff_times(self._h, C.byref(a), C.byref(b), C.byref(c)), 'pep_allele_diff_times')
         return a.value, b.value, c.value
+
+    # ---- K16
+    def group_verdicts(self, packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail=True, out_budget=1 << 30):
+        """The divergence verdicts of filt_per_group (PEPPAN.py:335-344, 352-366, 371-392) for many groups at once, decided on the GPU.  Rows and
+        groups as for allele_diff; genomes: per group the genome id of every row; inparalog: one flag per group; gd: (keys, values, default) as
+        orthofilter.gd_table makes them.  -> per group (verdict, tri, leader): verdict 0 not divergent / 1 divergent, no pair beyond its bound /
+        2 a pair beyond; for verdict 2 and detail=True tri int32[n(n-1)/2, 2] (K15's packed upper triangle) and leader uint32[n] (the row that
+        leads row j in the reference's leader grouping), else None.  Only those leave the device per pair; the verdicts cost one byte a group.
+        The packed triangles are reserved on the device for EVERY group, so a batch whose triangles exceed `out_budget` bytes, or whose bit
+        planes exceed the library's budget, is split exactly as allele_diff splits; the results do not depend on where."""
+        out_budget = min(int(out_budget), ALLELE_DIFF_MAX_BYTES)
+        packed, row_off, row_len, groups, genomes, inparalog = _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog)
+        n = np.array([len(g) for g in groups], dtype=np.int64)
+        need = 8 * (n * (n - 1) // 2)                                  # bytes of triangle per group
+        row_planes = 24 * ((3 * ((row_len.astype(np.int64) + 2) // 3) + 63) // 64)
+        if any(len(g) and int(g.max()) >= len(row_len) for g in groups):
+            return self._group_verdicts_call(packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail, n, True)      # the library's check reports it
+        planes = np.array([int(row_planes[g].sum()) for g in groups], dtype=np.int64)
+        over = np.flatnonzero(need > out_budget)
+        if len(over):
+            raise PepError('group_verdicts: group %d (%d rows) needs %d bytes of triangle, the budget is %d' % (over[0], n[over[0]], need[over[0]], out_budget))
+        over = np.flatnonzero(planes > ALLELE_DIFF_MAX_BYTES)
+        if len(over):
+            raise PepError('group_verdicts: group %d (%d rows) needs %d bytes of bit planes, the budget is %d' % (over[0], n[over[0]], planes[over[0]], ALLELE_DIFF_MAX_BYTES))
+        results, lo = [], 0
+        self._verdict_stats = [np.zeros(4), 0]
+        while lo < len(groups):
+            hi, total, pl = lo, 0, 0
+            while hi < len(groups) and total + need[hi] <= out_budget and pl + planes[hi] <= ALLELE_DIFF_MAX_BYTES:
+                total += int(need[hi])
+                pl += int(planes[hi])
+                hi += 1
+            whole = lo == 0 and hi == len(groups) and int(row_planes.sum()) <= ALLELE_DIFF_MAX_BYTES
+            results += self._group_verdicts_call(packed, row_off, row_len, groups[lo:hi], genomes[lo:hi], inparalog[lo:hi], gd, self_id, detail, n[lo:hi], whole)
+            lo = hi
+        return results
+
+    def _group_verdicts_call(self, packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail, n, whole):
+        if not whole and len(groups) and int(n.sum()):
+            packed, row_off, row_len, groups = _rows_of_groups(packed, row_off, row_len, groups, n)
+        args, keep = _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd)
+        verdict = np.zeros(max(len(groups), 1), dtype=np.uint8)
+        handle = C.c_void_p()
+        self._check(self._lib.pep_group_verdicts(self._h, *args, C.c_double(self_id), _ptr(verdict), C.byref(handle)), 'pep_group_verdicts')
+        try:
+            res = []
+            for g in range(len(groups)):
+                tri = leader = None
+                if detail and verdict[g] == 2:
+                    pairs = C.c_uint64()
+                    self._check(self._lib.pep_verdict_detail_size(handle, C.c_uint32(g), C.byref(pairs)), 'pep_verdict_detail_size')
+                    tri, leader = np.empty((pairs.value, 2), dtype=np.int32), np.empty(int(n[g]), dtype=np.uint32)
+                    self._check(self._lib.pep_verdict_detail_copy(handle, C.c_uint32(g), _ptr(tri), _ptr(leader)), 'pep_verdict_detail_copy')
+                res.append((int(verdict[g]), tri, leader))
+            ms, moved = self.group_verdicts_times()
+            if getattr(self, '_verdict_stats', None) is not None:
+                self._verdict_stats[0] += ms
+                self._verdict_stats[1] += moved
+        finally:
+            self._lib.pep_verdict_result_free(handle)
+        return res
+
+    def group_verdicts_times(self):
+        """of the newest pep_group_verdicts library call: (float64[4] kernel times in ms - bit planes, edge, pairs, leaders - when set_timing(2) is on,
+        else zeros; bytes that call and the detail copies of its result sent to the host)"""
+        ms, moved = (C.c_double * 4)(), C.c_uint64()
+        self._check(self._lib.pep_group_verdicts_times(self._h, ms, C.byref(moved)), 'pep_group_verdicts_times')
+        return np.array(list(ms)), int(moved.value)
+
+    def group_verdicts_totals(self):
+        """the same two figures summed over the library calls of the newest group_verdicts (one per part of a split batch)"""
+        st = getattr(self, '_verdict_stats', None) or [np.zeros(4), 0]
+        return st[0].copy(), int(st[1])
 
     # ---- K13
     def sha1(self, seqs):

@@ -11,6 +11,7 @@
 //                  the packed upper triangle and / or [2, n, 2], plain vector stores.
 // About 14 VALU instructions per pair and 64 columns: the kernel is bound by its n^2 x 8 B of output, the call by the copy to the host.
 #include "common.h"
+#include "allelediff_tile.h"
 #include <algorithm>
 #include <chrono>
 #include <numeric>
@@ -18,16 +19,11 @@
 
 namespace {
 
-constexpr int K15_TILE = 64;        // pairs per tile side
-constexpr int K15_KW = 4;           // words of every plane staged per step
-constexpr uint64_t K15_NONE = ~0ull;
-
 struct DiffGroup {
     uint64_t rows_off;              // first entry of the group in grp_rows
     uint64_t tri_off, edge_off;     // first int32 pair of the group's packed triangle / [2, n, 2] block in the device output
     uint32_t n, words;              // rows; words per plane
 };
-struct DiffTile { uint32_t g, ti, tj, kind; };      // kind 0: pairs a < b of tile (ti, tj); 1: rows {0, n - 1} against columns of tile tj
 
 // Neither kernel is tuned: by the recorded event times (profiles/allele_diff_rate.txt) they are a few per cent of a call that is bound by the
 // copy of its output.  Known slack: allele_planes keeps only `words` lanes of a wavefront busy (16 of 64 for 1 002 nt), each walking 64 digits
@@ -79,54 +75,11 @@ __global__ __launch_bounds__(256) void allele_diff(const DiffTile *__restrict__ 
                                                    const uint32_t *__restrict__ grp_rows, const uint64_t *__restrict__ plane_off,
                                                    const unsigned long long *__restrict__ planes, int2 *__restrict__ out)
 {
-    // [plane * KW + word][row]: the threads of a wavefront read 16 consecutive B rows (no bank conflict) and 4 A rows (broadcast)
-    __shared__ unsigned long long sA[3 * K15_KW][K15_TILE], sB[3 * K15_KW][K15_TILE];
-    __shared__ uint64_t offA[K15_TILE], offB[K15_TILE];
     const DiffTile T = tiles[blockIdx.x];
     const DiffGroup G = groups[T.g];
-    const uint32_t *idx = grp_rows + G.rows_off;
-    const uint32_t tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    if (tid < K15_TILE) {
-        uint64_t a = (uint64_t)T.ti * K15_TILE + tid;
-        if (T.kind == 1) a = tid == 0 ? 0 : tid == 1 ? (uint64_t)G.n - 1 : G.n;
-        offA[tid] = a < G.n ? plane_off[idx[a]] : K15_NONE;
-    } else if (tid < 2 * K15_TILE) {
-        const uint64_t b = (uint64_t)T.tj * K15_TILE + (tid - K15_TILE);
-        offB[tid - K15_TILE] = b < G.n ? plane_off[idx[b]] : K15_NONE;
-    }
+    const uint32_t tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     uint32_t mis[4][4], cmp[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mis[i][j] = cmp[i][j] = 0;
-    for (uint32_t w0 = 0; w0 < G.words; w0 += K15_KW) {
-        __syncthreads();                                            // the previous step's words are consumed (first step: offA / offB are written)
-        for (uint32_t e = tid; e < 2 * 3 * K15_KW * K15_TILE; e += 256) {
-            const uint32_t panel = e / (3 * K15_KW * K15_TILE), rem = e % (3 * K15_KW * K15_TILE), pw = rem / K15_TILE, row = rem % K15_TILE;
-            const uint32_t plane = pw / K15_KW, w = w0 + pw % K15_KW;
-            const uint64_t off = panel ? offB[row] : offA[row];
-            const unsigned long long v = (off != K15_NONE && w < G.words) ? planes[off + (uint64_t)plane * G.words + w] : 0ull;
-            if (panel) sB[pw][row] = v; else sA[pw][row] = v;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int k = 0; k < K15_KW; ++k) {                          // (unrolled, the four steps' LDS reads are hoisted together: 195 VGPRs instead of 95)
-            unsigned long long av[4], a0[4], a1[4], bv[4], b0[4], b1[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                av[i] = sA[k][ty * 4 + i]; a0[i] = sA[K15_KW + k][ty * 4 + i]; a1[i] = sA[2 * K15_KW + k][ty * 4 + i];
-                bv[i] = sB[k][tx + 16 * i]; b0[i] = sB[K15_KW + k][tx + 16 * i]; b1[i] = sB[2 * K15_KW + k][tx + 16 * i];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned long long c = av[i] & bv[j];
-                    cmp[i][j] += (uint32_t)__popcll(c);
-                    mis[i][j] += (uint32_t)__popcll(c & ((a0[i] ^ b0[j]) | (a1[i] ^ b1[j])));
-                }
-        }
-    }
+    k15_tile_counts(grp_rows + G.rows_off, G.n, G.words, T, plane_off, planes, mis, cmp);     // (allelediff_tile.h: shared with K16)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -143,6 +96,12 @@ __global__ __launch_bounds__(256) void allele_diff(const DiffTile *__restrict__ 
 }
 
 }  // namespace
+
+void pep_k15_queue_planes(hipStream_t st, uint64_t n_rows, const uint8_t *d_packed, const uint64_t *d_row_off, const uint32_t *d_row_len,
+                          const uint64_t *d_plane_off, unsigned long long *d_planes, uint32_t *d_bad_row)
+{
+    hipLaunchKernelGGL(allele_planes, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, st, n_rows, d_packed, d_row_off, d_row_len, d_plane_off, d_planes, d_bad_row);
+}
 
 int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
                         uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
@@ -249,8 +208,8 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
     {
         std::optional<EventTimer> tm;
         if (timed) tm.emplace(st);
-        hipLaunchKernelGGL(allele_planes, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, st, n_rows, W[0].as<const uint8_t>(), W[1].as<const uint64_t>(),
-                           W[2].as<const uint32_t>(), W[3].as<const uint64_t>(), W[4].as<unsigned long long>(), W[9].as<uint32_t>());
+        pep_k15_queue_planes(st, n_rows, W[0].as<const uint8_t>(), W[1].as<const uint64_t>(), W[2].as<const uint32_t>(), W[3].as<const uint64_t>(),
+                             W[4].as<unsigned long long>(), W[9].as<uint32_t>());
         if (timed) ctx->k15_ms[0] = tm->stop();
     }
     {

@@ -544,7 +544,7 @@ void pep_ctx_destroy(pep_ctx *ctx)
     DevBuf *bufs[] = {&ctx->sub_lds, &ctx->d_params, &ctx->scan_state[0].buf, &ctx->scan_state[1].buf, &ctx->fused_state[0].buf, &ctx->fused_state[1].buf, &ctx->fused_state[2].buf, &ctx->fused_state[3].buf, &ctx->d_min_score, &ctx->d_trace_mode, &ctx->d_trace_defer, &ctx->d_k1_base, &ctx->d_k1_seg, &ctx->d_k1_long, &ctx->d_k1_spec, &ctx->d_k1_tiles, &ctx->d_t_class, &ctx->d_t_subject, &ctx->d_nt_match, &ctx->q_nt.nt, &ctx->q_nt.off, &ctx->r_nt.nt, &ctx->r_nt.off,
                       &ctx->q.res, &ctx->q.off, &ctx->q.len, &ctx->t.res, &ctx->t.off, &ctx->t.len, &ctx->q.blk2seq, &ctx->t.blk2seq,
                       &ctx->sort_state, &ctx->sort_hist, &ctx->d_set, &ctx->d_zero, &ctx->d_k1_desc_q, &ctx->d_k1_desc_t, &ctx->d_self_delta, &ctx->d_self_t, &ctx->d_mail_copy,
-                      &ctx->nucl_q.d_off, &ctx->nucl_q.d_len, &ctx->nucl_q.d_desc, &ctx->nucl_t.d_off, &ctx->nucl_t.d_len, &ctx->nucl_t.d_desc, &ctx->nucl_t.d_first};
+                      &ctx->nucl_q.d_off, &ctx->nucl_q.d_len, &ctx->nucl_q.d_desc, &ctx->nucl_t.d_off, &ctx->nucl_t.d_len, &ctx->nucl_t.d_desc, &ctx->nucl_t.d_first, &ctx->k16_tri, &ctx->k16_leader};
     for (DevBuf *b : bufs) dev_release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1134,6 +1134,54 @@ int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pair
     *ms_planes = ctx->k15_ms[0];
     *ms_pairs = ctx->k15_ms[1];
     *ms_copy_back = ctx->k15_ms[2];
+    return PEP_OK;
+}
+
+int pep_group_verdicts_check(const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *grp_off,
+                             const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key, const double *gd_val,
+                             uint64_t n_gd, const double *gd_default, double self_id, char *msg, uint64_t msg_cap)
+{
+    std::string text;
+    const int rc = pep_k16_check(packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_genome, grp_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, text);
+    if (msg && msg_cap) {
+        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
+        memcpy(msg, text.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
+}
+
+int pep_group_verdicts(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,
+                       const uint64_t *grp_off, const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key,
+                       const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *verdict, pep_verdict_result **detail)
+{
+    if (!ctx) return PEP_ERR_ARG;
+    if (!detail || (n_groups && !verdict)) return pep_fail(ctx, PEP_ERR_ARG, "pep_group_verdicts: null table");
+    *detail = nullptr;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return pep_k16_group_verdicts(ctx, packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_genome, grp_inparalog, gd_key, gd_val, n_gd, gd_default, self_id,
+                                  verdict, detail);
+}
+
+int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs)
+{
+    if (!res || !n_pairs) return PEP_ERR_ARG;
+    return pep_k16_detail_size(res, g, n_pairs);
+}
+
+int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *tri, uint32_t *leader)
+{
+    if (!res) return PEP_ERR_ARG;
+    return pep_k16_detail_copy(res, g, tri, leader);
+}
+
+void pep_verdict_result_free(pep_verdict_result *res) { pep_k16_result_free(res); }
+
+int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host)
+{
+    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
+    for (int k = 0; k < 4; ++k) ms[k] = ctx->k16_ms[k];
+    *bytes_to_host = ctx->k16_bytes_to_host;
     return PEP_OK;
 }
 

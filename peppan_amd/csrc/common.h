@@ -195,6 +195,10 @@ struct pep_ctx {
     DevBuf d_mail_copy;                     // the alignment stage's counter block outside d_zero (trace.hip: emit -> pack_out, K10)
     bool zero_ok[4] = {false, false, false, false};     // which consumer regions of d_zero are still untouched since that fill (PEP_ZC_*)
     double k15_ms[3] = {0., 0., 0.};         // the newest pep_allele_diff: kernel times (planes, pairs) when pep_set_timing is 2, host time of the output's way back (allelediff.hip)
+    double k16_ms[4] = {0., 0., 0., 0.};     // the newest pep_group_verdicts: kernel times (planes, edge, pairs, leaders) when pep_set_timing is 2 (divergence.hip)
+    uint64_t k16_bytes_to_host = 0;          // ... and what it and the detail copies of its result sent to the host
+    uint64_t k16_serial = 0;                 // counts pep_group_verdicts calls: a pep_verdict_result is live while its serial is the newest
+    DevBuf k16_tri, k16_leader;              // grow-only: packed triangles and leaders of the newest pep_group_verdicts (read by pep_verdict_detail_copy)
     // stats of the last search
     pep_stats stats;
 };
@@ -347,6 +351,16 @@ int pep_k12_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off,
 int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
                         uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
                         int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap);
+// ---- divergence.hip (K16)
+int pep_k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *h_grp_off,
+                  const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
+                  const double *gd_default, double self_id, std::string &msg);      // every table check, no device
+int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
+                           const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key,
+                           const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *h_verdict, pep_verdict_result **detail);
+int pep_k16_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs);
+int pep_k16_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uint32_t *h_leader);
+void pep_k16_result_free(pep_verdict_result *res);
 // ---- dedup.hip (K13)
 int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest);
 int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep);

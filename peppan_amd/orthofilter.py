@@ -2,12 +2,17 @@
 
     compare_seq, compare_seqX   PEPPAN.py:296-316   drop-ins for the reference's two numba kernels
     group_differences           PEPPAN.py:330-333 + :346 + :370 for a whole `to_run` list (:624-626) in one GPU batch
+    group_verdicts              PEPPAN.py:335-392: what filt_per_group decides from those differences, decided on the GPU (K16); per-pair data
+                                comes back only for the groups that go on to the tree test
+    gd_table, distances_from_diff, incompatible_of   the host halves of it (the exp() per genome pair; :371-380; :400-406)
 
 Both counts are sums over columns, so the rows never leave the base-5 packing of the .seq store (mapbsn.encodeSeq): K15
 (csrc/allelediff.hip, Context.allele_diff) turns the packed bytes into bit planes and counts with population counts.  The float layer
-of filt_per_group (checkDiv, distances, the tree) is not here: see DESIGN.md section 8.  There is no CPU fallback.
+of filt_per_group up to the decision to build a tree is K16 (csrc/divergence.hip, Context.group_verdicts); the tree itself and its cutting
+are not here: see DESIGN.md section 8.  There is no CPU fallback.
 The drop-ins and group_differences share one cached context per process and device; close() releases it.
 """
+import collections
 import os
 
 import numpy as np
@@ -15,7 +20,8 @@ import numpy as np
 from . import _native as N
 from .mapbsn import MapBsn
 
-__all__ = ['compare_seq', 'compare_seqX', 'group_differences', 'iter_group_differences', 'pack_rows', 'close']
+__all__ = ['compare_seq', 'compare_seqX', 'group_differences', 'iter_group_differences', 'pack_rows', 'close',
+           'group_verdicts', 'gd_table', 'distances_from_diff', 'incompatible_of', 'GdTable', 'GroupVerdict']
 
 _CODE = np.full(256, 255, dtype=np.uint8)
 _CODE[[0, 65, 67, 71, 84]] = (0, 1, 2, 3, 4)
@@ -102,8 +108,9 @@ def compare_seqX(seqs, diff, device=None):
     return diff
 
 
-def iter_group_differences(seq_store, mats, ref_lens, edge=True, full=True, device=None, out_budget=1 << 30):
-    """group_differences as a generator: the GPU batch runs on the first next(); the int64 squares are made one group at a time"""
+def _read_groups(seq_store, mats, ref_lens):
+    """the packed rows of the groups' loci (column 5 of every table: member id // 1000, row id % 1000 of the store, PEPPAN.py:331), as they lie
+    in the store -> (packed, row_off, row_len, one array of row indices per group)"""
     own = not isinstance(seq_store, MapBsn)
     store = MapBsn(seq_store) if own else seq_store
     try:
@@ -127,8 +134,14 @@ def iter_group_differences(seq_store, mats, ref_lens, edge=True, full=True, devi
             store.close()
     packed = np.concatenate(rows) if rows else np.zeros(0, np.uint8)
     row_off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.uint64)
+    return packed, row_off, np.array(row_len, dtype=np.uint32), groups
+
+
+def iter_group_differences(seq_store, mats, ref_lens, edge=True, full=True, device=None, out_budget=1 << 30):
+    """group_differences as a generator: the GPU batch runs on the first next(); the int64 squares are made one group at a time"""
+    packed, row_off, row_len, groups = _read_groups(seq_store, mats, ref_lens)
     mode = (1 if full else 0) | (2 if edge else 0)
-    res = _context(device).allele_diff(packed, row_off, np.array(row_len, dtype=np.uint32), groups, mode, out_budget=out_budget) if mode else [(None, None)] * len(groups)
+    res = _context(device).allele_diff(packed, row_off, row_len, groups, mode, out_budget=out_budget) if mode else [(None, None)] * len(groups)
     for g, (tri, strip) in zip(groups, res):
         n = len(g)
         diffX = diff = None
@@ -151,3 +164,115 @@ def group_differences(seq_store, mats, ref_lens, edge=True, full=True, device=No
     without being decoded on the host.  -> per group (diffX, diff): what compare_seqX / compare_seq return for zero-filled int64[n, n, 2]
     (None for the one not asked for: edge=False / full=False)."""
     return list(iter_group_differences(seq_store, mats, ref_lens, edge, full, device, out_budget))
+
+
+GdTable = collections.namedtuple('GdTable', 'keys vals default self_id allowed_sigma')
+
+
+def gd_table(global_differences, self_id, allowed_sigma):
+    """The host half of K16: the one transcendental of checkDiv / distances (PEPPAN.py:341, :378) depends on the genome pair alone, so it is
+    evaluated here, with numpy as the reference writes it, once per entry of global_differences and once for the default (0.5, 0.6) of a
+    missing pair (:340, :377).  global_differences: the dict (g1, g2) -> (mean, sigma) or the [k, 2] object array get_global_difference saves
+    (:1666; dict(np.load(...)) at :328).  -> GdTable: keys uint64[k] = g1 << 32 | g2 ascending, vals float64[k, 3] = (gd0,
+    gd0 * exp(gd1 * sqrt(allowed_sigma)), gd0 * exp(gd1 * allowed_sigma)), default float64[3].  A key with g1 > g2 can never be looked up
+    (the reference sorts the pair, :340) and is left out."""
+    if not (np.isfinite(self_id) and self_id > 0):
+        raise ValueError('self_id must be finite and > 0, not %r' % (self_id,))
+    if not (np.isfinite(allowed_sigma) and allowed_sigma >= 0):
+        raise ValueError('allowed_sigma must be finite and >= 0, not %r' % (allowed_sigma,))
+    if not isinstance(global_differences, dict):
+        global_differences = dict(global_differences)
+    items = [(int(k[0]), int(k[1]), float(v[0]), float(v[1])) for k, v in global_differences.items() if k[0] <= k[1]]
+    if any(g1 < 0 or g2 >= 1 << 32 for g1, g2, _, _ in items):
+        raise ValueError('genome ids must fit 32 bits')
+    items.sort()
+    gd0 = np.array([i[2] for i in items] + [0.5], dtype=np.float64)
+    gd1 = np.array([i[3] for i in items] + [0.6], dtype=np.float64)
+    vals = np.stack([gd0, gd0 * np.exp(gd1 * np.sqrt(allowed_sigma)), gd0 * np.exp(gd1 * allowed_sigma)], axis=1)
+    if not (np.isfinite(vals).all() and (vals > 0).all()):
+        raise ValueError('global_differences holds a pair whose bound is not finite and > 0')
+    keys = np.array([(i[0] << 32) | i[1] for i in items], dtype=np.uint64)
+    return GdTable(keys, np.ascontiguousarray(vals[:-1]), vals[-1].copy(), float(self_id), allowed_sigma)
+
+
+def _gd_of_pairs(gd, ga, gb, aln):
+    """(gd0, checkDiv's denominator, the distances' denominator) of every pair: genome ids ga, gb and aln, arrays of one shape"""
+    lo, hi = np.minimum(ga, gb).astype(np.uint64), np.maximum(ga, gb).astype(np.uint64)
+    key = (lo << np.uint64(32)) | hi
+    at = np.searchsorted(gd.keys, key)
+    hit = at < len(gd.keys)
+    hit[hit] = gd.keys[at[hit]] == key[hit]
+    vals = np.concatenate([gd.vals, gd.default[None, :]])
+    row = np.where(hit, at, len(gd.keys))
+    same = ga == gb
+    own = np.maximum(gd.self_id, 2.0 / aln)
+    return np.where(same, own, vals[row, 0]), np.where(same, own, vals[row, 1]), np.where(same, own, vals[row, 2])
+
+
+def distances_from_diff(diff, genomes, gd):
+    """PEPPAN.py:371-380 by elementwise numpy: diff float64[n, n, 2] with its upper triangle filled (compare_seq's), the genome id of every row
+    (column 1 of the group's table), gd from gd_table -> distances float64[n, n, 2], symmetric, zero on the diagonal."""
+    diff = np.asarray(diff, dtype=np.float64)
+    n = diff.shape[0]
+    genomes = np.asarray(genomes).astype(np.int64)
+    distances = np.zeros((n, n, 2), dtype=np.float64)
+    a, b = np.triu_indices(n, 1)
+    mut, aln = diff[a, b, 0], diff[a, b, 1]
+    gd0, _, den = _gd_of_pairs(gd, genomes[a], genomes[b], aln)
+    d = mut / aln / den
+    distances[a, b, 0] = distances[b, a, 0] = d / gd0
+    distances[a, b, 1] = distances[b, a, 1] = 1 / gd0
+    return distances
+
+
+def incompatible_of(distances, groups):
+    """PEPPAN.py:400-406 with the reference's own expression (the order of a float sum is numpy's business) -> (incompatible float64[n, n, 2],
+    needs_tree: whether the reference goes on to build a tree, :406-407)"""
+    incompatible = np.zeros(shape=distances.shape, dtype=float)
+    for i1, g1 in enumerate(groups):
+        for i2 in range(i1 + 1, len(groups)):
+            g2 = groups[i2]
+            incompatible[g2[0], g1[0], :] = incompatible[g1[0], g2[0], :] = np.sum(distances[g1][:, g2, :], (0, 1))
+    return incompatible, not bool(np.all(incompatible[:, :, 0] <= incompatible[:, :, 1]))
+
+
+class GroupVerdict(object):
+    """verdict: 0 not divergent (the reference returns [mat] at :368), 1 divergent but no pair beyond its bound (:484), 2 a pair beyond (:383).
+    For verdict 2 and detail=True also diff, groups, distances, incompatible, needs_tree; None otherwise."""
+    __slots__ = ('verdict', 'diff', 'groups', 'distances', 'incompatible', 'needs_tree')
+
+    def __init__(self, verdict):
+        self.verdict = verdict
+        self.diff = self.groups = self.distances = self.incompatible = self.needs_tree = None
+
+
+def group_verdicts(seq_store, to_run_groups, global_differences, params, detail=True, device=None, out_budget=1 << 30):
+    """filt_per_group (PEPPAN.py:326-407) up to its decision to build a tree, for a whole `to_run` list (:624) in one GPU batch.
+
+    seq_store: the .seq store (MapBsn or its path); to_run_groups: per group (mat, inparalog, ref_len, ...) as filt_genes collects them
+    (column 1 of mat = genome id, column 5 = locus id); global_differences: the dict, the saved [k, 2] object array, or a GdTable;
+    params: self_id and allowed_sigma.  -> one GroupVerdict per group.  The packed rows go from the store to ONE Context.group_verdicts
+    batch; the device decides every verdict, and per-pair data comes back only for verdict 2 (when detail): diff float64[n, n, 2] as :370
+    leaves it, groups as :383-392 leave them, distances (:371-380, by distances_from_diff on the host) and incompatible / needs_tree
+    (:400-406).  The tree and its cutting (:409-482) stay with the caller."""
+    gd = global_differences if isinstance(global_differences, GdTable) else gd_table(global_differences, params['self_id'], params['allowed_sigma'])
+    mats = [np.asarray(t[0]) for t in to_run_groups]
+    packed, row_off, row_len, groups = _read_groups(seq_store, mats, [t[2] for t in to_run_groups])
+    genomes = [m[:, 1].astype(np.int64) if len(m) else np.zeros(0, np.int64) for m in mats]
+    if any(len(g) and (g.min() < 0 or g.max() >= 1 << 32) for g in genomes):
+        raise ValueError('genome ids must fit 32 bits')
+    inparalog = np.array([1 if t[1] else 0 for t in to_run_groups], dtype=np.uint8)
+    res = _context(device).group_verdicts(packed, row_off, row_len, groups, genomes, inparalog, gd, gd.self_id, detail=detail, out_budget=out_budget)
+    out = []
+    for genome, (verdict, tri, leader) in zip(genomes, res):
+        v = GroupVerdict(verdict)
+        if tri is not None:
+            n = len(leader)
+            v.diff = _fill_upper(np.zeros((n, n, 2), dtype=np.float64), tri)
+            order = np.argsort(leader, kind='stable')
+            cuts = np.flatnonzero(np.diff(leader[order])) + 1
+            v.groups = [part.tolist() for part in np.split(order, cuts)]
+            v.distances = distances_from_diff(v.diff, genome, gd)
+            v.incompatible, v.needs_tree = incompatible_of(v.distances, v.groups)
+        out.append(v)
+    return out
