@@ -248,37 +248,69 @@ def _rows_of_groups(packed, row_off, row_len, groups, n):
     return packed[src], new_off, row_len[used], np.split(inv.astype(np.uint32), np.cumsum(n)[:-1])
 
 
-def _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd):
-    """the arrays of one pep_group_verdicts / pep_group_verdicts_check call, in the order of their leading arguments, + the list that keeps them alive"""
+def _group_inputs(who, packed, row_off, row_len, groups):
+    """the row table and the groups of an allele_diff / group_verdicts call as flat contiguous arrays of the library's types"""
+    packed = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
+    row_off = np.ascontiguousarray(row_off, dtype=np.uint64).reshape(-1)
+    row_len = np.ascontiguousarray(row_len, dtype=np.uint32).reshape(-1)
+    if len(row_off) != len(row_len) + 1:
+        raise ValueError('%s: row_off needs one entry more than row_len' % who)
+    return packed, row_off, row_len, [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+
+
+def _group_tables(packed, row_len, groups, per_group=()):
+    """what the library reads of a batch: (packed, row_len, grp_off, grp_rows, *per_group), an array without entries replaced by one element
+    (the library is handed no null pointer) - the caller keeps them alive over the call"""
     n = np.array([len(g) for g in groups], dtype=np.int64)
     grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
-    total = int(grp_off[-1])
-    grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if total else np.zeros(1, np.uint32)
-    grp_genome = np.ascontiguousarray(np.concatenate(genomes), dtype=np.uint32) if total else np.zeros(1, np.uint32)
+    grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if grp_off[-1] else np.zeros(0, np.uint32)
+    return [a if len(a) else np.zeros(1, a.dtype) for a in (packed, row_len, grp_off, grp_rows) + tuple(per_group)]
+
+
+def _plan_batch(who, noun, need, row_len, groups, out_budget):
+    """Splits a batch greedily into library calls within `out_budget` bytes of output (need: bytes per group; `noun` names them in the message) and
+    the library's budget of bit planes -> [(lo, hi, whole)]: groups[lo:hi] per call, whole = the call takes the row table as it is, else only the
+    rows its groups use.  PepError when one group alone exceeds a budget."""
+    # bytes of bit planes per row (24 per 64 digits); per group an upper bound of what its rows add to a call (a row shared by two groups counts twice)
+    row_planes = 24 * ((3 * ((row_len.astype(np.int64) + 2) // 3) + 63) // 64)
+    if any(len(g) and int(g.max()) >= len(row_len) for g in groups):
+        # a row index out of range: the whole batch goes to the library as it is, whose check reports it (the same text, split or not)
+        return [(0, len(groups), True)]
+    planes = np.array([int(row_planes[g].sum()) for g in groups], dtype=np.int64)
+    for what, asked, budget in ((noun, need, out_budget), ('bit planes', planes, ALLELE_DIFF_MAX_BYTES)):
+        over = np.flatnonzero(asked > budget)
+        if len(over):
+            raise PepError('%s: group %d (%d rows) needs %d bytes of %s, the budget is %d' % (who, over[0], len(groups[over[0]]), asked[over[0]], what, budget))
+    plan, lo = [], 0
+    while lo < len(groups):
+        hi, total, pl = lo, 0, 0
+        while hi < len(groups) and total + need[hi] <= out_budget and pl + planes[hi] <= ALLELE_DIFF_MAX_BYTES:
+            total += int(need[hi])
+            pl += int(planes[hi])
+            hi += 1
+        plan.append((lo, hi, lo == 0 and hi == len(groups) and int(row_planes.sum()) <= ALLELE_DIFF_MAX_BYTES))
+        lo = hi
+    return plan
+
+
+def _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd):
+    """the arrays of one pep_group_verdicts / pep_group_verdicts_check call, in the order of their leading arguments, + the list that keeps them alive"""
+    grp_genome = np.ascontiguousarray(np.concatenate(genomes), dtype=np.uint32) if len(genomes) else np.zeros(0, np.uint32)
     keys, vals, default = gd[:3]
     keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
     vals = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1, 3)
     default = np.ascontiguousarray(default, dtype=np.float64).reshape(3)
     if len(keys) != len(vals):
         raise ValueError('group_verdicts: one row of values per key')
-    pk = packed if len(packed) else np.zeros(1, np.uint8)
-    rl = row_len if len(row_len) else np.zeros(1, np.uint32)
-    ip = inparalog if len(inparalog) else np.zeros(1, np.uint8)
-    kk = keys if len(keys) else np.zeros(1, np.uint64)
-    vv = vals if len(vals) else np.zeros((1, 3), np.float64)
-    keep = [pk, row_off, rl, grp_off, grp_rows, grp_genome, ip, kk, vv, default]
+    pk, rl, grp_off, grp_rows, grp_genome, ip, kk, vv = keep = _group_tables(packed, row_len, groups, (grp_genome, inparalog, keys, vals))
+    keep += [row_off, default]
     args = [_ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off), _ptr(grp_rows), _ptr(grp_genome), _ptr(ip),
             _ptr(kk), _ptr(vv), C.c_uint64(len(keys)), _ptr(default)]
     return args, keep
 
 
 def _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog):
-    packed = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
-    row_off = np.ascontiguousarray(row_off, dtype=np.uint64).reshape(-1)
-    row_len = np.ascontiguousarray(row_len, dtype=np.uint32).reshape(-1)
-    if len(row_off) != len(row_len) + 1:
-        raise ValueError('group_verdicts: row_off needs one entry more than row_len')
-    groups = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+    packed, row_off, row_len, groups = _group_inputs('group_verdicts', packed, row_off, row_len, groups)
     genomes = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in genomes]
     inparalog = np.ascontiguousarray(inparalog, dtype=np.uint8).reshape(-1)
     if len(genomes) != len(groups) or len(inparalog) != len(groups) or any(len(a) != len(b) for a, b in zip(groups, genomes)):
@@ -858,6 +890,7 @@ class Context(object):
         self._view = None
         self._nt_match_on, self.last_nt_match = False, None
         self._grouping, self.labels = 0, None           # set_grouping: K10 as the tail of every search
+        self._verdict_stats = [np.zeros(4), 0]          # kernel times and bytes to the host, summed over the library calls of the newest group_verdicts
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1148,12 +1181,7 @@ class Context(object):
         budget.  The arrays of one library call are views into ONE output buffer: holding any of them keeps that whole buffer alive
         (copy what is to be kept for long)."""
         out_budget = min(int(out_budget), ALLELE_DIFF_MAX_BYTES)
-        packed = np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)
-        row_off = np.ascontiguousarray(row_off, dtype=np.uint64).reshape(-1)
-        row_len = np.ascontiguousarray(row_len, dtype=np.uint32).reshape(-1)
-        if len(row_off) != len(row_len) + 1:
-            raise ValueError('allele_diff: row_off needs one entry more than row_len')
-        groups = [np.ascontiguousarray(g, dtype=np.uint32).reshape(-1) for g in groups]
+        packed, row_off, row_len, groups = _group_inputs('allele_diff', packed, row_off, row_len, groups)
         modes = np.full(len(groups), modes, dtype=np.uint8) if np.isscalar(modes) else np.ascontiguousarray(modes, dtype=np.uint8).reshape(-1)
         if len(modes) != len(groups):
             raise ValueError('allele_diff: one mode per group')
@@ -1161,41 +1189,19 @@ class Context(object):
         tri = np.where((modes & 1) > 0, n * (n - 1) // 2, 0)
         edge = np.where((modes & 2) > 0, 2 * n, 0)
         need = 2 * (tri + edge)                                       # int32 values per group
-        # bytes of bit planes per row (24 per 64 digits); per group an upper bound of what its rows add to a call (a row shared by two groups counts twice)
-        row_planes = 24 * ((3 * ((row_len.astype(np.int64) + 2) // 3) + 63) // 64)
-        if any(len(g) and int(g.max()) >= len(row_len) for g in groups):
-            # a row index out of range: the whole batch goes to the library as it is, whose check reports it (the same text, split or not)
-            return self._allele_diff_call(packed, row_off, row_len, groups, modes, n, tri, need, int(need.sum()), True)
-        planes = np.array([int(row_planes[g].sum()) for g in groups], dtype=np.int64)
-        over = np.flatnonzero(need * 4 > out_budget)
-        if len(over):
-            raise PepError('allele_diff: group %d (%d rows) needs %d bytes of output, the budget is %d' % (over[0], n[over[0]], need[over[0]] * 4, out_budget))
-        over = np.flatnonzero(planes > ALLELE_DIFF_MAX_BYTES)
-        if len(over):
-            raise PepError('allele_diff: group %d (%d rows) needs %d bytes of bit planes, the budget is %d' % (over[0], n[over[0]], planes[over[0]], ALLELE_DIFF_MAX_BYTES))
-        results, lo = [], 0
-        while lo < len(groups):
-            hi, total, pl = lo, 0, 0
-            while hi < len(groups) and (total + need[hi]) * 4 <= out_budget and pl + planes[hi] <= ALLELE_DIFF_MAX_BYTES:
-                total += int(need[hi])
-                pl += int(planes[hi])
-                hi += 1
-            whole = lo == 0 and hi == len(groups) and int(row_planes.sum()) <= ALLELE_DIFF_MAX_BYTES      # (else: only the rows the groups use)
-            results += self._allele_diff_call(packed, row_off, row_len, groups[lo:hi], modes[lo:hi], n[lo:hi], tri[lo:hi], need[lo:hi], total, whole)
-            lo = hi
+        results = []
+        for lo, hi, whole in _plan_batch('allele_diff', 'output', 4 * need, row_len, groups, out_budget):
+            results += self._allele_diff_call(packed, row_off, row_len, groups[lo:hi], modes[lo:hi], n[lo:hi], tri[lo:hi], need[lo:hi], whole)
         return results
 
-    def _allele_diff_call(self, packed, row_off, row_len, groups, modes, n, tri, need, total, whole):
+    def _allele_diff_call(self, packed, row_off, row_len, groups, modes, n, tri, need, whole):
         if not whole and len(groups):
             # part of a split batch: upload the rows these groups use, not the whole table
             packed, row_off, row_len, groups = _rows_of_groups(packed, row_off, row_len, groups, n)       # (indices are in range: allele_diff sends a batch with a bad one whole)
-        grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
-        grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if len(groups) and grp_off[-1] else np.zeros(1, np.uint32)
+        pk, rl, grp_off, grp_rows, md = _group_tables(packed, row_len, groups, (modes,))
         out_off = np.concatenate([[0], np.cumsum(need)]).astype(np.uint64)
+        total = int(out_off[-1])
         out = np.empty(max(total, 1), dtype=np.int32)
-        pk = packed if len(packed) else np.zeros(1, np.uint8)
-        rl = row_len if len(row_len) else np.zeros(1, np.uint32)
-        md = modes if len(modes) else np.zeros(1, np.uint8)
         self._check(self._lib.pep_allele_diff(self._h, _ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off),
                                               _ptr(grp_rows), _ptr(md), _ptr(out), _ptr(out_off), C.c_uint64(total)), 'pep_allele_diff')
         res = []
@@ -1225,28 +1231,10 @@ class Context(object):
         out_budget = min(int(out_budget), ALLELE_DIFF_MAX_BYTES)
         packed, row_off, row_len, groups, genomes, inparalog = _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog)
         n = np.array([len(g) for g in groups], dtype=np.int64)
-        need = 8 * (n * (n - 1) // 2)                                  # bytes of triangle per group
-        row_planes = 24 * ((3 * ((row_len.astype(np.int64) + 2) // 3) + 63) // 64)
-        if any(len(g) and int(g.max()) >= len(row_len) for g in groups):
-            return self._group_verdicts_call(packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail, n, True)      # the library's check reports it
-        planes = np.array([int(row_planes[g].sum()) for g in groups], dtype=np.int64)
-        over = np.flatnonzero(need > out_budget)
-        if len(over):
-            raise PepError('group_verdicts: group %d (%d rows) needs %d bytes of triangle, the budget is %d' % (over[0], n[over[0]], need[over[0]], out_budget))
-        over = np.flatnonzero(planes > ALLELE_DIFF_MAX_BYTES)
-        if len(over):
-            raise PepError('group_verdicts: group %d (%d rows) needs %d bytes of bit planes, the budget is %d' % (over[0], n[over[0]], planes[over[0]], ALLELE_DIFF_MAX_BYTES))
-        results, lo = [], 0
-        self._verdict_stats = [np.zeros(4), 0]
-        while lo < len(groups):
-            hi, total, pl = lo, 0, 0
-            while hi < len(groups) and total + need[hi] <= out_budget and pl + planes[hi] <= ALLELE_DIFF_MAX_BYTES:
-                total += int(need[hi])
-                pl += int(planes[hi])
-                hi += 1
-            whole = lo == 0 and hi == len(groups) and int(row_planes.sum()) <= ALLELE_DIFF_MAX_BYTES
+        plan = _plan_batch('group_verdicts', 'triangle', 8 * (n * (n - 1) // 2), row_len, groups, out_budget)
+        results, self._verdict_stats = [], [np.zeros(4), 0]
+        for lo, hi, whole in plan:
             results += self._group_verdicts_call(packed, row_off, row_len, groups[lo:hi], genomes[lo:hi], inparalog[lo:hi], gd, self_id, detail, n[lo:hi], whole)
-            lo = hi
         return results
 
     def _group_verdicts_call(self, packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail, n, whole):
@@ -1267,9 +1255,8 @@ class Context(object):
                     self._check(self._lib.pep_verdict_detail_copy(handle, C.c_uint32(g), _ptr(tri), _ptr(leader)), 'pep_verdict_detail_copy')
                 res.append((int(verdict[g]), tri, leader))
             ms, moved = self.group_verdicts_times()
-            if getattr(self, '_verdict_stats', None) is not None:
-                self._verdict_stats[0] += ms
-                self._verdict_stats[1] += moved
+            self._verdict_stats[0] += ms
+            self._verdict_stats[1] += moved
         finally:
             self._lib.pep_verdict_result_free(handle)
         return res
@@ -1283,8 +1270,7 @@ class Context(object):
 
     def group_verdicts_totals(self):
         """the same two figures summed over the library calls of the newest group_verdicts (one per part of a split batch)"""
-        st = getattr(self, '_verdict_stats', None) or [np.zeros(4), 0]
-        return st[0].copy(), int(st[1])
+        return self._verdict_stats[0].copy(), int(self._verdict_stats[1])
 
     # ---- K13
     def sha1(self, seqs):

@@ -10,20 +10,15 @@
 //                  (compare_seqX) is the same loop with a two-row A panel.  Output (mismatch + 1, comparable + 2) as int32 pairs:
 //                  the packed upper triangle and / or [2, n, 2], plain vector stores.
 // About 14 VALU instructions per pair and 64 columns: the kernel is bound by its n^2 x 8 B of output, the call by the copy to the host.
+// The checks of the row and group tables, their layout and the device prologue up to allele_planes are grouptable.h's, shared with K16.
 #include "common.h"
 #include "allelediff_tile.h"
+#include "grouptable.h"
 #include <algorithm>
 #include <chrono>
 #include <numeric>
-#include <optional>
 
 namespace {
-
-struct DiffGroup {
-    uint64_t rows_off;              // first entry of the group in grp_rows
-    uint64_t tri_off, edge_off;     // first int32 pair of the group's packed triangle / [2, n, 2] block in the device output
-    uint32_t n, words;              // rows; words per plane
-};
 
 // Neither kernel is tuned: by the recorded event times (profiles/allele_diff_rate.txt) they are a few per cent of a call that is bound by the
 // copy of its output.  Known slack: allele_planes keeps only `words` lanes of a wavefront busy (16 of 64 for 1 002 nt), each walking 64 digits
@@ -71,12 +66,12 @@ __global__ __launch_bounds__(256) void allele_planes(uint64_t n_rows, const uint
     if (bad) atomicMin(bad_row, (uint32_t)r);
 }
 
-__global__ __launch_bounds__(256) void allele_diff(const DiffTile *__restrict__ tiles, const DiffGroup *__restrict__ groups,
+__global__ __launch_bounds__(256) void allele_diff(const DiffTile *__restrict__ tiles, const GroupRec *__restrict__ groups,
                                                    const uint32_t *__restrict__ grp_rows, const uint64_t *__restrict__ plane_off,
                                                    const unsigned long long *__restrict__ planes, int2 *__restrict__ out)
 {
     const DiffTile T = tiles[blockIdx.x];
-    const DiffGroup G = groups[T.g];
+    const GroupRec G = groups[T.g];
     const uint32_t tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     uint32_t mis[4][4], cmp[4][4];
     k15_tile_counts(grp_rows + G.rows_off, G.n, G.words, T, plane_off, planes, mis, cmp);     // (allelediff_tile.h: shared with K16)
@@ -109,59 +104,15 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
 {
     ctx->k15_ms[0] = ctx->k15_ms[1] = ctx->k15_ms[2] = 0.;
     if (n_groups == 0) return PEP_OK;
-    if (n_rows >= 0xFFFFFFFFull) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_allele_diff: more than 2^32 - 2 rows");
-    // validate on the host so that a bad table is an error, not an out-of-bounds access; also lays out the buffers
-    std::vector<uint64_t> plane_off(n_rows + 1);
-    plane_off[0] = 0;
-    for (uint64_t r = 0; r < n_rows; ++r) {
-        const uint64_t s = ((uint64_t)h_row_len[r] + 2) / 3;
-        if (h_row_off[r + 1] < h_row_off[r] || h_row_off[r + 1] - h_row_off[r] != s)
-            return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: row " + std::to_string(r) + " does not hold ceil(row_len / 3) bytes");
-        plane_off[r + 1] = plane_off[r] + 3 * ((3 * s + 63) / 64);
-    }
-    if (h_grp_off[0] != 0) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: grp_off must start at 0");
-    std::vector<DiffGroup> groups(n_groups);
-    std::vector<DiffTile> tiles;
+    const GroupTables T{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows};
+    const GroupSpec S{"pep_allele_diff: ", "output", "tiles of pairs", 1};
+    GroupLayout L;
     std::vector<uint64_t> need(n_groups);           // int32 values of every group's output
-    uint64_t pairs = 0;
-    const auto over_budget = [&](uint32_t g) {             // at the first group that crosses it: `pairs` never grows past budget + one group (n < 2^31: no wrap)
-        return pep_fail(ctx, PEP_ERR_LIMIT, "pep_allele_diff: " + std::to_string(pairs * 8) + " bytes of output asked for, the device budget of one call is " +
-                                             std::to_string((uint64_t)PEP_ALLELE_DIFF_MAX_BYTES) + " (reached at group " + std::to_string(g) + ": split the batch)");
-    };
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        if (h_grp_off[g + 1] < h_grp_off[g]) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: grp_off must be non-decreasing");
-        const uint64_t n = h_grp_off[g + 1] - h_grp_off[g], before = pairs;
-        if (n >= 0x7FFFFFFFull) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_allele_diff: more than 2^31 - 2 rows in one group");
-        if (h_grp_mode[g] > 3) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: unknown mode bits of group " + std::to_string(g));
-        DiffGroup &G = groups[g];
-        G.rows_off = h_grp_off[g]; G.n = (uint32_t)n; G.words = 0; G.tri_off = G.edge_off = 0;
-        for (uint64_t k = h_grp_off[g]; k < h_grp_off[g + 1]; ++k) {
-            const uint32_t r = h_grp_rows[k];
-            if (r >= n_rows) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: row index " + std::to_string(r) + " of group " + std::to_string(g) + " out of range");
-            if (h_row_len[r] != h_row_len[h_grp_rows[h_grp_off[g]]])
-                return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: group " + std::to_string(g) + " mixes rows of different row_len");
-        }
-        if (n) G.words = (uint32_t)((plane_off[h_grp_rows[h_grp_off[g]] + 1] - plane_off[h_grp_rows[h_grp_off[g]]]) / 3);
-        const uint64_t nt = (n + K15_TILE - 1) / K15_TILE;
-        if ((h_grp_mode[g] & 1) && n > 1) {
-            G.tri_off = pairs;
-            pairs += n * (n - 1) / 2;
-            if (pairs * 8 > PEP_ALLELE_DIFF_MAX_BYTES) return over_budget(g);
-            for (uint64_t ti = 0; ti < nt; ++ti)
-                for (uint64_t tj = ti; tj < nt; ++tj) tiles.push_back(DiffTile{g, (uint32_t)ti, (uint32_t)tj, 0u});
-        }
-        if ((h_grp_mode[g] & 2) && n) {
-            G.edge_off = pairs;
-            pairs += 2 * n;
-            if (pairs * 8 > PEP_ALLELE_DIFF_MAX_BYTES) return over_budget(g);
-            for (uint64_t tj = 0; tj < nt; ++tj) tiles.push_back(DiffTile{g, 0u, (uint32_t)tj, 1u});
-        }
-        need[g] = 2 * (pairs - before);
-    }
-    if (tiles.size() > 0x7FFFFFFFull) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_allele_diff: more than 2^31 - 1 tiles of pairs in one call (split the batch)");
-    if (plane_off[n_rows] * 8 > PEP_ALLELE_DIFF_MAX_BYTES)
-        return pep_fail(ctx, PEP_ERR_LIMIT, "pep_allele_diff: " + std::to_string(plane_off[n_rows] * 8) + " bytes of bit planes asked for, the device budget of one call is " +
-                                             std::to_string((uint64_t)PEP_ALLELE_DIFF_MAX_BYTES) + " (split the batch)");
+    std::string msg;
+    const int rc = group_tables_check(T, S,
+        [&](uint32_t g, unsigned &want) { want = h_grp_mode[g]; return want > 3 ? "unknown mode bits of group " + std::to_string(g) : std::string(); },
+        [&](uint32_t g, const GroupRec &, uint64_t added) { need[g] = 2 * added; return 0; }, L, msg);
+    if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
     // where the caller wants the groups: inside out_cap, no two on the same values
     std::vector<uint32_t> order(n_groups);
     std::iota(order.begin(), order.end(), 0u);
@@ -174,58 +125,20 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
         if (h_out_off[g] < end_before) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: output of group " + std::to_string(g) + " overlaps another group's");
         end_before = h_out_off[g] + need[g];
     }
-    const uint64_t n_idx = h_grp_off[n_groups], n_bytes = h_row_off[n_rows];
-    if (tiles.empty()) {
+    if (L.tiles.empty()) {
         // nothing but empty groups, one-row triangles or groups without a mode bit: no kernel runs, so the bytes are looked at here
-        for (uint64_t k = 0; k < n_bytes; ++k)
-            if (h_packed[k] > 124) {
-                const uint64_t r = (uint64_t)(std::upper_bound(h_row_off, h_row_off + n_rows + 1, k) - h_row_off) - 1;
-                return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: row " + std::to_string(r) + " holds a byte above 124 (not three base-5 digits)");
-            }
+        for (uint64_t k = 0; k < h_row_off[n_rows]; ++k)
+            if (h_packed[k] > 124) return group_tables_bad_byte(ctx, S, (uint64_t)(std::upper_bound(h_row_off, h_row_off + n_rows + 1, k) - h_row_off) - 1);
         return PEP_OK;
     }
     DevBuf *W = ctx->ws;
-    hipStream_t st = ctx->stream;
-    PEP_TRY(dev_reserve(ctx, W[0], n_bytes + 1));
-    PEP_TRY(dev_reserve(ctx, W[1], (n_rows + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[2], (n_rows + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[3], (n_rows + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[4], (plane_off[n_rows] + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[5], (n_idx + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[6], (size_t)n_groups * sizeof(DiffGroup)));
-    PEP_TRY(dev_reserve(ctx, W[7], tiles.size() * sizeof(DiffTile)));
-    PEP_TRY(dev_reserve(ctx, W[8], (pairs + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[9], 256));
-    PEP_TRY(pep_h2d(ctx, W[0].p, h_packed, n_bytes));
-    PEP_TRY(pep_h2d(ctx, W[1].p, h_row_off, (n_rows + 1) * 8));
-    PEP_TRY(pep_h2d(ctx, W[2].p, h_row_len, n_rows * 4));
-    PEP_TRY(pep_h2d(ctx, W[3].p, plane_off.data(), (n_rows + 1) * 8));
-    PEP_TRY(pep_h2d(ctx, W[5].p, h_grp_rows, n_idx * 4));
-    PEP_TRY(pep_h2d(ctx, W[6].p, groups.data(), (size_t)n_groups * sizeof(DiffGroup)));
-    PEP_TRY(pep_h2d(ctx, W[7].p, tiles.data(), tiles.size() * sizeof(DiffTile)));
-    PEP_HIP(ctx, hipMemsetAsync(W[9].p, 0xFF, 4, st));
-    const bool timed = ctx->timing_level >= 2;
-    {
-        std::optional<EventTimer> tm;
-        if (timed) tm.emplace(st);
-        pep_k15_queue_planes(st, n_rows, W[0].as<const uint8_t>(), W[1].as<const uint64_t>(), W[2].as<const uint32_t>(), W[3].as<const uint64_t>(),
-                             W[4].as<unsigned long long>(), W[9].as<uint32_t>());
-        if (timed) ctx->k15_ms[0] = tm->stop();
-    }
-    {
-        std::optional<EventTimer> tm;
-        if (timed) tm.emplace(st);
-        hipLaunchKernelGGL(allele_diff, dim3((unsigned)tiles.size()), dim3(256), 0, st, W[7].as<const DiffTile>(), W[6].as<const DiffGroup>(),
-                           W[5].as<const uint32_t>(), W[3].as<const uint64_t>(), W[4].as<const unsigned long long>(), W[8].as<int2>());
-        if (timed) ctx->k15_ms[1] = tm->stop();
-    }
-    PEP_HIP(ctx, hipGetLastError());
-    uint32_t bad_row = 0xFFFFFFFFu;
-    PEP_TRY(pep_d2h_queue(ctx, &bad_row, W[9].p, 4));
-    PEP_HIP(ctx, pep_stream_wait(ctx));
-    pep_d2h_finish(ctx);
-    if (bad_row != 0xFFFFFFFFu)
-        return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: row " + std::to_string(bad_row) + " holds a byte above 124 (not three base-5 digits)");
+    PEP_TRY(dev_reserve(ctx, W[K15_WS_OUT], (L.pairs + 1) * 8));
+    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {}, ctx->k15_ms[0]));
+    pep_timed_stage(ctx, ctx->k15_ms[1], [&] {
+        hipLaunchKernelGGL(allele_diff, dim3((unsigned)L.tiles.size()), dim3(256), 0, ctx->stream, W[K15_WS_TILES].as<const DiffTile>(), W[K15_WS_GROUPS].as<const GroupRec>(),
+                           W[K15_WS_GRP_ROWS].as<const uint32_t>(), W[K15_WS_PLANE_OFF].as<const uint64_t>(), W[K15_WS_PLANES].as<const unsigned long long>(), W[K15_WS_OUT].as<int2>());
+    });
+    PEP_TRY(group_tables_finish(ctx, S));
     // groups that follow each other in the caller's buffer as they do on the device leave in one copy
     const auto copy_t0 = std::chrono::steady_clock::now();
     uint64_t dev_at = 0, run_dev = 0, run_host = 0, run = 0;
@@ -234,7 +147,7 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
         if (g < n_groups && run && h_out_off[g] == run_host + run) {
             run += need[g];
         } else {
-            if (run) PEP_TRY(pep_d2h_queue(ctx, h_out + run_host, W[8].as<const int32_t>() + run_dev, run * 4));
+            if (run) PEP_TRY(pep_d2h_queue(ctx, h_out + run_host, W[K15_WS_OUT].as<const int32_t>() + run_dev, run * 4));
             if (g == n_groups) break;
             run_host = h_out_off[g]; run_dev = dev_at; run = need[g];
         }

@@ -14,13 +14,15 @@
 // Every float decision is a chain of single correctly rounded double operations (__ddiv_rn / __dmul_rn: nothing to contract); the only
 // transcendental of the reference, exp, depends on the genome pair alone and arrives in a host-made table (gd0, denX, den) sorted by
 // g1 << 32 | g2, looked up by binary search.  Same-genome pairs use gd0 = fmax(self_id, 2 / aln) for all three.
+// The checks of the row and group tables, their layout and the device prologue up to allele_planes are K15's (grouptable.h); here: the gd table,
+// the grp_inparalog check, the edge-pair list and the 24-byte group record of the three kernels.
 #include "common.h"
 #include "allelediff_tile.h"
+#include "grouptable.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
-#include <optional>
 
 struct pep_verdict_result {
     pep_ctx *ctx = nullptr;
@@ -35,9 +37,8 @@ namespace {
 constexpr uint32_t K16_EDGE_PER_WAVE = 4;
 constexpr uint32_t K16_LDS_LEADERS = 4096;
 
-struct VGroup {
-    uint64_t rows_off;              // first entry of the group in grp_rows / grp_genome / leader
-    uint64_t tri_off;               // first int32 pair of the group's packed triangle
+struct VGroup {                     // a GroupRec as the three kernels here read it
+    uint64_t rows_off, tri_off;
     uint32_t n, words;
 };
 struct EdgePair { uint32_t g, a, b; };      // rows a, b (positions inside group g)
@@ -179,27 +180,23 @@ __global__ __launch_bounds__(256) void verdict_leaders(const VGroup *__restrict_
     }
 }
 
-struct Layout {
-    std::vector<uint64_t> plane_off;
-    std::vector<VGroup> groups;
-    std::vector<DiffTile> tiles;
+struct Layout : GroupLayout {
     std::vector<EdgePair> edges;
     std::vector<double> gd;         // [n_gd + 1][3]
-    uint64_t pairs = 0;
 };
+
+const GroupSpec K16_SPEC{"pep_group_verdicts: ", "triangles", "tiles or edge pairs", 2};
 
 bool k16_good(double v) { return std::isfinite(v) && v > 0.; }
 
-// every check of the tables, on the host, before anything is launched; also lays the device buffers out
-int k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *h_grp_off,
-              const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
+// every check of the tables, on the host, before anything is launched; also lays the device buffers out (the row and group tables: grouptable.h)
+int k16_check(const GroupTables &T, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
               const double *gd_default, double self_id, Layout &L, std::string &msg)
 {
-    const std::string me = "pep_group_verdicts: ";
-    const auto bad = [&](int code, const std::string &text) { msg = me + text; return code; };
-    if (!h_row_off || (n_rows && !h_row_len) || (n_groups && (!h_grp_off || !h_inparalog)) || (n_gd && (!gd_key || !gd_val)) || !gd_default) return bad(PEP_ERR_ARG, "null table");
-    if (n_groups && h_grp_off[n_groups] && (!h_grp_rows || !h_grp_genome)) return bad(PEP_ERR_ARG, "null table");
-    if (n_rows && h_row_off[n_rows] && !h_packed) return bad(PEP_ERR_ARG, "null table");
+    const auto bad = [&](int code, const std::string &text) { msg = K16_SPEC.me + text; return code; };
+    if (!T.row_off || (T.n_rows && !T.row_len) || (T.n_groups && (!T.grp_off || !h_inparalog)) || (n_gd && (!gd_key || !gd_val)) || !gd_default) return bad(PEP_ERR_ARG, "null table");
+    if (T.n_groups && T.grp_off[T.n_groups] && (!T.grp_rows || !h_grp_genome)) return bad(PEP_ERR_ARG, "null table");
+    if (T.n_rows && T.row_off[T.n_rows] && !T.packed) return bad(PEP_ERR_ARG, "null table");
     if (!k16_good(self_id)) return bad(PEP_ERR_ARG, "self_id must be finite and > 0");
     for (uint64_t i = 0; i < n_gd; ++i) {
         if ((gd_key[i] >> 32) > (gd_key[i] & 0xFFFFFFFFull)) return bad(PEP_ERR_ARG, "gd_key " + std::to_string(i) + " has g1 > g2");
@@ -212,66 +209,33 @@ int k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t
     }
     L.gd.assign(gd_val, gd_val + 3 * n_gd);
     L.gd.insert(L.gd.end(), gd_default, gd_default + 3);
-    if (n_rows >= 0xFFFFFFFFull) return bad(PEP_ERR_LIMIT, "more than 2^32 - 2 rows");
-    L.plane_off.assign(n_rows + 1, 0);
-    for (uint64_t r = 0; r < n_rows; ++r) {
-        const uint64_t s = ((uint64_t)h_row_len[r] + 2) / 3;
-        if (h_row_off[r + 1] < h_row_off[r] || h_row_off[r + 1] - h_row_off[r] != s)
-            return bad(PEP_ERR_ARG, "row " + std::to_string(r) + " does not hold ceil(row_len / 3) bytes");
-        L.plane_off[r + 1] = L.plane_off[r] + 3 * ((3 * s + 63) / 64);
-    }
-    if (n_groups && h_grp_off[0] != 0) return bad(PEP_ERR_ARG, "grp_off must start at 0");
-    L.groups.resize(n_groups);
     std::vector<std::pair<uint32_t, uint32_t>> by_genome;
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        if (h_grp_off[g + 1] < h_grp_off[g]) return bad(PEP_ERR_ARG, "grp_off must be non-decreasing");
-        const uint64_t n = h_grp_off[g + 1] - h_grp_off[g];
-        if (n >= 0x7FFFFFFFull) return bad(PEP_ERR_LIMIT, "more than 2^31 - 2 rows in one group");
-        if (h_inparalog[g] > 1) return bad(PEP_ERR_ARG, "grp_inparalog of group " + std::to_string(g) + " is neither 0 nor 1");
-        VGroup &G = L.groups[g];
-        G.rows_off = h_grp_off[g]; G.n = (uint32_t)n; G.words = 0; G.tri_off = L.pairs;
-        for (uint64_t k = h_grp_off[g]; k < h_grp_off[g + 1]; ++k) {
-            const uint32_t r = h_grp_rows[k];
-            if (r >= n_rows) return bad(PEP_ERR_ARG, "row index " + std::to_string(r) + " of group " + std::to_string(g) + " out of range");
-            if (h_row_len[r] != h_row_len[h_grp_rows[h_grp_off[g]]]) return bad(PEP_ERR_ARG, "group " + std::to_string(g) + " mixes rows of different row_len");
-        }
-        if (n < 2) continue;
-        const uint32_t r0 = h_grp_rows[h_grp_off[g]];
-        G.words = (uint32_t)((L.plane_off[r0 + 1] - L.plane_off[r0]) / 3);
-        L.pairs += n * (n - 1) / 2;
-        if (L.pairs * 8 > PEP_ALLELE_DIFF_MAX_BYTES)
-            return bad(PEP_ERR_LIMIT, std::to_string(L.pairs * 8) + " bytes of triangles asked for, the device budget of one call is " +
-                                          std::to_string((uint64_t)PEP_ALLELE_DIFF_MAX_BYTES) + " (reached at group " + std::to_string(g) + ": split the batch)");
-        const uint64_t nt = (n + K15_TILE - 1) / K15_TILE;
-        for (uint64_t ti = 0; ti < nt; ++ti)
-            for (uint64_t tj = ti; tj < nt; ++tj) L.tiles.push_back(DiffTile{g, (uint32_t)ti, (uint32_t)tj, 0u});
-        const uint32_t last = (uint32_t)n - 1;
-        for (uint32_t b = 0; b <= last; ++b) {
-            if (b != 0) L.edges.push_back(EdgePair{g, 0u, b});
-            if (b != last) L.edges.push_back(EdgePair{g, last, b});
-        }
-        if (h_inparalog[g]) {                                       // the first and the last row of every genome's sub-group against its rows (:352-366)
-            by_genome.clear();
-            for (uint32_t k = 0; k <= last; ++k) by_genome.emplace_back(h_grp_genome[h_grp_off[g] + k], k);
-            std::sort(by_genome.begin(), by_genome.end());
-            for (size_t lo = 0; lo < by_genome.size();) {
-                size_t hi = lo;
-                while (hi < by_genome.size() && by_genome[hi].first == by_genome[lo].first) ++hi;
-                const uint32_t sf = by_genome[lo].second, sl = by_genome[hi - 1].second;
-                for (size_t k = lo; hi - lo > 1 && k < hi; ++k) {
-                    const uint32_t b = by_genome[k].second;
-                    if (b != sf) L.edges.push_back(EdgePair{g, sf, b});
-                    if (b != sl) L.edges.push_back(EdgePair{g, sl, b});
-                }
-                lo = hi;
+    return group_tables_check(T, K16_SPEC,
+        [&](uint32_t g, unsigned &want) { want = 1; return h_inparalog[g] > 1 ? "grp_inparalog of group " + std::to_string(g) + " is neither 0 nor 1" : std::string(); },
+        [&](uint32_t g, const GroupRec &G, uint64_t) {
+            const uint32_t last = G.n - 1;
+            for (uint32_t b = 0; b <= last; ++b) {
+                if (b != 0) L.edges.push_back(EdgePair{g, 0u, b});
+                if (b != last) L.edges.push_back(EdgePair{g, last, b});
             }
-        }
-    }
-    if (L.tiles.size() > 0x7FFFFFFFull || L.edges.size() > 0x7FFFFFFFull) return bad(PEP_ERR_LIMIT, "more than 2^31 - 1 tiles or edge pairs in one call (split the batch)");
-    if (L.plane_off[n_rows] * 8 > PEP_ALLELE_DIFF_MAX_BYTES)
-        return bad(PEP_ERR_LIMIT, std::to_string(L.plane_off[n_rows] * 8) + " bytes of bit planes asked for, the device budget of one call is " +
-                                      std::to_string((uint64_t)PEP_ALLELE_DIFF_MAX_BYTES) + " (split the batch)");
-    return PEP_OK;
+            if (h_inparalog[g]) {                                       // the first and the last row of every genome's sub-group against its rows (:352-366)
+                by_genome.clear();
+                for (uint32_t k = 0; k <= last; ++k) by_genome.emplace_back(h_grp_genome[G.rows_off + k], k);
+                std::sort(by_genome.begin(), by_genome.end());
+                for (size_t lo = 0; lo < by_genome.size();) {
+                    size_t hi = lo;
+                    while (hi < by_genome.size() && by_genome[hi].first == by_genome[lo].first) ++hi;
+                    const uint32_t sf = by_genome[lo].second, sl = by_genome[hi - 1].second;
+                    for (size_t k = lo; hi - lo > 1 && k < hi; ++k) {
+                        const uint32_t b = by_genome[k].second;
+                        if (b != sf) L.edges.push_back(EdgePair{g, sf, b});
+                        if (b != sl) L.edges.push_back(EdgePair{g, sl, b});
+                    }
+                    lo = hi;
+                }
+            }
+            return L.edges.size();
+        }, L, msg);
 }
 
 }  // namespace
@@ -281,7 +245,7 @@ int pep_k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint
                   const double *gd_default, double self_id, std::string &msg)
 {
     Layout L;
-    return k16_check(h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, L, msg);
+    return k16_check(GroupTables{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows}, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, L, msg);
 }
 
 int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
@@ -291,9 +255,10 @@ int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t
     for (double &ms : ctx->k16_ms) ms = 0.;
     ctx->k16_bytes_to_host = 0;
     ++ctx->k16_serial;                                              // whatever an earlier result held on the device is about to be overwritten
+    const GroupTables T{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows};
     Layout L;
     std::string msg;
-    const int rc = k16_check(h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, L, msg);
+    const int rc = k16_check(T, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, L, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
     pep_verdict_result *res = new (std::nothrow) pep_verdict_result();
     if (!res) return pep_fail(ctx, PEP_ERR_INTERNAL, "pep_group_verdicts: out of memory");
@@ -305,71 +270,43 @@ int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t
     *detail = res;
     if (n_groups == 0) return PEP_OK;
     const auto run = [&]() -> int {
-        const uint64_t n_idx = h_grp_off[n_groups], n_bytes = h_row_off[n_rows];
+        const uint64_t n_idx = h_grp_off[n_groups];
         DevBuf *W = ctx->ws;
         hipStream_t st = ctx->stream;
-        PEP_TRY(dev_reserve(ctx, W[0], n_bytes + 1));
-        PEP_TRY(dev_reserve(ctx, W[1], (n_rows + 1) * 8));
-        PEP_TRY(dev_reserve(ctx, W[2], (n_rows + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[3], (n_rows + 1) * 8));
-        PEP_TRY(dev_reserve(ctx, W[4], (L.plane_off[n_rows] + 1) * 8));
-        PEP_TRY(dev_reserve(ctx, W[5], (n_idx + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[6], (size_t)n_groups * sizeof(VGroup)));
-        PEP_TRY(dev_reserve(ctx, W[7], (L.tiles.size() + 1) * sizeof(DiffTile)));
-        PEP_TRY(dev_reserve(ctx, W[9], 256));
-        PEP_TRY(dev_reserve(ctx, W[10], (n_idx + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[11], (L.edges.size() + 1) * sizeof(EdgePair)));
-        PEP_TRY(dev_reserve(ctx, W[12], (n_gd + 1) * 8));
-        PEP_TRY(dev_reserve(ctx, W[13], L.gd.size() * 8));
-        PEP_TRY(dev_reserve(ctx, W[14], (size_t)n_groups * 4));
-        PEP_TRY(dev_reserve(ctx, W[15], (size_t)n_groups));
-        PEP_TRY(dev_reserve(ctx, W[16], (n_idx + 1) * 4));
+        std::vector<VGroup> dev_groups(n_groups);
+        for (uint32_t g = 0; g < n_groups; ++g) dev_groups[g] = VGroup{L.groups[g].rows_off, L.groups[g].tri_off, L.groups[g].n, L.groups[g].words};
+        PEP_TRY(dev_reserve(ctx, W[K16_WS_FLAGS], (size_t)n_groups * 4));
+        PEP_TRY(dev_reserve(ctx, W[K16_WS_VERDICT], (size_t)n_groups));
+        PEP_TRY(dev_reserve(ctx, W[K16_WS_SPILL], (n_idx + 1) * 4));
         PEP_TRY(dev_reserve(ctx, ctx->k16_tri, (L.pairs + 1) * 8));
         PEP_TRY(dev_reserve(ctx, ctx->k16_leader, (n_idx + 1) * 4));
-        PEP_TRY(pep_h2d(ctx, W[0].p, h_packed, n_bytes));
-        PEP_TRY(pep_h2d(ctx, W[1].p, h_row_off, (n_rows + 1) * 8));
-        PEP_TRY(pep_h2d(ctx, W[2].p, h_row_len, n_rows * 4));
-        PEP_TRY(pep_h2d(ctx, W[3].p, L.plane_off.data(), (n_rows + 1) * 8));
-        PEP_TRY(pep_h2d(ctx, W[5].p, h_grp_rows, n_idx * 4));
-        PEP_TRY(pep_h2d(ctx, W[6].p, L.groups.data(), (size_t)n_groups * sizeof(VGroup)));
-        PEP_TRY(pep_h2d(ctx, W[7].p, L.tiles.data(), L.tiles.size() * sizeof(DiffTile)));
-        PEP_TRY(pep_h2d(ctx, W[10].p, h_grp_genome, n_idx * 4));
-        PEP_TRY(pep_h2d(ctx, W[11].p, L.edges.data(), L.edges.size() * sizeof(EdgePair)));
-        PEP_TRY(pep_h2d(ctx, W[12].p, gd_key, n_gd * 8));
-        PEP_TRY(pep_h2d(ctx, W[13].p, L.gd.data(), L.gd.size() * 8));
-        PEP_HIP(ctx, hipMemsetAsync(W[9].p, 0xFF, 4, st));
-        PEP_HIP(ctx, hipMemsetAsync(W[14].p, 0, (size_t)n_groups * 4, st));
-        const GdTable gd{W[12].as<const uint64_t>(), W[13].as<const double>(), n_gd, self_id};
-        const bool timed = ctx->timing_level >= 2;
-        const auto stage = [&](int which, const auto &launch) {
-            std::optional<EventTimer> tm;
-            if (timed) tm.emplace(st);
-            launch();
-            if (timed) ctx->k16_ms[which] = tm->stop();
-        };
-        if (n_rows)
-            stage(0, [&] { pep_k15_queue_planes(st, n_rows, W[0].as<const uint8_t>(), W[1].as<const uint64_t>(), W[2].as<const uint32_t>(), W[3].as<const uint64_t>(),
-                                                W[4].as<unsigned long long>(), W[9].as<uint32_t>()); });
+        PEP_TRY(group_tables_to_device(ctx, T, L, dev_groups.data(), (size_t)n_groups * sizeof(VGroup),
+                                       {{K16_WS_GENOME, h_grp_genome, n_idx * 4, 4}, {K16_WS_EDGES, L.edges.data(), L.edges.size() * sizeof(EdgePair), sizeof(EdgePair)},
+                                        {K16_WS_GD_KEY, gd_key, n_gd * 8, 8}, {K16_WS_GD_VAL, L.gd.data(), L.gd.size() * 8, 0}}, ctx->k16_ms[0]));
+        PEP_HIP(ctx, hipMemsetAsync(W[K16_WS_FLAGS].p, 0, (size_t)n_groups * 4, st));
+        const GdTable gd{W[K16_WS_GD_KEY].as<const uint64_t>(), W[K16_WS_GD_VAL].as<const double>(), n_gd, self_id};
+        const VGroup *d_groups = W[K15_WS_GROUPS].as<const VGroup>();
+        const uint32_t *d_grp_rows = W[K15_WS_GRP_ROWS].as<const uint32_t>(), *d_genome = W[K16_WS_GENOME].as<const uint32_t>();
+        const uint64_t *d_plane_off = W[K15_WS_PLANE_OFF].as<const uint64_t>();
+        const unsigned long long *d_planes = W[K15_WS_PLANES].as<const unsigned long long>();
+        uint32_t *d_flags = W[K16_WS_FLAGS].as<uint32_t>();
         if (!L.edges.empty())
-            stage(1, [&] { hipLaunchKernelGGL(verdict_edge, dim3((unsigned)ceil_div(L.edges.size(), 4 * K16_EDGE_PER_WAVE)), dim3(256), 0, st, (uint64_t)L.edges.size(),
-                                              W[11].as<const EdgePair>(), W[6].as<const VGroup>(), W[5].as<const uint32_t>(), W[10].as<const uint32_t>(),
-                                              W[3].as<const uint64_t>(), W[4].as<const unsigned long long>(), gd, W[14].as<uint32_t>()); });
+            pep_timed_stage(ctx, ctx->k16_ms[1], [&] {
+                hipLaunchKernelGGL(verdict_edge, dim3((unsigned)ceil_div(L.edges.size(), 4 * K16_EDGE_PER_WAVE)), dim3(256), 0, st, (uint64_t)L.edges.size(),
+                                   W[K16_WS_EDGES].as<const EdgePair>(), d_groups, d_grp_rows, d_genome, d_plane_off, d_planes, gd, d_flags);
+            });
         if (!L.tiles.empty())
-            stage(2, [&] { hipLaunchKernelGGL(verdict_pairs, dim3((unsigned)L.tiles.size()), dim3(256), 0, st, W[7].as<const DiffTile>(), W[6].as<const VGroup>(),
-                                              W[5].as<const uint32_t>(), W[10].as<const uint32_t>(), W[3].as<const uint64_t>(), W[4].as<const unsigned long long>(), gd,
-                                              W[14].as<uint32_t>(), ctx->k16_tri.as<int2>()); });
-        stage(3, [&] { hipLaunchKernelGGL(verdict_leaders, dim3(n_groups), dim3(256), 0, st, W[6].as<const VGroup>(), W[14].as<const uint32_t>(),
-                                          ctx->k16_tri.as<const int2>(), ctx->k16_leader.as<uint32_t>(), W[16].as<uint32_t>(), W[15].as<uint8_t>()); });
-        PEP_HIP(ctx, hipGetLastError());
-        uint32_t bad_row = 0xFFFFFFFFu;
-        PEP_TRY(pep_d2h_queue(ctx, &bad_row, W[9].p, 4));
-        PEP_TRY(pep_d2h_queue(ctx, res->verdict.data(), W[15].p, n_groups));
-        PEP_HIP(ctx, pep_stream_wait(ctx));
-        pep_d2h_finish(ctx);
+            pep_timed_stage(ctx, ctx->k16_ms[2], [&] {
+                hipLaunchKernelGGL(verdict_pairs, dim3((unsigned)L.tiles.size()), dim3(256), 0, st, W[K15_WS_TILES].as<const DiffTile>(), d_groups, d_grp_rows, d_genome,
+                                   d_plane_off, d_planes, gd, d_flags, ctx->k16_tri.as<int2>());
+            });
+        pep_timed_stage(ctx, ctx->k16_ms[3], [&] {
+            hipLaunchKernelGGL(verdict_leaders, dim3(n_groups), dim3(256), 0, st, d_groups, (const uint32_t *)d_flags, ctx->k16_tri.as<const int2>(),
+                               ctx->k16_leader.as<uint32_t>(), W[K16_WS_SPILL].as<uint32_t>(), W[K16_WS_VERDICT].as<uint8_t>());
+        });
+        PEP_TRY(pep_d2h_queue(ctx, res->verdict.data(), W[K16_WS_VERDICT].p, n_groups));
         ctx->k16_bytes_to_host = (uint64_t)n_groups + 4;
-        if (bad_row != 0xFFFFFFFFu)
-            return pep_fail(ctx, PEP_ERR_ARG, "pep_group_verdicts: row " + std::to_string(bad_row) + " holds a byte above 124 (not three base-5 digits)");
-        return PEP_OK;
+        return group_tables_finish(ctx, K16_SPEC);
     };
     const int rc2 = run();
     if (rc2 != PEP_OK) {
