@@ -72,3 +72,24 @@ def random_group(rng, n, ref_len, gap=None, div=None):
     full = rng.integers(0, 5, (n, 3 * s))
     full[:, :ref_len] = codes
     return (full[:, :s] * 25 + full[:, s:2 * s] * 5 + full[:, 2 * s:]).astype(np.uint8)
+
+
+def plane_words(L):
+    """64-bit words per bit plane of a row of L nt: ceil(3 * ceil(L / 3) / 64)"""
+    return -(-3 * -(-L // 3) // 64)
+
+
+def bit_of_column(L):
+    """the bit of the planes that holds column c of a row of L columns: digit d of byte j is column d * s + j and bit 3 j + d"""
+    s = -(-L // 3)
+    c = np.arange(L)
+    return 3 * (c % s) + c // s
+
+
+def beyond_first_trip(L):
+    """(the columns of a row of L nt, highest bit first, that a wavefront reaches in its second trip over the plane words or later - bit >= 4 096 -, that
+    bit bound).  A row of exactly 64 words has no such column: there it is the last word, which lane 63 alone reads."""
+    bit = bit_of_column(L)
+    bound = 4096 if plane_words(L) > 64 else 64 * (plane_words(L) - 1)
+    cols = np.flatnonzero(bit >= bound)
+    return cols[np.argsort(-bit[cols])], bound

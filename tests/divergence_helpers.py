@@ -6,6 +6,9 @@ the pair counts of allele_diff_helpers.numpy_tri_edge, one pair at a time (not f
     checkDiv  : mut / aln / (gd[0] * exp(gd[1] * sqrt(allowed_sigma))) > 1      rows a in {first, last} against every b != a
     distances : d = mut / aln / (gd[0] * exp(gd[1] * allowed_sigma)); beyond when d / gd[0] > 1 / gd[0]       all a < b
     leaders   : rows in order; j joins the FIRST leader g with mut(g, j) <= 0.01 * aln(g, j), else becomes a leader
+
+For groups too large for plain Python loops (thousands of rows): matmul_counts (the pair counts as one-hot matrix products, independent of
+numpy_tri_edge) and leaders_numpy (the leader rule alone, one numpy comparison per row); test_divergence_host.py pins both against restate.
 """
 import base64
 import gzip
@@ -168,3 +171,117 @@ def clade(rng, anc, n, div, gap=0.):
     codes[mut] = (codes[mut] - 1 + rng.integers(1, 4, int(mut.sum()))) % 4 + 1
     codes[rng.random(codes.shape) < gap] = 0
     return codes
+
+
+def fuzz_groups(seed, count, n_max):
+    """groups aimed in turn at the three verdicts (what comes out is the restatement's business): a calm clade of genomes that mostly know each
+    other; a clade between checkDiv's bound and the distances' bound (allowed_sigma 5, where the two are far apart); and clades far apart or
+    rows far from each other, with genomes that repeat.  n log-uniform in 2 .. n_max, ref_len 30 .. 3 000, gap rates 0 .. 0.3."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(count):
+        n = int(np.exp(rng.uniform(np.log(2), np.log(n_max + 1))))
+        L = int(rng.integers(30, 3001))
+        aim, self_id = k % 3, (0.002, 0.005)[(k // 3) % 2]
+        sigma = 5 if aim == 1 else (1, 3, 5)[(k // 3) % 3]
+        genomes = rng.permutation(n) + 1
+        if aim == 0:
+            codes = clade(rng, rng.integers(1, 5, L), n, rng.uniform(0, 0.004), gap=rng.uniform(0, 0.3))
+            if n > 5 and rng.random() < 0.5:             # a genome twice among the inner rows: seen by an in-paralog sub-group only
+                genomes[n // 2] = genomes[1]
+        elif aim == 1:
+            L = max(L, 400)
+            lo, hi = 0.02 * np.exp(0.5 * np.sqrt(sigma)), 0.02 * np.exp(0.5 * sigma)
+            codes = clade(rng, rng.integers(1, 5, L), n, np.sqrt(lo * hi) / 2 * rng.uniform(0.85, 1.15), gap=rng.uniform(0, 0.1))
+        else:
+            codes = clade(rng, rng.integers(1, 5, L), n, rng.choice([0.002, 0.01, 0.15]), gap=rng.uniform(0, 0.3))
+            if n > 4 and rng.random() < 0.6:             # a second clade far from the first
+                codes[n // 2:] = clade(rng, rng.integers(1, 5, L), n - n // 2, rng.choice([0.002, 0.006]))
+            genomes = rng.integers(0, max(2, int(n * rng.choice([0.7, 3.0]))), n)
+        ids = sorted(set(genomes.tolist()))
+        keep = 1.0 if aim == 1 else 0.9
+        gd = {(a, b): (0.02, 0.5) for i, a in enumerate(ids) for b in ids[i + 1:] if rng.random() < keep}
+        out.append(dict(packed=pack_codes(codes, rng), ref_len=L, genomes=genomes, inparalog=bool(rng.integers(0, 2)), gd=gd, self_id=self_id, allowed_sigma=sigma))
+    return out
+
+
+def matmul_counts(seqs):
+    """seqs uint8[n, L] of 0 / ASCII ACGT (decode_rows) -> (mut, aln) int32[n, n], symmetric: mut = mismatch + 1, aln = comparable + 2 of every pair of
+    rows.  Matching columns = the sum over the four bases of onehot @ onehot.T, comparable columns = valid @ valid.T, mismatch = comparable -
+    matching.  float32 products and sums of 0 / 1 are exact while a count stays below 2^24."""
+    assert seqs.shape[1] < 1 << 24
+    valid = (seqs > 0).astype(np.float32)
+    comparable = valid @ valid.T
+    matching = np.zeros_like(comparable)
+    for base in b'ACGT':
+        onehot = (seqs == base).astype(np.float32)
+        matching += onehot @ onehot.T
+    return (comparable - matching).astype(np.int32) + 1, comparable.astype(np.int32) + 2
+
+
+def tri_from_square(mut, aln):
+    """the packed upper triangle int32[n(n-1)/2, 2] in row-major pair order of two [n, n] arrays"""
+    upper = np.triu(np.ones(mut.shape, dtype=bool), 1)
+    return np.stack([mut[upper], aln[upper]], axis=1)
+
+
+def leaders_numpy(mut, aln):
+    """mut, aln: the integer [n, n] pair counts (read at [l, j] with l < j only) -> uint32[n], the row that leads row j.
+    The contract: the rows are taken in order; row j joins the FIRST leader l, in the order in which the leaders were made, for which
+    float(mut[l, j]) <= 0.01 * float(aln[l, j]) - one correctly rounded double product, one comparison -; when there is none, row j becomes the
+    newest leader and leads itself.  Row 0 is therefore always a leader."""
+    n = len(mut)
+    out = np.zeros(n, dtype=np.uint32)
+    leaders = np.zeros(n, dtype=np.int64)
+    count = 0
+    for j in range(n):
+        l = leaders[:count]
+        hit = np.flatnonzero(mut[l, j].astype(np.float64) <= 0.01 * aln[l, j].astype(np.float64))
+        if len(hit):
+            out[j] = l[hit[0]]
+        else:
+            leaders[count] = out[j] = j
+            count += 1
+    return out
+
+
+def matching_leaders(mut, aln, lead, j):
+    """the leaders (rows, in leader order) in front of row j that row j matches, from the same counts: what makes "the first one wins" a decision"""
+    l = np.flatnonzero(lead[:j] == np.arange(j))
+    return l[mut[l, j].astype(np.float64) <= 0.01 * aln[l, j].astype(np.float64)]
+
+
+def founders_group(rng, D, L, variants=(), between=(), behind=()):
+    """A group of D founders - independent uniformly random gap-free rows of L columns, about 3 L / 4 columns apart, so each of them becomes a leader,
+    and founder p is leader number p - and of followers, for the leader rule at L = 200 (aln = 202, 0.01 * aln = 2.02: two rows match iff they
+    differ in at most ONE column).
+      variants  (src, var): the founder at leader position `var` is replaced by founder `src` with two columns changed - three columns from a match,
+                so it stays a leader; behind everything else comes a follower made of founder `src` with one of the two changes: one column from
+                both, it must join whichever of the two is the earlier leader
+      between   k: a copy of founder k three rows behind it, between the founders (from there on the row index and the leader count differ)
+      behind    k: a copy of founder k behind the last founder
+    -> (codes int64[n, L], row_of int64[D]: the row of every founder, joins [(row, founder it must join)], triples [(row, earlier founder, later founder)])"""
+    F = rng.integers(1, 5, (D, L))
+    middles = []
+    for src, var in variants:
+        cols = rng.choice(L, 2, replace=False)
+        F[var] = F[src]
+        F[var, cols] = F[src, cols] % 4 + 1
+        mid = F[src].copy()
+        mid[cols[0]] = F[var, cols[0]]
+        middles.append(mid)
+    rows, row_of, joins, triples = [], np.zeros(D, dtype=np.int64), [], []
+    for p in range(D):
+        row_of[p] = len(rows)
+        rows.append(F[p])
+        if p - 3 in between:
+            joins.append((len(rows), p - 3))
+            rows.append(F[p - 3])
+    for k in behind:
+        joins.append((len(rows), k))
+        rows.append(F[k])
+    for (src, var), mid in zip(variants, middles):
+        joins.append((len(rows), min(src, var)))
+        triples.append((len(rows), min(src, var), max(src, var)))
+        rows.append(mid)
+    return np.array(rows), row_of, joins, triples

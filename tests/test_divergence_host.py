@@ -1,6 +1,7 @@
 """K16 (divergence verdicts of gene groups, PEPPAN.py:335-392) without a GPU: the ABI, the host half of the float layer (gd_table,
 distances_from_diff, incompatible_of) against expressions evaluated one key / one pair at a time, the g20 fixture against the independent
-restatement, and the table checks of pep_group_verdicts, which need no device."""
+restatement, the table checks of pep_group_verdicts, which need no device, and the fast reference of the large-group GPU tests (matmul_counts,
+leaders_numpy) against the restatement."""
 import os
 import sys
 
@@ -8,8 +9,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from allele_diff_helpers import random_group, square_from_tri  # noqa: E402
-from divergence_helpers import load_g20, pair_counts, restate, restate_distances, restate_incompatible, verdict_table  # noqa: E402
+from allele_diff_helpers import decode_rows, random_group, square_from_tri  # noqa: E402
+from divergence_helpers import (founders_group, fuzz_groups, leaders_numpy, load_g20, matching_leaders, matmul_counts, pack_codes, pair_counts, restate,  # noqa: E402
+                                restate_distances, restate_incompatible, tri_from_square, verdict_table)
 
 
 @pytest.fixture(scope='module')
@@ -149,3 +151,36 @@ def test_table_checks_need_no_device(N):
     with pytest.raises(ValueError):
         N.group_verdicts_check(packed, row_off, row_len, index, [np.arange(5)], [0], gd, 0.002)
     assert N.group_verdicts_check(packed, row_off, row_len, index, genomes, [1], gd, 0.005) is None
+
+
+def test_leaders_numpy_over_matmul_counts_equals_the_restatement():
+    """the reference of the large-group GPU tests is only as good as this: on every fuzz group that reaches verdict 2 and on the constructed
+    founder / variant / follower groups at small size, triangle and leaders are the restatement's"""
+    rng = np.random.default_rng(16)
+    cases = fuzz_groups(1602, 240, 120)
+    # the construction of test_leaders_past_256_and_past_the_lds_list, 30 founders instead of 4 200 (every pair known to the table, as its default row says there)
+    for variants, between, behind in (([(10, 25)], (), (0, 29)), ([(3, 9), (20, 14)], (5, 22), (0, 7, 29)), ((), (0,), (26,))):
+        codes, row_of, joins, triples = founders_group(rng, 30, 200, variants, between, behind)
+        n = len(codes)
+        cases.append(dict(packed=pack_codes(codes, rng), ref_len=200, genomes=np.arange(n), inparalog=False, self_id=0.002, allowed_sigma=5,
+                          gd={(a, b): (0.02, 0.5) for a in range(n) for b in range(a + 1, n)}, built=(row_of, joins, triples)))
+    done = several = 0
+    for c in cases:
+        want = restate(c['packed'], c['ref_len'], c['genomes'], c['inparalog'], c['gd'], c['self_id'], c['allowed_sigma'])
+        assert want['verdict'] == 2 or 'built' not in c
+        if want['verdict'] != 2:
+            continue
+        mut, aln = matmul_counts(decode_rows(c['packed'], c['ref_len']))
+        assert mut.dtype == np.int32 and np.array_equal(mut, mut.T) and np.array_equal(aln, aln.T)
+        assert np.array_equal(tri_from_square(mut, aln), want['tri'])
+        lead = leaders_numpy(mut, aln)
+        assert lead.dtype == np.uint32 and np.array_equal(lead, want['leader'])
+        done += 1
+        several += int(len(want['groups']) > 2)
+        if 'built' in c:
+            row_of, joins, triples = c['built']
+            assert np.array_equal(np.flatnonzero(lead == np.arange(len(lead))), row_of)          # founder p is leader number p
+            assert all(lead[row] == row_of[k] for row, k in joins) and len(joins) >= 2
+            for row, first, second in triples:
+                assert matching_leaders(mut, aln, lead, row).tolist() == [row_of[first], row_of[second]]
+    assert done >= 50 + 3 and several >= 10, (done, several)

@@ -1,5 +1,7 @@
 """K15 on the GPU: Context.allele_diff, the compare_seq / compare_seqX drop-ins and group_differences against the reference's own values
-(tests/golden/g19_allele_diff.json.gz) and an independent numpy formulation (tests/allele_diff_helpers.py).  Bit for bit everywhere."""
+(tests/golden/g19_allele_diff.json.gz) and an independent numpy formulation (tests/allele_diff_helpers.py).  Bit for bit everywhere.
+Beside the fixture, the fuzz and the at-size case: rows of 4 095 .. 12 300 nt (more than 64 words per bit plane, the second and later trips of
+allele_planes' word loop) and every group size around the 64-row tile at every width around the four words staged per step."""
 import os
 import sys
 import time
@@ -8,7 +10,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from allele_diff_helpers import load_g19, decode_rows, numpy_tri_edge, square_from_tri, random_group  # noqa: E402
+from allele_diff_helpers import (beyond_first_trip, bit_of_column, load_g19, decode_rows, numpy_tri_edge, plane_words, square_from_tri,  # noqa: E402
+                                 random_group)
+from divergence_helpers import pack_codes, restate  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -212,6 +216,89 @@ def test_at_size_2000_rows_of_1002_nt(ctx):
     assert np.array_equal(diff, square_from_tri(n, want_tri))
     diffX = OF.compare_seqX(seqs, np.zeros((n, n, 2), dtype=np.int64))
     assert np.array_equal(diffX[0], want_edge[0]) and np.array_equal(diffX[-1], want_edge[1]) and not diffX[1:-1].any()
+
+
+def test_rows_of_more_than_64_plane_words(ctx):
+    """allele_planes gives lane l the words l, l + 64, ...: every other test stays below 48 words, one trip.  Random groups of 5 and 70 rows per length,
+    and per length two groups of one row copied, changed and gapped only beyond the first trip (bit >= 4 096) or only within it."""
+    rng = np.random.default_rng(4096)
+    lens = (4095, 4096, 8190, 8191, 12300)
+    assert [plane_words(L) for L in lens] == [64, 65, 128, 129, 193]
+    groups, ref_lens, kinds = [], [], []
+    for L in lens:
+        high, bound = beyond_first_trip(L)
+        low = np.flatnonzero(bit_of_column(L) < bound)
+        low = low[np.argsort(-bit_of_column(L)[low])]
+        assert len(high) >= 1 and len(high) + len(low) == L and (bound == 4096 or plane_words(L) == 64)
+        made = [random_group(rng, 5, L), random_group(rng, 70, L)]
+        for cols in (high, low):
+            # the highest bits of the part, its lowest one and some between
+            touch = np.unique(np.concatenate([cols[:12], cols[-1:], rng.choice(cols, min(len(cols), 20), replace=False)]))
+            codes = np.repeat(rng.integers(1, 5, L)[None, :], 7, axis=0)
+            how = rng.integers(0, 3, (6, len(touch)))                            # per row (the first one stays) and column: as it is, another base, a gap
+            how[0, :], how[1, :] = 1, 2                                          # ... every column with another base in one row and a gap in another
+            part = codes[1:, touch]
+            part[how == 1] = part[how == 1] % 4 + 1
+            part[how == 2] = 0
+            codes[1:, touch] = part
+            made.append(pack_codes(codes, rng))
+        groups += made
+        ref_lens += [L] * 4
+        kinds += ['5 rows', '70 rows', 'beyond the first trip', 'within the first trip']
+    packed, row_off, row_len, index = table(groups, ref_lens)
+    t0 = time.time()
+    res = ctx.allele_diff(packed, row_off, row_len, index, 3)
+    t1 = time.time()
+    for p, L, kind, (tri, edge) in zip(groups, ref_lens, kinds, res):
+        seqs = decode_rows(p, L)
+        want_tri, want_edge = numpy_tri_edge(seqs)
+        if 'trip' in kind:
+            # from the reference: there is something to lose (k mismatches, gaps), and nothing of it in the other part of the row
+            high, bound = beyond_first_trip(L)
+            keep = bit_of_column(L) < bound if 'beyond' in kind else bit_of_column(L) >= bound
+            assert want_tri[:, 0].max() > 1 and want_tri[:, 1].min() < L + 2, (L, kind)
+            rest = numpy_tri_edge(seqs[:, keep])[0]
+            assert np.all(rest[:, 0] == 1) and np.all(rest[:, 1] == keep.sum() + 2), (L, kind)
+        assert same(tri, want_tri), (L, kind)
+        assert same(edge, want_edge), (L, kind)
+    print('long rows: Context.allele_diff of %d groups %.3f s, numpy formulation %.2f s' % (len(groups), t1 - t0, time.time() - t1))
+
+
+def test_tile_and_staging_boundaries(ctx):
+    """every group size around the 64-row tile (one tile, a tile and a row, two, three and a row) at every plane width around the K15_KW = 4 words staged
+    per step, in all three modes; and the same groups through K16, whose verdict_pairs masks a < b && b < n over the same tiles"""
+    rng = np.random.default_rng(6465)
+    sizes, lens = (2, 63, 64, 65, 127, 128, 129, 193), (1, 21, 22, 64, 190, 193, 256, 257, 320, 575, 577)
+    assert {plane_words(L) for L in lens} >= {1, 2, 3, 4, 5, 9} and {plane_words(L) % 4 for L in lens} == {0, 1, 2, 3}
+    assert {L % 3 for L in lens} == {0, 1, 2} and {3 * -(-L // 3) % 64 == 0 for L in lens} == {True, False}
+    groups, ref_lens = [], []
+    for k, (n, L) in enumerate((n, L) for n in sizes for L in lens):
+        groups.append(random_group(rng, n, L, gap=(0.15, 0.02)[k % 2], div=0.002 if L in (22, 257) else 0.6))       # (two widths that others repeat stay calm)
+        ref_lens.append(L)
+    want = [numpy_tri_edge(decode_rows(p, L)) for p, L in zip(groups, ref_lens)]
+    packed, row_off, row_len, index = table(groups, ref_lens)
+    modes = rng.integers(1, 4, len(groups)).astype(np.uint8)
+    for mode in (1, 2, 3, modes):
+        res = ctx.allele_diff(packed, row_off, row_len, index, mode)
+        for k, ((tri, edge), (want_tri, want_edge)) in enumerate(zip(res, want)):
+            m = int(mode if np.isscalar(mode) else mode[k])
+            assert (same(tri, want_tri) if m & 1 else tri is None) and (same(edge, want_edge) if m & 2 else edge is None), (m, len(groups[k]), ref_lens[k])
+    # K16 over the same rows: genome ids 0 .. n - 1 in every group, one table for all
+    from peppan_amd import orthofilter as OF
+    gd_dict = {(a, b): (0.02, 0.5) for a in range(max(sizes)) for b in range(a + 1, max(sizes))}
+    got = ctx.group_verdicts(packed, row_off, row_len, index, [np.arange(len(p)) for p in groups], [0] * len(groups), OF.gd_table(gd_dict, 0.002, 5), 0.002)
+    seen = set()
+    for p, L, (want_tri, _), (verdict, tri, leader) in zip(groups, ref_lens, want, got):
+        n = len(p)
+        sq = square_from_tri(n, want_tri)
+        w = restate(p, L, np.arange(n), False, gd_dict, 0.002, 5, counts=(want_tri, sq[:, :, 0].tolist(), sq[:, :, 1].tolist()))
+        assert verdict == w['verdict'], (n, L)
+        if verdict == 2:
+            assert tri.dtype == np.int32 and np.array_equal(tri, w['tri']) and leader.dtype == np.uint32 and np.array_equal(leader, w['leader']), (n, L)
+            seen.add((n, plane_words(L) % 4))
+        else:
+            assert tri is None and leader is None
+    assert seen == {(n, r) for n in sizes for r in range(4)}, sorted(seen)          # a returned triangle at every size and every staging tail
 
 
 def test_error_conventions_and_context_stays_usable(ctx):

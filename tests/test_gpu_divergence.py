@@ -1,6 +1,9 @@
 """K16 on the GPU: Context.group_verdicts and orthofilter.group_verdicts against the facts recorded from the reference's own filt_per_group
 (tests/golden/g20_divergence.json.gz) and an independent restatement in plain Python loops (tests/divergence_helpers.py).  Verdicts, leaders
-and triangles are compared with ==: every float decision is a chain of single correctly rounded double operations, no tolerance anywhere."""
+and triangles are compared with ==: every float decision is a chain of single correctly rounded double operations, no tolerance anywhere.
+Beside the fixture, the fuzz, the ties and the at-size case: a group of 4 200 leaders with rows that match two of them (the chunks of 256 of
+verdict_leaders, its list beyond 4 096 leaders and "the first leader wins", against leaders_numpy over matmul_counts, which test_divergence_host.py
+pins), and rows of 4 095 .. 12 300 nt, whose bit planes are longer than one trip of a wavefront."""
 import os
 import sys
 import time
@@ -9,8 +12,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from allele_diff_helpers import counts, decode_rows, numpy_tri_edge, random_group, square_from_tri  # noqa: E402
-from divergence_helpers import clade, load_g20, pack_codes, pair_counts, restate, verdict_table  # noqa: E402
+from allele_diff_helpers import beyond_first_trip, bit_of_column, counts, decode_rows, numpy_tri_edge, plane_words, random_group, square_from_tri  # noqa: E402
+from divergence_helpers import (clade, founders_group, fuzz_groups, leaders_numpy, load_g20, matching_leaders, matmul_counts, pack_codes, pair_counts,  # noqa: E402
+                                restate, tri_from_square, verdict_table)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,38 +63,6 @@ def test_every_golden_case_exactly(ctx):
             if c['tree_asked']:
                 assert sorted(g[0] for g in groups) == c['leaders'], c['name']
         assert needs_tree == c['tree_asked'], c['name']
-
-
-def fuzz_groups(seed, count, n_max):
-    """groups aimed in turn at the three verdicts (what comes out is the restatement's business): a calm clade of genomes that mostly know each
-    other; a clade between checkDiv's bound and the distances' bound (allowed_sigma 5, where the two are far apart); and clades far apart or
-    rows far from each other, with genomes that repeat.  n log-uniform in 2 .. n_max, ref_len 30 .. 3 000, gap rates 0 .. 0.3."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for k in range(count):
-        n = int(np.exp(rng.uniform(np.log(2), np.log(n_max + 1))))
-        L = int(rng.integers(30, 3001))
-        aim, self_id = k % 3, (0.002, 0.005)[(k // 3) % 2]
-        sigma = 5 if aim == 1 else (1, 3, 5)[(k // 3) % 3]
-        genomes = rng.permutation(n) + 1
-        if aim == 0:
-            codes = clade(rng, rng.integers(1, 5, L), n, rng.uniform(0, 0.004), gap=rng.uniform(0, 0.3))
-            if n > 5 and rng.random() < 0.5:             # a genome twice among the inner rows: seen by an in-paralog sub-group only
-                genomes[n // 2] = genomes[1]
-        elif aim == 1:
-            L = max(L, 400)
-            lo, hi = 0.02 * np.exp(0.5 * np.sqrt(sigma)), 0.02 * np.exp(0.5 * sigma)
-            codes = clade(rng, rng.integers(1, 5, L), n, np.sqrt(lo * hi) / 2 * rng.uniform(0.85, 1.15), gap=rng.uniform(0, 0.1))
-        else:
-            codes = clade(rng, rng.integers(1, 5, L), n, rng.choice([0.002, 0.01, 0.15]), gap=rng.uniform(0, 0.3))
-            if n > 4 and rng.random() < 0.6:             # a second clade far from the first
-                codes[n // 2:] = clade(rng, rng.integers(1, 5, L), n - n // 2, rng.choice([0.002, 0.006]))
-            genomes = rng.integers(0, max(2, int(n * rng.choice([0.7, 3.0]))), n)
-        ids = sorted(set(genomes.tolist()))
-        keep = 1.0 if aim == 1 else 0.9
-        gd = {(a, b): (0.02, 0.5) for i, a in enumerate(ids) for b in ids[i + 1:] if rng.random() < keep}
-        out.append(dict(packed=pack_codes(codes, rng), ref_len=L, genomes=genomes, inparalog=bool(rng.integers(0, 2)), gd=gd, self_id=self_id, allowed_sigma=sigma))
-    return out
 
 
 def run_by_params(ctx, cases, **kw):
@@ -331,6 +303,100 @@ def test_at_size_2000_rows_of_1002_nt_each_verdict_once(ctx):
                     leaders.append(j)
                     want[j] = j
             assert len(leaders) > 1 and np.array_equal(leader, want)
+
+
+def test_leaders_past_256_and_past_the_lds_list(ctx):
+    """verdict_leaders keeps 4 096 leaders in LDS and the rest in a global list, tests them 256 at a time and must return the FIRST match in leader
+    order.  ref_len 200 without gaps: two rows match iff they differ in at most one column (founders_group).  What the group was built for is
+    asserted from the reference (leaders_numpy over matmul_counts), never from the device."""
+    rng = np.random.default_rng(4200)
+    L, D = 200, 4200
+    # (src, var) by leader position: LDS against the global list; both in the global list, in two wavefronts of chunk 16; two wavefronts of chunk 0; one
+    # wavefront; and one whose two-column variant is the EARLIER row (chunks 1 and 3)
+    variants = [(10, 4150), (4120, 4180), (70, 200), (5, 40), (1000, 300)]
+    behind = [0, 63, 64, 255, 256, 257, 4095, 4096, 4097, D - 1]
+    built = [founders_group(rng, D, L, variants, between=(100, 4100), behind=behind)]
+    built += [founders_group(rng, d, L, behind=(d - 1, 0)) for d in (255, 256, 257)]           # the chunk boundary alone, and a ragged batch around the big group
+    groups = [pack_codes(b[0], rng) for b in built]
+    den_x, den = 0.02 * np.exp(0.5 * np.sqrt(5)), 0.02 * np.exp(0.5 * 5)
+    gd = (np.zeros(0, np.uint64), np.zeros((0, 3)), np.array([0.02, den_x, den]))              # (as at size: one bound for every pair, from the default row)
+    packed, row_off, row_len, index = verdict_table(groups, [L] * len(groups))
+    order = [1, 0, 2, 3]                                                                        # the big group in the middle of the batch
+    t0 = time.time()
+    got = ctx.group_verdicts(packed, row_off, row_len, [index[k] for k in order], [np.arange(len(groups[k])) for k in order], [0] * 4, gd, 0.002)
+    got = [got[order.index(k)] for k in range(4)]
+    t1 = time.time()
+    for k, ((codes, row_of, joins, triples), p, (verdict, tri, leader)) in enumerate(zip(built, groups, got)):
+        n = len(codes)
+        mut, aln = matmul_counts(decode_rows(p, L))
+        lead = leaders_numpy(mut, aln)
+        # the reference shows what the group was built for
+        assert np.array_equal(np.flatnonzero(lead == np.arange(n)), row_of), k                 # founder p is leader number p
+        assert len(row_of) == (D, 255, 256, 257)[k] and n == len(row_of) + len(joins)
+        assert all(lead[row] == row_of[f] for row, f in joins), k
+        if k == 0:
+            assert len(row_of) > 4096 and n == D + 2 + len(behind) + len(variants)
+            assert [int(lead[row]) for row, _ in joins[2:2 + len(behind)]] == [int(row_of[f]) for f in behind]
+            assert [(row - int(row_of[f])) for row, f in joins[:2]] == [4, 4] and row_of[4100] == 4101 and row_of[D - 1] == D + 1
+            assert [(first, second) for _, first, second in triples] == [(10, 4150), (4120, 4180), (70, 200), (5, 40), (300, 1000)]
+            for row, first, second in triples:
+                assert matching_leaders(mut, aln, lead, row).tolist() == [row_of[first], row_of[second]]
+        # the verdict, with numpy: checkDiv of the first and last row, then every pair against the distances' bound
+        q = mut[[0, n - 1]].astype(np.float64) / aln[[0, n - 1]].astype(np.float64) / den_x
+        q[0, 0] = q[1, n - 1] = 0
+        want_tri = tri_from_square(mut, aln)
+        t = want_tri.astype(np.float64)
+        assert bool((q > 1).any()) and bool((t[:, 0] / t[:, 1] / den / 0.02 > 1 / 0.02).any())
+        assert verdict == 2, k
+        assert tri.dtype == np.int32 and np.array_equal(tri, want_tri), k
+        assert leader.dtype == np.uint32 and np.array_equal(leader, lead), k
+    t2 = time.time()
+    print('leaders: Context.group_verdicts of 4 217 + 257 + 258 + 259 rows %.3f s, matmul counts and numpy leaders %.2f s' % (t1 - t0, t2 - t1))
+
+
+def test_rows_of_more_than_64_plane_words(ctx):
+    """verdict_edge and allele_planes walk a row's plane words 64 at a time; every other test stays below 48 words.  Per length a calm group, a group
+    whose first and last row differ from the others ONLY where a later trip reads, and a two-clade group."""
+    rng = np.random.default_rng(4096)
+    lens = (4095, 4096, 8190, 8191, 12300)
+    assert [plane_words(L) for L in lens] == [64, 65, 128, 129, 193]
+    n = 6
+    gd_dict = {(a, b): (0.02, 0.5) for a in range(n) for b in range(a + 1, n)}
+    den_x, den = 0.02 * np.exp(0.5 * np.sqrt(5)), 0.02 * np.exp(0.5 * 5)
+    gd = (np.zeros(0, np.uint64), np.zeros((0, 3)), np.array([0.02, den_x, den]))
+
+    def ref(codes):
+        return restate(pack_codes(codes), codes.shape[1], np.arange(n), False, gd_dict, 0.002, 5)
+
+    groups, ref_lens, want = [], [], []
+    for L in lens:
+        calm = clade(rng, rng.integers(1, 5, L), n, 0.002, gap=0.05)
+        # group two: all rows alike and gapped but for `shared` columns below the bound; beyond it the first and the last row carry another base than the
+        # inner rows in h columns.  h is the smallest number at which the reference calls the group divergent.
+        high, bound = beyond_first_trip(L)
+        low = np.flatnonzero(bit_of_column(L) < bound)
+        assert len(high) >= 1 and len(high) + len(low) == L
+        shared = rng.choice(low, 20 * min(len(high), 15), replace=False)
+        late = None
+        for h in range(1, min(len(high), 60) + 1):
+            codes = np.zeros((n, L), dtype=np.int64)
+            codes[:, shared] = 1
+            codes[:, high[:h]] = 2
+            codes[0, high[:h]] = codes[n - 1, high[:h]] = 3
+            if ref(codes)['verdict'] > 0:
+                late = codes
+                break
+        assert late is not None and ref(late[:, low])['verdict'] == 0, L           # what a walk of one trip sees of it is calm
+        two = np.concatenate([clade(rng, rng.integers(1, 5, L), n // 2, 0.002), clade(rng, rng.integers(1, 5, L), n - n // 2, 0.002)])
+        for codes in (calm, late, two):
+            groups.append(pack_codes(codes, rng))
+            ref_lens.append(L)
+            want.append(restate(groups[-1], L, np.arange(n), False, gd_dict, 0.002, 5))
+        assert [w['verdict'] for w in want[-3:]] in ([0, 1, 2], [0, 2, 2]), L
+    packed, row_off, row_len, index = verdict_table(groups, ref_lens)
+    got = ctx.group_verdicts(packed, row_off, row_len, index, [np.arange(n)] * len(groups), [0] * len(groups), gd, 0.002)
+    for k, (r, w) in enumerate(zip(got, want)):
+        check_against(r, w, (ref_lens[k], k % 3))
 
 
 def test_error_conventions_and_context_stays_usable(ctx):
