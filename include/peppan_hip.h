@@ -240,7 +240,9 @@ int pep_merge_hits(uint64_t n, const pep_hit *hits, const uint32_t *cigar, uint6
                    pep_hit *out_hits, uint32_t *out_cigar, uint64_t *n_out, uint64_t *n_cigar_out);
 
 /* K7: integer counts of mode-1 rescoring per hit, out[5*i..] = nMatch, nMismatch, nGap, bGap, mGap.
- * Uses the nucleotide sets given to pep_set_query_nt / pep_set_ref_nt. */
+ * Uses the nucleotide sets given to pep_set_query_nt / pep_set_ref_nt.  rs < re is a forward-strand hit; every other hit, a one-base
+ * range (rs == re) included, is read on the reverse strand, complemented, as the reference does (`t[8] < t[9]` is false, uberBlast.py:412).
+ * A run with op code 3 is PEP_ERR_ARG ("unknown CIGAR op"), as in pep_alleles. */
 int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int64_t *out);
 
 /* K7 as the tail of every search of this context (-s 1 in PEPPAN's hot call, PEPPAN.py:229-230: every hit of both tools is rescored, uberBlast.py:352-353):

@@ -734,7 +734,7 @@ void oracle_rescore_counts(const uint8_t *q, const uint8_t *r, int64_t qs, int64
                            const uint32_t *cigar, uint32_t n_runs, int64_t *out)
 {
     int64_t qi = qs - 1, nmatch = 0, nmis = 0, ngap = 0, bgap = 0, mgap = 0;
-    int rev = rs > re;
+    int rev = rs >= re;                   /* a one-base range takes the reference's else arm (`t[8] < t[9]` is false, uberBlast.py:412): complemented */
     int64_t ri = rev ? rs - 1 : rs - 1;   /* 0-based index of the first aligned reference base */
     for (uint32_t k = 0; k < n_runs; ++k) {
         int64_t n = cigar[k] >> 2; int op = cigar[k] & 3;

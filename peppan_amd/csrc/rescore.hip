@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k7_rescore(uint64_t n, const pep_nt_hit *
     if (h >= n) return;
     const pep_nt_hit hit = hits[h];
     const uint8_t *q = q_nt + q_off[hit.q], *r = r_nt + r_off[hit.r];
-    const bool rev = hit.rs > hit.re;
+    const bool rev = hit.rs >= hit.re;           // a one-base range is read complemented: the reference's `t[8] < t[9]` is false there (uberBlast.py:412)
     long long qi = (long long)hit.qs - 1, ri = (long long)hit.rs - 1;
     long long nmatch = 0, ncol = 0, ngap = 0, bgap = 0, mgap = 0;
     const uint32_t *cg = cigar + hit.cigar_off;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void k7_hits(uint64_t n_bound, const uint32_t 
     if (h >= n) return;
     const pep_hit hit = hits[h];
     long long qi, ri;
-    bool rev;
+    bool rev;                                    // from the target's descriptor, not from rs >= re as in k7_rescore: a search emits no one-base reference range
     uint32_t r_seq;
     if (TOOL == 0) {
         const PackDesc dq = reinterpret_cast<const PackDesc *>(q_desc)[hit.q], dt = reinterpret_cast<const PackDesc *>(t_desc)[hit.t];
@@ -156,10 +156,11 @@ int pep_k7_rescore(pep_ctx *ctx, uint64_t n, const pep_nt_hit *h_hits, const uin
         uint64_t qa = 0, ra = 0;
         for (uint32_t k = 0; k < h.cigar_runs; ++k) {
             const uint32_t run = h_cigar[h.cigar_off + k];
+            if ((run & 3u) == 3) return pep_fail(ctx, PEP_ERR_ARG, "pep_rescore_nt: unknown CIGAR op");
             if ((run & 3u) != 2) qa += run >> 2;
             if ((run & 3u) != 1) ra += run >> 2;
         }
-        const bool rev = h.rs > h.re;
+        const bool rev = h.rs >= h.re;
         const uint64_t rlo = rev ? h.re : h.rs, rhi = rev ? h.rs : h.re;
         if (h.qs < 1 || h.qs - 1 + qa > ql || rlo < 1 || rhi > rl || ra != rhi - rlo + 1)
             return pep_fail(ctx, PEP_ERR_ARG, "pep_rescore_nt: CIGAR inconsistent with the hit coordinates");
