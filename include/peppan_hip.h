@@ -23,6 +23,7 @@
  *   pep_search              `diamond makedb` + 5 x `diamond blastp ... --outfmt 101`   uberBlast.py:531-533, 546-552
  *   pep_hit fields          the SAM fields parseDiamond consumes (POS, CIGAR, |SEQ|, NM, ZR, ZS)   uberBlast.py:25-58
  *   pep_rescore_nt          cigar2score mode 1 inside RunBlast.reScore      uberBlast.py:226-249, 397-415
+ *   pep_rescore_codons(_check)   cigar2score modes 2 / 3 (amino-acid / codon-position scoring) inside RunBlast.reScore   uberBlast.py:250-269, 397-415
  *   pep_components(_of_hits) union-find of get_gene_group (partition only)  PEPPAN.py:1598-1607
  *   pep_linclust            `mmseqs createdb / linclust / createtsv`        clust.py:62-66
  *   pep_overlaps            numba tab2overlaps inside returnOverlap          uberBlast.py:73-97, 378-395
@@ -49,7 +50,7 @@ extern "C" {
 #endif
 
 /* 17 gained, additively, the K16 entry points: pep_group_verdicts, pep_group_verdicts_check, pep_verdict_detail_size, pep_verdict_detail_copy,
- * pep_verdict_result_free, pep_group_verdicts_times. */
+ * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check. */
 #define PEP_ABI_VERSION 17
 
 #define PEP_OK 0
@@ -244,6 +245,26 @@ int pep_merge_hits(uint64_t n, const pep_hit *hits, const uint32_t *cigar, uint6
  * range (rs == re) included, is read on the reverse strand, complemented, as the reference does (`t[8] < t[9]` is false, uberBlast.py:412).
  * A run with op code 3 is PEP_ERR_ARG ("unknown CIGAR op"), as in pep_alleles. */
 int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int64_t *out);
+
+/* K7 over the codon grid: the integer counts of rescoring modes 2 and 3 per hit (cigar2score, uberBlast.py:250-269); hits, CIGAR arena, nucleotide sets,
+ * base codes and strand rule as for pep_rescore_nt.  The columns of a hit are the columns of its M and I runs in CIGAR order (an I column has a query base
+ * and no reference base; D runs only move the reference cursor).  With phase = (qs - 1) % 3 and whole = max(n_col - phase, 0) / 3, column p is kept when
+ * p >= phase and p - phase < 3 * whole, as position (p - phase) % 3 of codon (p - phase) / 3: a trailing partial codon is dropped.  out[7*i..]:
+ *   mode 3   hit0, hit1, hit2 (kept columns with equal codes at codon position 0 / 1 / 2; an I column never matches), paired (kept columns that have a
+ *            reference base), nGap, bGap, mGap (as pep_rescore_nt reports them);
+ *   mode 2   aa_match, codons, sub_sum, 0, nGap, bGap, mGap: over the kept codons without an I column, with word = 25 c0 + 5 c1 + c2 of the three codes and
+ *            qa = aa_of_word[query word], ra = aa_of_word[reference word]: their number, those with qa == ra, and the (signed) sum of sub[(qa << 5) + ra].
+ * The float identity and score are the caller's (peppan_amd.uberBlast.codon_scores_from_counts keeps the reference's order of operations), and so are the
+ * two tables: aa_of_word[125] (every entry below 32) and sub[1024], read in mode 2 only (mode 3 takes NULL).
+ * PEP_ERR_ARG: a mode other than 2 or 3, a NULL table or an aa_of_word entry of 32 or more in mode 2, and what pep_rescore_nt refuses, in its words behind
+ * this function's name.  PEP_ERR_STATE before both nucleotide sets are given.  On an error nothing is written to out and the context stays usable; n == 0
+ * is PEP_OK.  pep_rescore_codons_check runs the host checks alone - no context, no device - over the offsets (q_off[n_q + 1], r_off[n_r + 1]) of the two
+ * nucleotide sets; the message goes to msg (msg_cap bytes, 0-terminated). */
+int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode,
+                       const uint8_t *aa_of_word /*[125], mode 2*/, const int8_t *sub /*[1024], mode 2*/, int64_t *out /*[7 n]*/);
+int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode,
+                             const uint8_t *aa_of_word, const int8_t *sub, const uint64_t *q_off, uint64_t n_q,
+                             const uint64_t *r_off, uint64_t n_r, char *msg, uint64_t msg_cap);
 
 /* K7 as the tail of every search of this context (-s 1 in PEPPAN's hot call, PEPPAN.py:229-230: every hit of both tools is rescored, uberBlast.py:352-353):
  * with on = 1 pep_search ends with the count of identical nucleotide columns of every hit it emits - K7's n_match, the one of its five counts that needs the

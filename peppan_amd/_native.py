@@ -15,7 +15,7 @@ EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy
            'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
            'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
            'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
-           'pep_merge_hits', 'pep_rescore_nt', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
+           'pep_merge_hits', 'pep_rescore_nt', 'pep_rescore_codons', 'pep_rescore_codons_check', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
            'pep_similar_classify', 'pep_similar_scan', 'pep_pair_support', 'pep_similar_resolve', 'pep_fasta_keep', 'pep_fasta_scan', 'pep_fasta_records', 'pep_store_mat_member', 'pep_store_seq_member', 'pep_store_tab_members', 'pep_store_tab_archive', 'pep_deflate_literals', 'pep_deflate_fast', 'pep_crc32', 'pep_pack_member', 'pep_argsort_object_order',
            'pep_set_nt_match', 'pep_result_nt_match', 'pep_table_from_hits', 'pep_cols_fix_end', 'pep_cols_order', 'pep_cols_gather', 'pep_lex_order', 'pep_set_host_threads']
 
@@ -327,6 +327,47 @@ def group_verdicts_check(packed, row_off, row_len, groups, genomes, inparalog, g
     rc = lib.pep_group_verdicts_check(*args, C.c_double(self_id), msg, C.c_uint64(len(msg)))
     if rc != 0:
         raise PepError('pep_group_verdicts_check failed (%d): %s' % (rc, msg.value.decode()))
+
+
+def codon_tables(table_id=11):
+    """(aa_of_word uint8[125], sub int8[1024]) for rescoring mode 2, made from the module tables of peppan_amd.uberBlast / configure - the one source, the library
+    holds no copy: gtable (for table 4 entry 56 becomes 22, the reference's own patch, uberBlast.py:223-224) and blosum62 padded to 32 x 32"""
+    from .uberBlast import gtable
+    from .configure import blosum62
+    aa = np.array(gtable).reshape(-1)
+    if table_id == 4:
+        aa = aa.copy()
+        aa[56] = 22
+    sub = np.zeros(1024, dtype=np.float64)
+    flat = np.asarray(blosum62, dtype=np.float64).reshape(-1)
+    assert aa.shape == (125,) and len(flat) <= 1024
+    sub[:len(flat)] = flat
+    for name, t, lo, hi in (('gtable', aa, 0, 255), ('blosum62', sub, -128, 127)):
+        assert np.all(t == np.round(t)) and t.min() >= lo and t.max() <= hi, name + ': entries must be integers in range'
+    return np.ascontiguousarray(aa, dtype=np.uint8), np.ascontiguousarray(sub, dtype=np.int8)
+
+
+def _codon_args(nt_hits, cigar, mode, tables):
+    """the leading arguments of pep_rescore_codons / pep_rescore_codons_check behind the context + what keeps them alive; tables: (aa_of_word, sub) or None"""
+    nt_hits = np.ascontiguousarray(nt_hits, dtype=NT_HIT_DTYPE)
+    cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    cg = cigar if len(cigar) else np.zeros(1, np.uint32)
+    hh = nt_hits if len(nt_hits) else np.zeros(1, NT_HIT_DTYPE)
+    aa, sub = (None, None) if tables is None else (None if t is None else np.ascontiguousarray(t, dtype=d) for t, d in zip(tables, (np.uint8, np.int8)))
+    args = [C.c_uint64(len(nt_hits)), _ptr(hh), _ptr(cg), C.c_uint64(len(cigar)), C.c_int32(int(mode)), None if aa is None else _ptr(aa), None if sub is None else _ptr(sub)]
+    return args, [hh, cg, aa, sub]
+
+
+def rescore_codons_check(nt_hits, cigar, mode, q_off, r_off, table_id=11, tables='module'):
+    """the host checks of pep_rescore_codons alone (no context, no device): PepError with the library's code and text, else None.  q_off / r_off:
+    offsets [n + 1] of the two nucleotide sets; tables: (aa_of_word, sub) instead of the module's own for table_id (None, or a None entry: a NULL pointer)"""
+    lib = load_library()
+    args, keep = _codon_args(nt_hits, cigar, mode, codon_tables(table_id) if isinstance(tables, str) else tables)
+    q_off, r_off = np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(r_off, dtype=np.uint64)
+    msg = C.create_string_buffer(512)
+    rc = lib.pep_rescore_codons_check(*args, _ptr(q_off), C.c_uint64(len(q_off) - 1), _ptr(r_off), C.c_uint64(len(r_off) - 1), msg, C.c_uint64(len(msg)))
+    if rc != 0:
+        raise PepError('pep_rescore_codons_check failed (%d): %s' % (rc, msg.value.decode()))
 
 
 def ovl_filter(q, r, qs, qe, ss, se, score, iden, coverage, delta):
@@ -1100,6 +1141,15 @@ class Context(object):
         if len(nt_hits):
             cg = cigar if len(cigar) else np.zeros(1, np.uint32)
             self._check(self._lib.pep_rescore_nt(self._h, C.c_uint64(len(nt_hits)), _ptr(nt_hits), _ptr(cg), C.c_uint64(len(cigar)), _ptr(out)), 'pep_rescore_nt')
+        return out
+
+    def rescore_codons(self, nt_hits, cigar, mode, table_id=11):
+        """K7 over the codon grid (pep_rescore_codons): the integer counts of rescoring modes 2 / 3 per hit -> int64[n, 7], mode 3
+        (hit0, hit1, hit2, paired, n_gap, b_gap, m_gap), mode 2 (aa_match, codons, sub_sum, 0, n_gap, b_gap, m_gap); uberBlast.codon_scores_from_counts
+        turns them into identity and score.  The amino-acid and substitution tables of mode 2 are this package's (codon_tables)"""
+        args, keep = _codon_args(nt_hits, cigar, mode, codon_tables(table_id) if mode == 2 else None)
+        out = np.zeros((len(nt_hits), 7), dtype=np.int64)
+        self._check(self._lib.pep_rescore_codons(self._h, *args, _ptr(out if len(out) else np.zeros(7, np.int64))), 'pep_rescore_codons')
         return out
 
     # ---- K14

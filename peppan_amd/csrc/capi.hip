@@ -1064,6 +1064,27 @@ int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint3
     return pep_k7_rescore(ctx, n, hits, cigar, n_cigar, out);
 }
 
+int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
+                       const int8_t *sub, int64_t *out)
+{
+    if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return pep_k7_codons(ctx, n, hits, cigar, n_cigar, mode, aa_of_word, sub, out);
+}
+
+int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
+                             const int8_t *sub, const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, char *msg, uint64_t msg_cap)
+{
+    std::string text;
+    const int rc = pep_k7_codons_check(n, hits, cigar, n_cigar, mode, aa_of_word, sub, q_off, n_q, r_off, n_r, text);
+    if (msg && msg_cap) {
+        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
+        memcpy(msg, text.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
+}
+
 int pep_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *a, const uint32_t *b, uint32_t *label)
 {
     if (!ctx || (n_nodes && !label) || (n_edges && (!a || !b))) return PEP_ERR_ARG;

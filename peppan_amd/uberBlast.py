@@ -290,10 +290,29 @@ def rescore_alignments(run_len, run_op, run_owner, q_cat, q_at, r_cat, r_at, fir
     return n_match / n_total, np.bincount(codon_owner, weights=blosum62[(q_aa << 5) + r_aa], minlength=n) - gap_cost_open - gap_cost_len
 
 
+def codon_scores_from_counts(counts, mode, gap_open=6, gap_extend=1):
+    """(identity, score) as float64 arrays from the integer counts of K7's codon grid (Context.rescore_codons: int64[n, 7]), with the expressions of
+    rescore_alignments' modes 3 and 2 above in their order of operations - the three weighted position counts added left to right, the gap terms as they
+    stand there.  A hit without a whole codon gives 0 / 0 = nan, as the reference gives it."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 7).astype(np.float64)
+    n_gap, b_gap, m_gap = c[:, 4], c[:, 5], c[:, 6]
+    gap_cost_open, gap_cost_len = n_gap * (gap_open - gap_extend), b_gap * gap_extend
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if mode == 3:
+            n_match = c[:, 0] * _CODON_WEIGHT[0] + c[:, 1] * _CODON_WEIGHT[1] + c[:, 2] * _CODON_WEIGHT[2]
+            n_mis = c[:, 3] - n_match
+            return n_match / (n_match + n_mis + b_gap - m_gap), n_match * 3 - n_mis * 1 - gap_cost_open - gap_cost_len
+        if mode != 2:
+            raise ValueError('codon_scores_from_counts: mode 2 or 3')
+        n_match = c[:, 0] * 3.
+        n_total = c[:, 1] * 3. + b_gap - m_gap
+        return n_match / n_total, c[:, 2] - gap_cost_open - gap_cost_len
+
+
 def cigar2score(data):
     """(cigar, rSeq, qSeq, frame, mode, gapOpen, gapExtend, table_id) -> (identity, score): the reference's per-alignment entry point
-    (uberBlast.py:221), one alignment through rescore_alignments.  RunBlast.reScore does not come through here: mode 1 is counted on the
-    GPU (K7), modes 2 / 3 take all rows of the table in one call."""
+    (uberBlast.py:221), one alignment through rescore_alignments.  RunBlast.reScore does not come through here: all three modes are counted on
+    the GPU (K7; _rescore_table)."""
     cigar, r_seq, q_seq, frame, mode, gap_open, gap_ext, table_id = data
     iden, score = rescore_alignments([n for n, op in cigar], [_OP_CODE[op] for n, op in cigar], np.zeros(len(cigar), dtype=np.int64),
                                      q_seq, [0], r_seq, [0], [frame], mode, gap_open, gap_ext, table_id)
@@ -755,13 +774,16 @@ class RunBlast(object):
         return self._rescore_table(ref, qry, HitTable.from_rows(blastab), mode, min_id, table_id).to_rows()
 
     def _rescore_table(self, ref, qry, T, mode, min_id, table_id=11, cut=True, ctx=None):
-        """Mode 1: integer counts on the GPU (K7), float arithmetic and np.round in float64 here.  Modes 2 / 3 (amino-acid / codon-position
-        scoring, not used by PEPPAN's calls) walk the rows on the host.  cut=False: identity and score are replaced in place and every row stays"""
+        """All three modes: integer counts on the GPU (K7: rescore_nt for mode 1, rescore_codons for the amino-acid / codon-position scoring of modes
+        2 / 3), float arithmetic and np.round in float64 here.  A context object that has no rescore_codons (a stand-in of the host tests) takes the host
+        walk of rescore_alignments for modes 2 / 3; N.Context always has the method, so the product never takes that branch.
+        cut=False: identity and score are replaced in place and every row stays"""
         self._load(ref, qry)
         if len(T) == 0:
             return T
-        if mode == 1:
-            ctx = ctx or get_context(self.device)
+        ctx = ctx or get_context(self.device)
+        on_gpu = mode == 1 or hasattr(ctx, 'rescore_codons')
+        if on_gpu:
             self._ensure_nt(ctx)
             h = np.zeros(len(T), dtype=N.NT_HIT_DTYPE)
             # (a table of this instance's own tools carries the name tables the sides were prepared with: row codes ARE sequence indices)
@@ -769,10 +791,13 @@ class RunBlast(object):
             h['r'] = T.ri if T.r_tab is self._r_tab else np.array([self.r_index[str(x)] for x in T.r_tab], dtype=np.int64)[T.ri]
             h['qs'], h['qe'], h['rs'], h['re'] = T.qs, T.qe, T.ss, T.se
             h['cigar_runs'], h['cigar_off'] = T.c_runs, T.c_off
+        if mode == 1:
             c = ctx.rescore_nt(h, T.arena).astype(np.int64)
             n_match, n_mis, n_gap, b_gap, m_gap = c.T
             iden = n_match.astype(np.float64) / (n_match + n_mis + b_gap - m_gap)
             score = (n_match * 3 - n_mis - n_gap * (6 - 1) - b_gap * 1).astype(np.float64)
+        elif on_gpu:
+            iden, score = codon_scores_from_counts(ctx.rescore_codons(h, T.arena, mode, table_id), mode, 6, 1)
         else:
             # the aligned stretch of every row's query and reference (reverse strand: complemented and turned), back to back, then ONE call
             enc = {}
