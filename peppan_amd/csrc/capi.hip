@@ -1061,7 +1061,7 @@ int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint3
 {
     if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k7_rescore(ctx, n, hits, cigar, n_cigar, out);
+    return pep_k7_table(ctx, "pep_rescore_nt", n, hits, cigar, n_cigar, 1, nullptr, nullptr, 5, out);
 }
 
 int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
@@ -1069,7 +1069,7 @@ int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const u
 {
     if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k7_codons(ctx, n, hits, cigar, n_cigar, mode, aa_of_word, sub, out);
+    return pep_k7_table(ctx, "pep_rescore_codons", n, hits, cigar, n_cigar, mode, aa_of_word, sub, 7, out);
 }
 
 int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,

@@ -330,12 +330,12 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n_cands, const in
 int pep_extend_finish(pep_ctx *ctx);
 int pep_selftest_dpp(pep_ctx *ctx);
 // ---- rescore.hip (K7)
-int pep_k7_rescore(pep_ctx *ctx, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int64_t *h_out);
+// pep_rescore_nt (mode 1, no tables, width 5) and pep_rescore_codons (its mode and tables, width 7): checks, upload, k7_table<mode>, h_out[n, width]; `who` leads the messages
+int pep_k7_table(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode,
+                 const uint8_t *aa_of_word, const int8_t *sub, uint32_t width, int64_t *h_out);
 // the host checks of a table of hits, shared by pep_rescore_nt and pep_rescore_codons (`who` leads the message)
 int pep_k7_check(const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, const uint64_t *q_off, uint64_t n_q,
                  const uint64_t *r_off, uint64_t n_r, std::string &msg);
-int pep_k7_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
-                  const int8_t *sub, int64_t *h_out);
 int pep_k7_codons_check(uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word, const int8_t *sub,
                         const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, std::string &msg);
 // ---- unionfind.hip (K10)

@@ -12,8 +12,7 @@ import os
 
 import numpy as np
 
-from rescore_helpers import OPS, encode, hit_runs, pack_runs, revcomp, unpack_runs
-from peppan_amd._native import NT_HIT_DTYPE
+from rescore_helpers import OPS, encode, hit_table, pack_runs, random_bases, revcomp, unpack_runs
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 with open(os.path.join(GOLDEN, 'g01_tables.json')) as _f:
@@ -162,15 +161,11 @@ def assert_codon_coverage(cov, least=20):
 
 
 # ---------------------------------------------------------------------------------------------------------------- planted hits
-def _bases(rng, n):
-    return rng.choice(np.frombuffer(b'ACGT', dtype=np.uint8), n).tobytes()
-
-
 def planted_codon_hits(rng, per_class=24):
     """-> (q_seqs, r_seqs, rows, arena words): hits of the classes random_hits (made for mode 1) reaches rarely or never, every one with its own query and its
     own run words; the reference is one sequence and its reverse complement, a hit lies on either.  Rows are NT_HIT_DTYPE tuples with cigar_off counted from
     the start of the returned words."""
-    R = _bases(rng, 600)
+    R = random_bases(rng, 600)
     r_seqs = [R, revcomp(R)]
     q_seqs, rows, arena = [], [], []
 
@@ -180,7 +175,7 @@ def planted_codon_hits(rng, per_class=24):
         rev = int(rng.integers(0, 2))
         ra = sum(n for n, t in runs if t != 'I')
         assert len(q_body) == sum(n for n, t in runs if t != 'D') and ra >= 1 and lo + ra <= len(R)
-        q_seqs.append(_bases(rng, pad) + q_body + _bases(rng, int(rng.integers(0, 4))))
+        q_seqs.append(random_bases(rng, pad) + q_body + random_bases(rng, int(rng.integers(0, 4))))
         a, b = lo + 1, lo + ra
         if rev:
             a, b = len(R) - a + 1, len(R) - b + 1
@@ -202,9 +197,9 @@ def planted_codon_hits(rng, per_class=24):
         add(R[lo:lo + 2], [[2, 'M']], lo, pad=1 + 3 * (i % 2))                       # phase 1, two columns: one beyond the phase, no whole codon
         # a leading I run, then M; and M | I | M with the I run inside one codon at every position
         g, m = 1 + i % 5, 5 + i % 7
-        add(_bases(rng, g) + mutate(R[lo:lo + m]), [[g, 'I'], [m, 'M']], lo)
+        add(random_bases(rng, g) + mutate(R[lo:lo + m]), [[g, 'I'], [m, 'M']], lo)
         a, g, b = 1 + i % 7, 1 + i % 4, 4 + i % 5
-        add(mutate(R[lo:lo + a]) + _bases(rng, g) + mutate(R[lo + a:lo + a + b]), [[a, 'M'], [g, 'I'], [b, 'M']], lo)
+        add(mutate(R[lo:lo + a]) + random_bases(rng, g) + mutate(R[lo + a:lo + a + b]), [[a, 'M'], [g, 'I'], [b, 'M']], lo)
         # M | D | M with the D run inside a codon
         add(mutate(R[lo:lo + a]) + mutate(R[lo + a + g:lo + a + g + b]), [[a, 'M'], [g, 'D'], [b, 'M']], lo)
         # word 56 = digits 2 1 1 = "NCC" in the query's frame: on the query side, on the reference side (the query then reads the reference's bases
@@ -217,7 +212,7 @@ def planted_codon_hits(rng, per_class=24):
         body[6:7] = b'N'
         add(bytes(body), [[m, 'M']], lo, pad=3 * (i % 2))
     # the reference side of word 56 and of N: a reference of its own that carries them, read on either strand
-    special = bytearray(_bases(rng, 300))
+    special = bytearray(random_bases(rng, 300))
     for at in range(9, 290, 30):
         special[at:at + 3] = b'NCC'
         special[at + 15:at + 16] = b'N'
@@ -233,7 +228,7 @@ def planted_codon_hits(rng, per_class=24):
         if i % 3 == 1:
             q_body[at + 15 - lo:at + 16 - lo] = b'G'                               # N on the reference side only
         rev = i % 2
-        q_seqs.append(_bases(rng, 3 * (i % 3)) + bytes(q_body) + _bases(rng, 2))
+        q_seqs.append(random_bases(rng, 3 * (i % 3)) + bytes(q_body) + random_bases(rng, 2))
         pad = 3 * (i % 3)
         a, b = lo + 1, lo + m
         if rev:
@@ -246,34 +241,5 @@ def planted_codon_hits(rng, per_class=24):
 def with_planted(rng, q_seqs, r_seqs, hits, arena, per_class=24):
     """the output of random_hits with planted_codon_hits appended -> (q_seqs, r_seqs, hits, arena)"""
     pq, pr, rows, words = planted_codon_hits(rng, per_class)
-    extra = np.zeros(len(rows), dtype=NT_HIT_DTYPE)
-    for k, row in enumerate(rows):
-        extra[k] = (row[0] + len(q_seqs), row[1] + len(r_seqs)) + tuple(row[2:8]) + (row[8] + len(arena),)
+    extra = hit_table([(row[0] + len(q_seqs), row[1] + len(r_seqs)) + tuple(row[2:8]) + (row[8] + len(arena),) for row in rows])
     return list(q_seqs) + pq, list(r_seqs) + pr, np.concatenate([hits, extra]), np.concatenate([arena, np.array(words, dtype=np.uint32)])
-
-
-# ---------------------------------------------------------------------------------------------------------------- bad tables
-def bad_tables(q_seqs, r_seqs, hits, arena):
-    """[(what, hits, arena, n_cigar, message)] - every table pep_rescore_nt's checks refuse, made from a good one (shared with the GPU test)"""
-    victim = int(np.flatnonzero((hits['rs'] < hits['re']) & (hits['cigar_runs'] >= 3))[1:][0])
-    assert 0 < victim < len(hits) - 1
-
-    def bad(**fields):
-        h = hits.copy()
-        for f, v in fields.items():
-            h[f][victim] = v
-        return h
-    v = hits[victim]
-    ql, rl = len(q_seqs[v['q']]), len(r_seqs[v['r']])
-    index, coords = 'pep_rescore_codons: hit index out of range', 'pep_rescore_codons: CIGAR inconsistent with the hit coordinates'
-    assert int((hits['cigar_off'] + hits['cigar_runs']).max()) == len(arena)
-    spoiled = np.concatenate([arena, np.array(pack_runs(hit_runs(hits, arena, victim)), dtype=np.uint32)])
-    spoiled[len(arena) + 1] |= 3
-    n = len(arena)
-    return [('q', bad(q=len(q_seqs)), arena, n, index), ('r', bad(r=len(r_seqs)), arena, n, index), ('slice', bad(cigar_off=n - 1), arena, n, index),
-            ('slice beyond 2^64', bad(cigar_off=2 ** 64 - 1), arena, n, index), ('short arena', hits, arena, n - 1, index),
-            ('qs 0', bad(qs=0), arena, n, coords), ('query end', bad(qs=int(v['qs']) + (ql - int(v['qe'])) + 1), arena, n, coords),
-            ('re past', bad(rs=int(v['rs']) + (rl - int(v['re'])) + 1, re=rl + 1), arena, n, coords),
-            ('rs 0', bad(rs=0, re=int(v['re']) - int(v['rs'])), arena, n, coords), ('re 0', bad(rs=int(v['re']) - int(v['rs']), re=0), arena, n, coords),
-            ('span', bad(re=int(v['re']) + 1) if v['re'] < rl else bad(re=int(v['re']) - 1), arena, n, coords),
-            ('op 3', bad(cigar_off=n), spoiled, len(spoiled), 'pep_rescore_codons: unknown CIGAR op')]

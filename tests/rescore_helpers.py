@@ -152,6 +152,11 @@ def _consumed(runs):
     return sum(n for n, t in runs if t != 'D'), sum(n for n, t in runs if t != 'I')
 
 
+COVERAGE_CLASSES = ('forward', 'reverse', 'one_base', 'reverse_with_I', 'reverse_with_D', 'forward_with_I', 'forward_with_D', 'mgap', 'gap_1_or_2', 'leading_gap',
+                    'trailing_gap', 'other_q', 'other_r', 'shared_cigar', 'lower_case_q', 'lower_case_r') + tuple(
+                        'flush_%s_%s' % (end, strand) for strand in ('forward', 'reverse') for end in ('q_start', 'q_end', 'r_low', 'r_high'))
+
+
 def random_hits(rng, n_q, n_r, n_hits, max_len=700):
     """-> (q_seqs, r_seqs, hits [NT_HIT_DTYPE], arena uint32, coverage dict).  Sequences are bytes; hit k's runs are
     arena[hits['cigar_off'][k]:][:hits['cigar_runs'][k]].  Built in, not left to luck: M runs of M_EDGES and of random lengths up to 300; I and D runs of
@@ -221,11 +226,7 @@ def random_hits(rng, n_q, n_r, n_hits, max_len=700):
         hits[k] = (i, j, qs, qs + qa - 1, hi if rev else lo, lo if rev else hi, len(runs), 0, off)
     arena = np.array(arena, dtype=np.uint32)
 
-    cov = dict.fromkeys(('forward', 'reverse', 'one_base', 'reverse_with_I', 'reverse_with_D', 'forward_with_I', 'forward_with_D', 'mgap', 'gap_1_or_2',
-                         'leading_gap', 'trailing_gap', 'other_q', 'other_r', 'shared_cigar', 'lower_case_q', 'lower_case_r'), 0)
-    for strand in ('forward', 'reverse'):
-        for end in ('q_start', 'q_end', 'r_low', 'r_high'):
-            cov['flush_%s_%s' % (end, strand)] = 0
+    cov = dict.fromkeys(COVERAGE_CLASSES, 0)
     ratios, m_runs, gap_runs, seen_off = set(), set(), set(), set()
     for h in hits.tolist():
         i, j, qs, qe, rs, re, n_runs, _, off = h
@@ -275,11 +276,6 @@ def reference_table(q_seqs, r_seqs, hits, arena):
     return out
 
 
-COVERAGE_CLASSES = ('forward', 'reverse', 'one_base', 'reverse_with_I', 'reverse_with_D', 'forward_with_I', 'forward_with_D', 'mgap', 'gap_1_or_2', 'leading_gap',
-                    'trailing_gap', 'other_q', 'other_r', 'shared_cigar', 'lower_case_q', 'lower_case_r') + tuple(
-                        'flush_%s_%s' % (end, strand) for strand in ('forward', 'reverse') for end in ('q_start', 'q_end', 'r_low', 'r_high'))
-
-
 def assert_coverage(cov, least=20):
     """the conditions a comparison over random_hits' output relies on: they are on the inputs, so they are checked before anything is compared"""
     for key in COVERAGE_CLASSES:
@@ -289,3 +285,54 @@ def assert_coverage(cov, least=20):
     assert cov['m_runs'] >= set(M_EDGES) and max(cov['m_runs']) > 200
     assert cov['gap_runs'] == {(g, t) for g in GAPS for t in 'ID'}
     assert cov['first_cigar_off'] > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- what the GPU tests of both kernel families build with
+# a base that is neither the one it replaces nor its complement: a planted mismatch is one on either strand, also in a one-base range
+OTHER_BASE = bytes.maketrans(b'ACGT', b'CATG')
+
+
+def load(ctx, q_seqs, r_seqs):
+    ctx.set_query_nt(q_seqs, 11)
+    ctx.set_ref_nt(r_seqs, 6, 11)
+
+
+def planted(seq, at):
+    s = bytearray(seq)
+    s[at:at + 1] = bytes(s[at:at + 1]).translate(OTHER_BASE)
+    return bytes(s)
+
+
+def random_bases(rng, n):
+    return rng.choice(np.frombuffer(b'ACGT', dtype=np.uint8), n).tobytes()
+
+
+def hit_table(rows):
+    return np.array(rows, dtype=NT_HIT_DTYPE)
+
+
+def bad_tables(who, q_seqs, r_seqs, hits, arena):
+    """[(what, hits, arena, n_cigar, message)] - every table the check shared by pep_rescore_nt and pep_rescore_codons refuses, made from a good one; `who`,
+    the entry point's name, leads the message.  The last one is the victim's own runs behind the arena, the second of them with op code 3."""
+    victim = int(np.flatnonzero((hits['rs'] < hits['re']) & (hits['cigar_runs'] >= 3))[1:][0])    # a forward hit of several runs, somewhere among good ones
+    assert 0 < victim < len(hits) - 1
+
+    def bad(**fields):
+        h = hits.copy()
+        for f, v in fields.items():
+            h[f][victim] = v
+        return h
+    v = hits[victim]
+    ql, rl = len(q_seqs[v['q']]), len(r_seqs[v['r']])
+    index, coords = who + ': hit index out of range', who + ': CIGAR inconsistent with the hit coordinates'
+    assert int((hits['cigar_off'] + hits['cigar_runs']).max()) == len(arena)
+    spoiled = np.concatenate([arena, np.array(pack_runs(hit_runs(hits, arena, victim)), dtype=np.uint32)])
+    spoiled[len(arena) + 1] |= 3
+    n = len(arena)
+    return [('q', bad(q=len(q_seqs)), arena, n, index), ('r', bad(r=len(r_seqs)), arena, n, index), ('slice', bad(cigar_off=n - 1), arena, n, index),
+            ('slice beyond 2^64', bad(cigar_off=2 ** 64 - 1), arena, n, index), ('short arena', hits, arena, n - 1, index),
+            ('qs 0', bad(qs=0), arena, n, coords), ('query end', bad(qs=int(v['qs']) + (ql - int(v['qe'])) + 1), arena, n, coords),
+            ('re past', bad(rs=int(v['rs']) + (rl - int(v['re'])) + 1, re=rl + 1), arena, n, coords),
+            ('rs 0', bad(rs=0, re=int(v['re']) - int(v['rs'])), arena, n, coords), ('re 0', bad(rs=int(v['re']) - int(v['rs']), re=0), arena, n, coords),
+            ('span', bad(re=int(v['re']) + 1) if v['re'] < rl else bad(re=int(v['re']) - 1), arena, n, coords),
+            ('op 3', bad(cigar_off=n), spoiled, len(spoiled), who + ': unknown CIGAR op')]

@@ -1,4 +1,4 @@
-"""K7 on the GPU - k7_rescore behind Context.rescore_nt and k7_hits as the tail of a search (Context.set_nt_match) - against the slice-by-slice
+"""K7 on the GPU - k7_table<1> behind Context.rescore_nt and k7_hits as the tail of a search (Context.set_nt_match) - against the slice-by-slice
 restatement of the reference's lines in tests/rescore_helpers.py.  Integers and two float64 values: everything is compared with ==."""
 import ctypes as C
 import os
@@ -8,14 +8,13 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from rescore_helpers import (assert_coverage, encode, hit_runs, pack_runs, random_hits, reference_counts, reference_identity_score,  # noqa: E402
-                             reference_table, revcomp, unpack_runs)
+from rescore_helpers import (assert_coverage, bad_tables, encode, hit_runs, hit_table, load, pack_runs, planted, random_bases, random_hits,  # noqa: E402
+                             reference_counts, reference_identity_score, reference_table, revcomp, unpack_runs)
+from rescore_codon_helpers import with_planted  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7777
-# a base that is neither the one it replaces nor its complement: a planted mismatch is one on either strand, also in a one-base range
-OTHER_BASE = bytes.maketrans(b'ACGT', b'CATG')
 
 
 @pytest.fixture(scope='module')
@@ -25,29 +24,6 @@ def ctx():
     from peppan_amd import _native as N
     with N.Context(0) as c:
         yield c
-
-
-def hit_table(rows):
-    from peppan_amd import _native as N
-    hits = np.zeros(len(rows), dtype=N.NT_HIT_DTYPE)
-    for k, row in enumerate(rows):
-        hits[k] = row
-    return hits
-
-
-def load(ctx, q_seqs, r_seqs):
-    ctx.set_query_nt(q_seqs, 11)
-    ctx.set_ref_nt(r_seqs, 6, 11)
-
-
-def planted(seq, at):
-    s = bytearray(seq)
-    s[at:at + 1] = bytes(s[at:at + 1]).translate(OTHER_BASE)
-    return bytes(s)
-
-
-def random_bases(rng, n):
-    return rng.choice(np.frombuffer(b'ACGT', dtype=np.uint8), n).tobytes()
 
 
 @pytest.mark.parametrize('seed', [71, 72, 73])
@@ -202,6 +178,19 @@ def test_float_end_of_the_rescored_table(ctx):
         assert np.array_equal(cut.rid, keep) and np.array_equal(cut.iden, want[keep, 0]) and np.array_equal(cut.score, want[keep, 1])
 
 
+@pytest.mark.parametrize('mode', [2, 3])
+def test_gap_counts_agree_across_the_modes(ctx, mode):
+    """k7_table<1> and k7_table<2 | 3> take a hit's gap counts with the same pass: on the fuzz table both files build, columns 2:5 of rescore_nt are
+    columns 4:7 of rescore_codons (each side is held to its restatement elsewhere)"""
+    rng = np.random.default_rng(413)
+    q_seqs, r_seqs, hits, arena, _ = random_hits(rng, 30, 30, 1500)
+    q_seqs, r_seqs, hits, arena = with_planted(rng, q_seqs, r_seqs, hits, arena, per_class=6)
+    load(ctx, q_seqs, r_seqs)
+    gaps = ctx.rescore_nt(hits, arena)[:, 2:5]
+    assert len(hits) > 1500 and (gaps[:, 2] > 0).sum() >= 20 and ((gaps[:, 0] > 0) & (gaps[:, 2] == 0)).sum() >= 20
+    assert np.array_equal(gaps, ctx.rescore_codons(hits, arena, mode)[:, 4:7])
+
+
 # ---------------------------------------------------------------------------------------------------------------- k7_hits
 @pytest.fixture(scope='module')
 def genes_and_contigs():
@@ -293,8 +282,6 @@ def test_error_conventions_and_context_stays_usable(ctx):
     q_seqs, r_seqs, hits, arena, _ = random_hits(np.random.default_rng(9), 12, 12, 120)
     load(ctx, q_seqs, r_seqs)
     want = reference_table(q_seqs, r_seqs, hits, arena)
-    victim = int(np.flatnonzero((hits['rs'] < hits['re']) & (hits['cigar_runs'] >= 3))[1:][0])    # a forward hit of several runs, somewhere among good ones
-    assert 0 < victim < len(hits) - 1
 
     def raw(c, h, cigar, n_cigar=None):
         out = np.full((len(h), 5), SENTINEL, dtype=np.int64)
@@ -310,30 +297,13 @@ def test_error_conventions_and_context_stays_usable(ctx):
             c.rescore_nt(h, cigar[:len(cigar) if n_cigar is None else n_cigar])
         assert np.array_equal(c.rescore_nt(hits, arena), want)                         # ... and the context goes on
 
-    def bad(**fields):
-        h = hits.copy()
-        for f, v in fields.items():
-            h[f][victim] = v
-        return h
-    v = hits[victim]
-    ql, rl = len(q_seqs[v['q']]), len(r_seqs[v['r']])
-    index, coords = 'pep_rescore_nt: hit index out of range', 'pep_rescore_nt: CIGAR inconsistent with the hit coordinates'
-    refused(ctx, bad(q=len(q_seqs)), arena, -2, index)
-    refused(ctx, bad(r=len(r_seqs)), arena, -2, index)
-    refused(ctx, bad(cigar_off=len(arena) - 1), arena, -2, index)                      # the slice runs past the arena
-    assert int((hits['cigar_off'] + hits['cigar_runs']).max()) == len(arena)
-    refused(ctx, hits, arena, -2, index, n_cigar=len(arena) - 1)                       # ... and so does the last slice of an arena one word short
-    refused(ctx, bad(qs=0), arena, -2, coords)
-    refused(ctx, bad(qs=int(v['qs']) + (ql - int(v['qe'])) + 1), arena, -2, coords)      # the query end one base past the sequence
-    refused(ctx, bad(rs=int(v['rs']) + (rl - int(v['re'])) + 1, re=rl + 1), arena, -2, coords)       # re past the reference, the range as long as before
-    refused(ctx, bad(rs=0, re=int(v['re']) - int(v['rs'])), arena, -2, coords)         # the lower reference coordinate 0, the range as long as before
-    refused(ctx, bad(rs=int(v['re']) - int(v['rs']), re=0), arena, -2, coords)         # ... on the reverse strand
-    refused(ctx, bad(re=int(v['re']) + 1) if v['re'] < rl else bad(re=int(v['re']) - 1), arena, -2, coords)      # reference columns != |re - rs| + 1
-    runs = hit_runs(hits, arena, victim)
-    spoiled = np.concatenate([arena, np.array(pack_runs(runs), dtype=np.uint32)])
-    spoiled[len(arena) + 1] |= 3                                                       # the victim's own runs, the second one with op code 3
-    refused(ctx, bad(cigar_off=len(arena)), spoiled, -2, 'pep_rescore_nt: unknown CIGAR op')
-    assert np.array_equal(ctx.rescore_nt(bad(cigar_off=len(arena)), np.concatenate([arena, np.array(pack_runs(runs), dtype=np.uint32)])), want)
+    cases = bad_tables('pep_rescore_nt', q_seqs, r_seqs, hits, arena)
+    for what, h, cg, n_cigar, text in cases:
+        refused(ctx, h, cg, -2, text, n_cigar=n_cigar)
+    what, h, _, _, _ = cases[-1]                                                       # the victim's own runs behind the arena: refused with op code 3 ...
+    victim = int(np.flatnonzero(h['cigar_off'] != hits['cigar_off'])[0])
+    own = arena[int(hits['cigar_off'][victim]):][:int(hits['cigar_runs'][victim])]
+    assert what == 'op 3' and np.array_equal(ctx.rescore_nt(h, np.concatenate([arena, own])), want)      # ... and taken as they are
     # before any nucleotide set was given: a context of its own
     with N.Context(0) as fresh:
         rc, out = raw(fresh, hits, arena)

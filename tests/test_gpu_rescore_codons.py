@@ -1,4 +1,4 @@
-"""K7's codon grid on the GPU - k7_codons behind Context.rescore_codons, rescoring modes 2 and 3 - against the slice-by-slice restatement of the reference's
+"""K7's codon grid on the GPU - k7_table<2> and k7_table<3> behind Context.rescore_codons, rescoring modes 2 and 3 - against the slice-by-slice restatement of the reference's
 lines in tests/rescore_codon_helpers.py and against rows written down in closed form.  Integers and two float64 values: everything is compared with ==."""
 import ctypes as C
 import os
@@ -8,14 +8,12 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from rescore_helpers import assert_coverage, hit_runs, pack_runs, random_hits, revcomp  # noqa: E402
-from rescore_codon_helpers import assert_codon_coverage, bad_tables, codon_coverage, reference_codon_table, with_planted  # noqa: E402
+from rescore_helpers import assert_coverage, bad_tables, hit_runs, hit_table, load, pack_runs, planted, random_bases, random_hits, revcomp  # noqa: E402
+from rescore_codon_helpers import assert_codon_coverage, codon_coverage, reference_codon_table, with_planted  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7777
-# a base that is neither the one it replaces nor its complement: a planted mismatch is one on either strand
-OTHER_BASE = bytes.maketrans(b'ACGT', b'CATG')
 STRIDE_W = 200               # codons of the longest run of test_codon_stride_table
 
 
@@ -26,29 +24,6 @@ def ctx():
     from peppan_amd import _native as N
     with N.Context(0) as c:
         yield c
-
-
-def load(ctx, q_seqs, r_seqs):
-    ctx.set_query_nt(q_seqs, 11)
-    ctx.set_ref_nt(r_seqs, 6, 11)
-
-
-def planted(seq, at):
-    s = bytearray(seq)
-    s[at:at + 1] = bytes(s[at:at + 1]).translate(OTHER_BASE)
-    return bytes(s)
-
-
-def random_bases(rng, n):
-    return rng.choice(np.frombuffer(b'ACGT', dtype=np.uint8), n).tobytes()
-
-
-def hit_table(rows):
-    from peppan_amd import _native as N
-    hits = np.zeros(len(rows), dtype=N.NT_HIT_DTYPE)
-    for k, row in enumerate(rows):
-        hits[k] = row
-    return hits
 
 
 def assert_rows(got, want, hits, arena):
@@ -265,7 +240,7 @@ def test_error_conventions_and_context_stays_usable(ctx):
             assert np.array_equal(c.rescore_codons(hits, arena, m), want[m])            # ... and the context goes on
 
     for mode in (2, 3):
-        for what, h, cg, n_cigar, text in bad_tables(q_seqs, r_seqs, hits, arena):
+        for what, h, cg, n_cigar, text in bad_tables('pep_rescore_codons', q_seqs, r_seqs, hits, arena):
             refused(ctx, h, cg, n_cigar, mode, (aa, sub), -2, text)
             if n_cigar == len(cg):
                 with pytest.raises(N.PepError, match=text):

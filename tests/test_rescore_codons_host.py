@@ -9,8 +9,8 @@ import pytest
 from conftest import load_golden
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from rescore_helpers import encode, hit_runs, random_hits  # noqa: E402
-from rescore_codon_helpers import bad_tables, load_g21, reference_codon_counts, with_planted  # noqa: E402
+from rescore_helpers import bad_tables, encode, hit_runs, random_hits  # noqa: E402
+from rescore_codon_helpers import load_g21, reference_codon_counts, with_planted  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,7 +101,7 @@ def test_check_entry_point():
         assert N.rescore_codons_check(hits, arena, mode, q_off, r_off) is None
         assert N.rescore_codons_check(hits, arena, mode, q_off, r_off, table_id=4) is None
         assert N.rescore_codons_check(hits[:0], arena[:0], mode, q_off, r_off) is None
-        for what, h, cg, n_cigar, text in bad_tables(q_seqs, r_seqs, hits, arena):
+        for what, h, cg, n_cigar, text in bad_tables('pep_rescore_codons', q_seqs, r_seqs, hits, arena):
             with pytest.raises(N.PepError, match=r'pep_rescore_codons_check failed \(-2\): %s$' % text):
                 N.rescore_codons_check(h, cg[:n_cigar], mode, q_off, r_off)
     assert N.rescore_codons_check(hits, arena, 3, q_off, r_off, tables=None) is None          # mode 3 reads no table

@@ -1,5 +1,5 @@
 """Config-size inputs for the kernels outside the all-vs-all step, for rocprofv3 (tools/profile_other.sh):
-   K7 k7_rescore + the nucleotide search : the reference's hot call on the 10k-gene FASTA (about 70 k hits rescored)
+   K7 k7_hits + the nucleotide search    : the reference's hot call on the 10k-gene FASTA (about 70 k hits rescored)
    K9 lc_*                               : linclust on 200 000 genes x ~1 kb
    K13 k13_sha1 / k13_table              : sha1 + duplicate collapse of 300 000 genes
    K11 ovl_sweep, K12 k12_*              : get_map_bsn, 10 000 exemplars x 8 genomes

@@ -1,8 +1,8 @@
-"""Rescoring modes 2 and 3 (K7's codon grid, csrc/rescore.hip: k7_codons) measured on one GPU beside the path they replace.
+"""Rescoring modes 2 and 3 (K7's codon grid, csrc/rescore.hip: k7_table<2>, k7_table<3>) measured on one GPU beside the path they replace.
     python tools/rescore_modes_rate.py [out.txt] [--hits N] [--gpu-only]
 A table shaped like the hot call's: 70 000 hits of about 1 000 columns - 2 000 genes of 900 .. 1 100 nt against mutated copies of them on either strand,
 every hit with 0 .. 3 gap runs of 1 .. 6 bases (fixed seed).  Reported per mode, in one process: the wall time of RunBlast._rescore_table through the GPU
-(upload of the table, k7_codons, float end), and beside it the host walk it took before K7 counted these modes - rescore_alignments fed by the same
+(upload of the table, k7_table, float end), and beside it the host walk it took before K7 counted these modes - rescore_alignments fed by the same
 function through a context object without rescore_codons, which is that path unchanged.  The two must give identical identity and score arrays, and that
 is asserted.  One warm-up call and the median of 5 for the GPU route, one call of the host walk (seconds, and gigabytes of temporaries).  --gpu-only leaves the
 host walk out: for a run under `rocprofv3 --kernel-trace --stats`, whose table gives the kernel's own time.  The lines are appended to the file named
@@ -103,7 +103,7 @@ with N.Context(0) as ctx:
             new = rb._rescore_table(None, None, T, mode, None, 11, cut=False, ctx=ctx)
             t.append(time.perf_counter() - t0)
         gpu_s = float(np.median(t))
-        say('mode %d  _rescore_table through the GPU (table upload + k7_codons + float end): median %.4f s (min %.4f, max %.4f) of 5' % (mode, gpu_s, min(t), max(t)))
+        say('mode %d  _rescore_table through the GPU (table upload + k7_table<%d> + float end): median %.4f s (min %.4f, max %.4f) of 5' % (mode, mode, gpu_s, min(t), max(t)))
         if gpu_only:
             continue
         T = table()
