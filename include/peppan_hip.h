@@ -50,8 +50,9 @@ extern "C" {
 #endif
 
 /* 17 gained, additively, the K16 entry points: pep_group_verdicts, pep_group_verdicts_check, pep_verdict_detail_size, pep_verdict_detail_copy,
- * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check. */
-#define PEP_ABI_VERSION 17
+ * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check.
+ * 18 gained pep_live_resources. */
+#define PEP_ABI_VERSION 18
 
 #define PEP_OK 0
 #define PEP_ERR_HIP (-1)       /* a HIP runtime call failed */
@@ -165,6 +166,9 @@ int pep_version(void);
 int pep_device_count(void);
 int pep_ctx_create(int device, pep_ctx **out);
 void pep_ctx_destroy(pep_ctx *ctx);
+/* what the library holds in this process right now, over all contexts: bytes of device buffers, bytes of pinned host buffers, HIP events.  Back at
+ * their earlier values once every context made since is destroyed (a result that outlives its context holds host memory only). */
+int pep_live_resources(uint64_t *device_bytes, uint64_t *pinned_bytes, uint32_t *events);
 const char *pep_last_error(const pep_ctx *ctx);
 void pep_default_params(pep_search_params *p);
 /* sensitivity of the translated search: 0 = DIAMOND's two default-mode seed shapes (what the reference's command line runs, uberBlast.py:550),

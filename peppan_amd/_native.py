@@ -8,10 +8,10 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpeppan_hip.so')
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 MAX_SEQ_LEN = (1 << 23) - 256          # PEP_MAX_SEQ_LEN: longest single sequence of a packed set
 ALLELE_DIFF_MAX_BYTES = 1 << 31        # PEP_ALLELE_DIFF_MAX_BYTES: output (and bit planes) of one pep_allele_diff call
-EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy', 'pep_last_error', 'pep_default_params', 'pep_set_sensitivity',
+EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy', 'pep_live_resources', 'pep_last_error', 'pep_default_params', 'pep_set_sensitivity',
            'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
            'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
            'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
@@ -123,6 +123,14 @@ def load_library():
         raise PepError('libpeppan_hip.so ABI version mismatch')
     _lib = lib
     return lib
+
+
+def live_resources():
+    """pep_live_resources: (bytes of device buffers, bytes of pinned host buffers, HIP events) the library holds in this process, over all contexts"""
+    dev, pin, ev = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    if load_library().pep_live_resources(C.byref(dev), C.byref(pin), C.byref(ev)) != 0:
+        raise PepError('pep_live_resources failed')
+    return dev.value, pin.value, ev.value
 
 
 DEFAULT_SHAPES = ('111101110111', '111011010010111')          # DIAMOND's two default-sensitivity shapes (weight 10)

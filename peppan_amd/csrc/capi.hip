@@ -30,33 +30,19 @@ int pep_fail(pep_ctx *ctx, int code, const std::string &msg)
 int dev_reserve(pep_ctx *ctx, DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p) return PEP_OK;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     size_t want = std::max<size_t>(bytes + bytes / 4, 256);
     want = (want + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return pep_fail(ctx, PEP_ERR_HIP, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
-    }
-    b.cap = want;
+    const hipError_t e = b.alloc(want);
+    if (e != hipSuccess) return pep_fail(ctx, PEP_ERR_HIP, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
     return PEP_OK;
-}
-
-void dev_release(DevBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
 }
 
 int pin_reserve(pep_ctx *ctx, PinBuf &b, size_t bytes)
 {
     if (bytes <= b.cap) return PEP_OK;
-    if (b.p) (void)hipHostFree(b.p);
-    b.p = nullptr; b.cap = 0;
     const size_t want = bytes + bytes / 4 + 4096;
-    PEP_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&b.p), want, hipHostMallocDefault));
-    b.cap = want;
+    const hipError_t e = b.alloc(want);
+    if (e != hipSuccess) return pep_fail(ctx, PEP_ERR_HIP, std::string("hipHostMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
     return PEP_OK;
 }
 
@@ -77,7 +63,7 @@ int pep_h2d(pep_ctx *ctx, void *d_dst, const void *h_src, size_t n)
     memcpy(ctx->pin_up.p + ctx->pin_up_used, h_src, n);
     PEP_HIP(ctx, hipMemcpyAsync(d_dst, ctx->pin_up.p + ctx->pin_up_used, n, hipMemcpyHostToDevice, ctx->stream));
     ctx->pin_up_used += need;
-    if (!ctx->up_event && hipEventCreateWithFlags(&ctx->up_event, pep_wait_event_flags()) != hipSuccess) return pep_fail(ctx, PEP_ERR_HIP, "hipEventCreate failed");
+    if (!ctx->up_event.ensure(pep_wait_event_flags())) return pep_fail(ctx, PEP_ERR_HIP, "hipEventCreate failed");
     PEP_HIP(ctx, hipEventRecord(ctx->up_event, ctx->stream));
     ctx->up_event_set = true;
     return PEP_OK;
@@ -116,7 +102,7 @@ void pep_d2h_finish(pep_ctx *ctx)
 void pep_timer_begin(pep_ctx *ctx, int id)
 {
     if (ctx->timing_level < (id == TM_SW ? 1 : 2)) return;        // (an event between two kernels costs about 6 us of idle GPU: pep_set_timing)
-    if (!ctx->tm_a[id] && (hipEventCreate(&ctx->tm_a[id]) != hipSuccess || hipEventCreate(&ctx->tm_b[id]) != hipSuccess)) { ctx->tm_a[id] = nullptr; return; }
+    if (!ctx->tm_a[id].ensure() || !ctx->tm_b[id].ensure()) return;
     ctx->tm_state[id] = hipEventRecord(ctx->tm_a[id], ctx->stream) == hipSuccess ? 1 : 0;
 }
 
@@ -219,7 +205,7 @@ hipError_t pep_event_wait(hipEvent_t ev)
 
 hipError_t pep_stream_wait(pep_ctx *ctx)
 {
-    if (!ctx->wait_event && hipEventCreateWithFlags(&ctx->wait_event, pep_wait_event_flags()) != hipSuccess) return hipStreamSynchronize(ctx->stream);
+    if (!ctx->wait_event.ensure(pep_wait_event_flags())) return hipStreamSynchronize(ctx->stream);
     const hipError_t r = hipEventRecord(ctx->wait_event, ctx->stream);
     if (r != hipSuccess) return hipStreamSynchronize(ctx->stream);
     return pep_event_wait(ctx->wait_event);
@@ -422,6 +408,17 @@ int download_aa(pep_ctx *ctx, const SeqSet &s, uint8_t *codes, uint64_t cap, uin
     return PEP_OK;
 }
 
+// the text of a device-free table check (pep_*_check) into the caller's char[msg_cap], cut to fit; passes `rc` on
+int message_out(int rc, const std::string &text, char *msg, uint64_t msg_cap)
+{
+    if (msg && msg_cap) {
+        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
+        memcpy(msg, text.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
+}
+
 }  // namespace
 
 // entry points for other translation units (K9's gapped verification drives the alignment engine on its own sequence sets)
@@ -507,7 +504,7 @@ int pep_ctx_create(int device, pep_ctx **out)
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     pep_default_params(&ctx->params);
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return PEP_ERR_HIP; }
-    if (hipStreamCreate(&ctx->stream) != hipSuccess) { delete ctx; return PEP_ERR_HIP; }
+    if (hipStreamCreate(&ctx->stream.s) != hipSuccess) { delete ctx; return PEP_ERR_HIP; }
     if (pin_reserve(ctx, ctx->pin_small, 16384) != PEP_OK) { *out = ctx; return PEP_ERR_HIP; }
     int rc = pep_selftest_dpp(ctx);
     if (rc != PEP_OK) { *out = ctx; return rc; }      // caller can read the message, then destroy
@@ -515,39 +512,21 @@ int pep_ctx_create(int device, pep_ctx **out)
     return PEP_OK;
 }
 
-void pep_ctx_destroy(pep_ctx *ctx)
+// a result that outlives the context (freeing it afterwards is allowed) takes its own copy of the staged table and forgets the context; then the members go
+pep_ctx::~pep_ctx()
 {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    for (auto &b : ctx->ws) dev_release(b);
-    for (int id = 0; id < TM_COUNT; ++id) { if (ctx->tm_a[id]) (void)hipEventDestroy(ctx->tm_a[id]); if (ctx->tm_b[id]) (void)hipEventDestroy(ctx->tm_b[id]); }
-    pep_drop_dev_result(ctx);
-    if (ctx->staged_result) {
-        // the result outlives the context (freeing it afterwards is allowed): it takes its own copy and forgets the context
-        pep_materialise_staged(ctx);
-    }
-    if (ctx->pin_small.p) (void)hipHostFree(ctx->pin_small.p);
-    if (ctx->pin_stage.p) (void)hipHostFree(ctx->pin_stage.p);
-    if (ctx->pin_k1.p) (void)hipHostFree(ctx->pin_k1.p);
-    if (ctx->pin_k1q.p) (void)hipHostFree(ctx->pin_k1q.p);
-    if (ctx->pin_labels.p) (void)hipHostFree(ctx->pin_labels.p);
-    if (ctx->pin_nt_match.p) (void)hipHostFree(ctx->pin_nt_match.p);
-    if (ctx->k1_event) (void)hipEventDestroy(ctx->k1_event);
-    if (ctx->k1q_event) (void)hipEventDestroy(ctx->k1q_event);
-    if (ctx->k1_t0) (void)hipEventDestroy(ctx->k1_t0);
-    if (ctx->k1_t1) (void)hipEventDestroy(ctx->k1_t1);
-    if (ctx->wait_event) (void)hipEventDestroy(ctx->wait_event);
-    if (ctx->up_event) (void)hipEventDestroy(ctx->up_event);
-    if (ctx->pin_down.p) (void)hipHostFree(ctx->pin_down.p);
-    if (ctx->pin_up.p) (void)hipHostFree(ctx->pin_up.p);
-    if (ctx->pin_ms.p) (void)hipHostFree(ctx->pin_ms.p);
-    DevBuf *bufs[] = {&ctx->sub_lds, &ctx->d_params, &ctx->scan_state[0].buf, &ctx->scan_state[1].buf, &ctx->fused_state[0].buf, &ctx->fused_state[1].buf, &ctx->fused_state[2].buf, &ctx->fused_state[3].buf, &ctx->d_min_score, &ctx->d_trace_mode, &ctx->d_trace_defer, &ctx->d_k1_base, &ctx->d_k1_seg, &ctx->d_k1_long, &ctx->d_k1_spec, &ctx->d_k1_tiles, &ctx->d_t_class, &ctx->d_t_subject, &ctx->d_nt_match, &ctx->q_nt.nt, &ctx->q_nt.off, &ctx->r_nt.nt, &ctx->r_nt.off,
-                      &ctx->q.res, &ctx->q.off, &ctx->q.len, &ctx->t.res, &ctx->t.off, &ctx->t.len, &ctx->q.blk2seq, &ctx->t.blk2seq,
-                      &ctx->sort_state, &ctx->sort_hist, &ctx->d_set, &ctx->d_zero, &ctx->d_k1_desc_q, &ctx->d_k1_desc_t, &ctx->d_self_delta, &ctx->d_self_t, &ctx->d_mail_copy,
-                      &ctx->nucl_q.d_off, &ctx->nucl_q.d_len, &ctx->nucl_q.d_desc, &ctx->nucl_t.d_off, &ctx->nucl_t.d_len, &ctx->nucl_t.d_desc, &ctx->nucl_t.d_first, &ctx->k16_tri, &ctx->k16_leader};
-    for (DevBuf *b : bufs) dev_release(*b);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    (void)hipSetDevice(device);
+    pep_drop_dev_result(this);
+    pep_materialise_staged(this);
+}
+
+void pep_ctx_destroy(pep_ctx *ctx) { delete ctx; }
+
+int pep_live_resources(uint64_t *device_bytes, uint64_t *pinned_bytes, uint32_t *events)
+{
+    if (!device_bytes || !pinned_bytes || !events) return PEP_ERR_ARG;
+    *device_bytes = pep_live.device_bytes; *pinned_bytes = pep_live.pinned_bytes; *events = pep_live.events;
+    return PEP_OK;
 }
 
 const char *pep_last_error(const pep_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -602,20 +581,18 @@ int pep_translate(pep_ctx *ctx, int force)
 {
     if (!ctx) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    // (the two timing events live as long as the context)
-    if (!ctx->k1_t0 && (hipEventCreate(&ctx->k1_t0) != hipSuccess || hipEventCreate(&ctx->k1_t1) != hipSuccess)) { ctx->k1_t0 = ctx->k1_t1 = nullptr; }
     // both sides are queued first (reference, then queries); the reference's summary is taken while the query kernels run
     ctx->resid_from_nucl = false;           // (pep_use_nt_as_residues left q_ready / t_ready false: K1 runs again)
     const bool do_q = ctx->q_from_nt && (force || !ctx->q_ready), do_t = ctx->t_from_nt && (force || !ctx->t_ready);
     if (!do_q && !do_t) return PEP_OK;       // nothing to translate (pep_search calls this every time): no events, no waiting
-    const bool timed = ctx->timing_level >= 2 && ctx->k1_t0;
+    const bool timed = ctx->timing_level >= 2 && ctx->k1_t0.ensure() && ctx->k1_t1.ensure();      // (the two timing events: made when a timed translation first needs them, kept as long as the context)
     if (timed) (void)hipEventRecord(ctx->k1_t0, ctx->stream);
     if (do_t) PEP_TRY(pep_k1_ref(ctx, ctx->t_frames, ctx->t_gtable, 1));
     if (do_q) PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 1));
     if (do_t) { PEP_TRY(pep_k1_ref(ctx, ctx->t_frames, ctx->t_gtable, 2)); ctx->t_ready = true; }
     if (do_q) { PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 2)); ctx->q_ready = true; }
     float ms = 0.f;
-    if (timed && ctx->k1_t1 && hipEventRecord(ctx->k1_t1, ctx->stream) == hipSuccess && pep_event_wait(ctx->k1_t1) == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->k1_t0, ctx->k1_t1);
+    if (timed && hipEventRecord(ctx->k1_t1, ctx->stream) == hipSuccess && pep_event_wait(ctx->k1_t1) == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->k1_t0, ctx->k1_t1);
     ctx->stats.ms_k1 = ms;
     return PEP_OK;
 }
@@ -1077,12 +1054,7 @@ int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t 
 {
     std::string text;
     const int rc = pep_k7_codons_check(n, hits, cigar, n_cigar, mode, aa_of_word, sub, q_off, n_q, r_off, n_r, text);
-    if (msg && msg_cap) {
-        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
-        memcpy(msg, text.data(), k);
-        msg[k] = 0;
-    }
-    return rc;
+    return message_out(rc, text, msg, msg_cap);
 }
 
 int pep_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *a, const uint32_t *b, uint32_t *label)
@@ -1164,12 +1136,7 @@ int pep_group_verdicts_check(const uint8_t *packed, const uint64_t *row_off, con
 {
     std::string text;
     const int rc = pep_k16_check(packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_genome, grp_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, text);
-    if (msg && msg_cap) {
-        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
-        memcpy(msg, text.data(), k);
-        msg[k] = 0;
-    }
-    return rc;
+    return message_out(rc, text, msg, msg_cap);
 }
 
 int pep_group_verdicts(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/peppan_hip.h"
 
@@ -26,11 +28,28 @@
         if (_rc != PEP_OK) return _rc; \
     } while (0)
 
-// grow-only device buffer
+// ---- ownership.  Every device buffer, pinned buffer, event and stream of the library is held by one of the four types below and released by its destructor:
+// a new one is a member (of pep_ctx, of a struct inside it) or a local and needs nothing else.  They are the only places that free a HIP resource, and the
+// only ones that count what is alive (process-wide: pep_live_resources).  Move-only: a declared move constructor deletes both copies.
+struct PepLive { std::atomic<uint64_t> device_bytes{0}, pinned_bytes{0}; std::atomic<uint32_t> events{0}; };
+inline PepLive pep_live;
+
+// grow-only device buffer (dev_reserve)
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~DevBuf() { release(); }
+    void release() { if (p) { (void)hipFree(p); pep_live.device_bytes -= cap; } p = nullptr; cap = 0; }
+    hipError_t alloc(size_t bytes)          // exactly `bytes`, in place of what it held
+    {
+        release();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) { cap = bytes; pep_live.device_bytes += bytes; } else p = nullptr;
+        return e;
+    }
 };
 
 // packed sequence set on the device.  Residues of sequence i live at res[off[i] .. off[i]+len[i]);
@@ -68,7 +87,42 @@ struct NtSet {
 struct PinBuf {
     uint8_t *p = nullptr;
     size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(PinBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~PinBuf() { release(); }
+    void release() { if (p) { (void)hipHostFree(p); pep_live.pinned_bytes -= cap; } p = nullptr; cap = 0; }
+    hipError_t alloc(size_t bytes)
+    {
+        release();
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), bytes, hipHostMallocDefault);
+        if (e == hipSuccess) { cap = bytes; pep_live.pinned_bytes += bytes; } else p = nullptr;
+        return e;
+    }
 };
+
+// an event, created when it is first needed
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) { (void)hipEventDestroy(e); --pep_live.events; } }
+    // false: the runtime gave none (every caller has its own way on without one)
+    bool ensure(unsigned flags = hipEventDefault) { if (!e && hipEventCreateWithFlags(&e, flags) == hipSuccess) ++pep_live.events; return e != nullptr; }
+    operator hipEvent_t() const { return e; }
+};
+
+// the context's stream: declared in front of every buffer and event, so the last of them to go
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+static_assert(!std::is_copy_constructible<DevBuf>::value && std::is_nothrow_move_constructible<DevBuf>::value && sizeof(DevBuf) == 16, "DevBuf: move-only, two words");
+static_assert(!std::is_copy_constructible<PinBuf>::value && std::is_nothrow_move_constructible<PinBuf>::value, "PinBuf: move-only");
+static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_constructible<Event>::value, "Event: move-only");
 
 struct pep_result;
 
@@ -83,9 +137,11 @@ struct PackDesc {
 // ... and of a packed nucleotide sequence (pep_use_nt_as_residues: NuclSide::d_desc): the sequence and whether it is its reverse complement
 struct NuclDesc { uint32_t seq, rev; };
 
+enum PepTimer { TM_SEED = 0, TM_TOTAL, TM_SW, TM_SW_TRACE, TM_TRACE, TM_MATCH0, TM_MATCH1, TM_MATCH2, TM_MATCH3, TM_COUNT };
+
 struct pep_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;                          // declared before every buffer and event: destroyed after them
     PinBuf pin_small;                       // 16 KiB: counters read back between kernels
     size_t pin_small_used = 0;
     struct PendingRead { void *dst; size_t off, n; } pending[32];
@@ -98,17 +154,17 @@ struct pep_ctx {
     const uint32_t *self_first = nullptr;   // what pep_self_map found applicable to the current sets: d_self_t (K1's) or the nucleotide tool's nucl_t.d_first; its entries; may a target be longer than its query
     uint32_t self_first_cnt = 0;
     int self_exact_len = 0;
-    hipEvent_t k1_event = nullptr;          // the point of the stream where the reference side's downloads have arrived
-    hipEvent_t k1q_event = nullptr;         // ... and the query side's
+    Event k1_event;                         // the point of the stream where the reference side's downloads have arrived
+    Event k1q_event;                        // ... and the query side's
     bool k1q_event_set = false;
     bool k1_t_deferred = false;             // pep_search: the reference side's K1 is queued, its summary not taken yet
-    hipEvent_t wait_event = nullptr;        // pep_stream_wait: marks the point of the stream the host is waiting for
-    hipEvent_t k1_t0 = nullptr, k1_t1 = nullptr;   // pep_translate's timing pair (created once)
+    Event wait_event;                       // pep_stream_wait: marks the point of the stream the host is waiting for
+    Event k1_t0, k1_t1;                     // pep_translate's timing pair (created once)
     uint32_t k1_desc_cap = 0;               // descriptor slots of the reference side's last K1 (the summary sits behind them in pin_k1)
     bool t_tables_lazy = false, q_tables_lazy = false;   // a side's host tables (meta records, h_off, h_len) have not been built from its pinned descriptors yet (pep_k1_host_tables)
     PinBuf pin_up;                          // grow-only: staging area of uploads out of pageable memory (pep_h2d)
     size_t pin_up_used = 0;
-    hipEvent_t up_event = nullptr;          // the point of the stream where the last upload out of pin_up has left it
+    Event up_event;                         // the point of the stream where the last upload out of pin_up has left it
     bool up_event_set = false;
     PinBuf pin_down;                        // grow-only: staging area of downloads into pageable memory (pep_d2h_queue / pep_d2h_finish)
     size_t pin_down_used = 0;
@@ -165,8 +221,8 @@ struct pep_ctx {
     bool d_params_valid = false;
     // phase timers: events recorded on the stream, read once after the search's final synchronisation (waiting for an end event in
     // the middle of a search costs a host round trip with the GPU idle, and lets nothing be queued behind a running SW pass)
-    hipEvent_t tm_a[12] = {}, tm_b[12] = {};
-    int tm_state[12] = {};                   // 0 idle, 1 begun, 2 ended (waiting to be read)
+    Event tm_a[TM_COUNT], tm_b[TM_COUNT];
+    int tm_state[TM_COUNT] = {};                // 0 idle, 1 begun, 2 ended (waiting to be read)
     int timing_level = 0;                    // pep_set_timing: 0 no phase timers, 1 the score pass only, 2 all of them
     PinBuf pin_labels;                       // grow-only: K10's labels on their way to the caller
     uint64_t trace_swept = 0;               // pairs the last traceback pass swept (the rest were settled by the gapless shortcut)
@@ -201,6 +257,7 @@ struct pep_ctx {
     DevBuf k16_tri, k16_leader;              // grow-only: packed triangles and leaders of the newest pep_group_verdicts (read by pep_verdict_detail_copy)
     // stats of the last search
     pep_stats stats;
+    ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
 };
 
 struct pep_result {
@@ -218,18 +275,17 @@ struct pep_result {
 };
 
 // HIP-event stopwatch on one stream (the kernel times bench.py reports are taken with it, inside the library,
-// on the stream the kernels are launched on); destroys its events on every exit path
+// on the stream the kernels are launched on); its events go with it on every exit path
 hipError_t pep_event_wait(hipEvent_t ev);      // polls before it sleeps (capi.hip)
 unsigned pep_wait_event_flags();               // flags of an event that is only ever waited for (blocking when PEPPAN_HIP_SPIN_US=0)
 
 struct EventTimer {
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     hipStream_t st;
     explicit EventTimer(hipStream_t s) : st(s)
     {
-        if (hipEventCreate(&a) != hipSuccess) a = nullptr;
-        if (hipEventCreate(&b) != hipSuccess) b = nullptr;
-        if (a) (void)hipEventRecord(a, st);
+        b.ensure();
+        if (a.ensure()) (void)hipEventRecord(a, st);
     }
     float stop()                      // records the end event, waits for it, returns milliseconds (0 on failure)
     {
@@ -237,16 +293,8 @@ struct EventTimer {
         if (a && b && hipEventRecord(b, st) == hipSuccess && pep_event_wait(b) == hipSuccess) (void)hipEventElapsedTime(&ms, a, b);
         return ms;
     }
-    ~EventTimer()
-    {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    EventTimer(const EventTimer &) = delete;
-    EventTimer &operator=(const EventTimer &) = delete;
 };
 
-enum PepTimer { TM_SEED = 0, TM_TOTAL, TM_SW, TM_SW_TRACE, TM_TRACE, TM_MATCH0, TM_MATCH1, TM_MATCH2, TM_MATCH3, TM_COUNT };
 void pep_timer_begin(pep_ctx *ctx, int id);
 void pep_timer_end(pep_ctx *ctx, int id);
 void pep_timers_resolve(pep_ctx *ctx);     // after a stream synchronisation: elapsed times -> ctx->stats.ms_*
@@ -275,7 +323,7 @@ void pep_d2h_finish(pep_ctx *ctx);
 void pep_materialise_staged(pep_ctx *ctx);
 void pep_drop_dev_result(pep_ctx *ctx);
 int dev_reserve(pep_ctx *ctx, DevBuf &b, size_t bytes);
-void dev_release(DevBuf &b);
+inline void dev_release(DevBuf &b) { b.release(); }      // the explicit early release
 
 // Layout of pep_ctx::d_zero: every small counter block a search needs starts from zero, and one fill at the start of the search clears
 // them all (each used to be a fill of its own in front of its kernel: eleven tiny launches per search).  A stage that runs without the

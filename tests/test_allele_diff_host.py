@@ -17,9 +17,9 @@ def test_library_exports_allele_diff_and_abi_17():
     lib = N.load_library()
     assert hasattr(lib, 'pep_allele_diff')
     assert 'pep_allele_diff' in N.EXPORTS
-    assert lib.pep_version() == 17 and N.ABI_VERSION == 17
+    assert lib.pep_version() == 18 and N.ABI_VERSION == 18          # (17 when K15 arrived; 18 gained pep_live_resources)
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'peppan_hip.h')).read()
-    assert '#define PEP_ABI_VERSION 17' in hdr and 'PEPPAN.py:296-316, 332-333' in hdr
+    assert '#define PEP_ABI_VERSION 18' in hdr and 'PEPPAN.py:296-316, 332-333' in hdr
 
 
 def test_fixture_covers_the_cases_the_feature_is_pinned_by():
