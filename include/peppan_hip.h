@@ -33,6 +33,7 @@
  *   pep_alleles             aligned-allele strings + base-5 packing of iter_map_bsn   PEPPAN.py:812-835, 846-848
  *   pep_allele_diff         numba compare_seq / compare_seqX of filt_per_group over the rows of the .seq store   PEPPAN.py:296-316, 332-333
  *   pep_group_verdicts      checkDiv over the edge rows, the distances test and the leader grouping of filt_per_group   PEPPAN.py:335-344, 352-366, 371-392
+ *   pep_gene_ingroups       determineGroup inside initializing2: the in-group rows of every gene of the .tab store and the gene's score   PEPPAN.py:1041-1056, 1058-1076
  *   pep_store_mat_member / pep_store_seq_member   the 1000-group members of the .mat / .seq stores get_map_bsn writes (host C++:
  *                           the .npy pickle stream emitted from the numeric hit table)   PEPPAN.py:950-966
  *   pep_table_from_hits / pep_cols_fix_end / pep_cols_order / pep_cols_gather   RunBlast.run's numeric chain between a search and the caller (host C++:
@@ -51,7 +52,7 @@ extern "C" {
 
 /* 17 gained, additively, the K16 entry points: pep_group_verdicts, pep_group_verdicts_check, pep_verdict_detail_size, pep_verdict_detail_copy,
  * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check.
- * 18 gained pep_live_resources. */
+ * 18 gained pep_live_resources; and, additively, the K17 entry points: pep_gene_ingroups, pep_gene_ingroups_check, pep_gene_ingroups_times. */
 #define PEP_ABI_VERSION 18
 
 #define PEP_OK 0
@@ -390,6 +391,30 @@ int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t 
 int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *tri, uint32_t *leader);
 void pep_verdict_result_free(pep_verdict_result *res);
 int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host);
+
+/* K17: in-group rows and gene scores of `initializing` - determineGroup (PEPPAN.py:1041-1056) as initializing2 calls it for every gene of the
+ * .tab store, and the gene's score (:1058-1076).  Gene g is rows [gene_off[g], gene_off[g+1]) of the three row tables, in the order of :1069:
+ * genome (column 1), iden (column 4 after the rescale of :1070, >= 0), score (column 2).  With thr = (min_iden - 0.02) * 10000 evaluated by the
+ * caller as the reference writes it, seed[j] = iden[j] >= thr and, for two rows i < j of one gene,
+ *   sc(i, j) = (1. - iden[j] / iden[i]) / den,  den = self_id for two rows of one genome, else column 2 of the table below for the two genomes
+ *                                                (gd_default[2] when the pair is not in it),
+ *   raw[j]   = seed[j] or there is an i < j with seed[i] and sc(i, j) < 1,
+ *   keep[j]  = raw[first row of the gene with genome[j]'s genome]       (:1054-1055),
+ *   gene_score[g] = sum of abs(score[j]) over the kept rows that are the first of their genome       (:1074).
+ * The reference's ordered walk with its early exit computes the same: only seeds ever act as sources and the flags only grow.  Every operation
+ * of sc is a single correctly rounded double operation, so keep equals numpy's bit for bit.  The table is pep_group_verdicts' own
+ * (peppan_amd.orthofilter.gd_table with allowed_sigma = nSigma).  All tables are checked on the host before anything is launched.
+ * PEP_ERR_ARG: gene_off not ascending from 0 to n_rows, a negative iden, a key with g1 > g2 or out of order, a value that is not finite or
+ * not > 0, self_id or thr not finite.  PEP_ERR_LIMIT: n_rows >= 2^32.  Empty batches and empty genes are legal; an empty gene scores 0.  On an
+ * error nothing is written and the context stays usable.  The work is quadratic in the rows of a gene in the worst case, as the reference's.
+ * pep_gene_ingroups_check runs the checks alone: no context, no device; the message goes to msg (msg_cap bytes, 0-terminated).
+ * pep_gene_ingroups_times: of the newest call, the kernel times in ms - pairs, finish - when pep_set_timing is 2 (else zeros), and the bytes
+ * the call sent to the host: n_rows + 8 * n_genes. */
+int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                      const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *keep, int64_t *gene_score);
+int pep_gene_ingroups_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                            const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, char *msg, uint64_t msg_cap);
+int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host);
 
 /* K14 and its two host passes: the consumer of the all-vs-all table (get_similar_pairs, PEPPAN.py:194-294).
  *

@@ -15,7 +15,7 @@ EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy
            'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
            'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
            'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
-           'pep_merge_hits', 'pep_rescore_nt', 'pep_rescore_codons', 'pep_rescore_codons_check', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
+           'pep_merge_hits', 'pep_rescore_nt', 'pep_rescore_codons', 'pep_rescore_codons_check', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_gene_ingroups', 'pep_gene_ingroups_check', 'pep_gene_ingroups_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
            'pep_similar_classify', 'pep_similar_scan', 'pep_pair_support', 'pep_similar_resolve', 'pep_fasta_keep', 'pep_fasta_scan', 'pep_fasta_records', 'pep_store_mat_member', 'pep_store_seq_member', 'pep_store_tab_members', 'pep_store_tab_archive', 'pep_deflate_literals', 'pep_deflate_fast', 'pep_crc32', 'pep_pack_member', 'pep_argsort_object_order',
            'pep_set_nt_match', 'pep_result_nt_match', 'pep_table_from_hits', 'pep_cols_fix_end', 'pep_cols_order', 'pep_cols_gather', 'pep_lex_order', 'pep_set_host_threads']
 
@@ -55,6 +55,9 @@ SUPPORT_ROW_DTYPE = np.dtype([('q_start', '<u4'), ('r_start', '<u4'), ('cigar_ru
 SUPPORT_NONE = -2 ** 31
 ROW_ORDINARY, ROW_CONFLICT, ROW_ABSORB_QUERY, ROW_ABSORB_REF = 0, 1, 2, 3
 EVENT_CONFLICT, EVENT_SUPPORT = 0, 1
+
+
+INGROUP_MAX_IDEN = (1 << 31) - 1         # column 4 of a gene's table travels as int32
 
 
 class SupportLimits(C.Structure):
@@ -335,6 +338,39 @@ def group_verdicts_check(packed, row_off, row_len, groups, genomes, inparalog, g
     rc = lib.pep_group_verdicts_check(*args, C.c_double(self_id), msg, C.c_uint64(len(msg)))
     if rc != 0:
         raise PepError('pep_group_verdicts_check failed (%d): %s' % (rc, msg.value.decode()))
+
+
+def _ingroup_tables(genome, iden, score, gene_off, gd):
+    """the arrays of one pep_gene_ingroups / pep_gene_ingroups_check call as the library's types -> (leading arguments, n_rows, n_genes, what keeps them alive)"""
+    genome = np.ascontiguousarray(genome, dtype=np.uint32).reshape(-1)
+    iden = np.ascontiguousarray(iden, dtype=np.int32).reshape(-1)
+    score = np.ascontiguousarray(score, dtype=np.int64).reshape(-1)
+    gene_off = np.ascontiguousarray(gene_off, dtype=np.uint64).reshape(-1)
+    if not (len(genome) == len(iden) == len(score)):
+        raise ValueError('gene_ingroups: genome, iden and score hold one entry per row')
+    if len(gene_off) < 1:
+        raise ValueError('gene_ingroups: gene_off needs one entry more than there are genes')
+    keys, vals, default = gd[:3]
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    vals = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1, 3)
+    default = np.ascontiguousarray(default, dtype=np.float64).reshape(3)
+    if len(keys) != len(vals):
+        raise ValueError('gene_ingroups: one row of values per key')
+    n_rows, n_genes = len(genome), len(gene_off) - 1
+    keep = [a if len(a) else np.zeros(1, a.dtype) for a in (genome, iden, score, gene_off, keys, vals)] + [default]
+    g, i, s, o, kk, vv, dd = keep
+    args = [_ptr(g), _ptr(i), _ptr(s), C.c_uint64(n_rows), C.c_uint32(n_genes), _ptr(o), _ptr(kk), _ptr(vv), C.c_uint64(len(keys)), _ptr(dd)]
+    return args, n_rows, n_genes, keep
+
+
+def gene_ingroups_check(genome, iden, score, gene_off, gd, self_id, thr):
+    """the host checks of pep_gene_ingroups alone (no context, no device): PepError with the library's code and text, else None"""
+    lib = load_library()
+    args, _, _, keep = _ingroup_tables(genome, iden, score, gene_off, gd)
+    msg = C.create_string_buffer(512)
+    rc = lib.pep_gene_ingroups_check(*args, C.c_double(self_id), C.c_double(thr), msg, C.c_uint64(len(msg)))
+    if rc != 0:
+        raise PepError('pep_gene_ingroups_check failed (%d): %s' % (rc, msg.value.decode()))
 
 
 def codon_tables(table_id=11):
@@ -1329,6 +1365,24 @@ class Context(object):
     def group_verdicts_totals(self):
         """the same two figures summed over the library calls of the newest group_verdicts (one per part of a split batch)"""
         return self._verdict_stats[0].copy(), int(self._verdict_stats[1])
+
+    # ---- K17
+    def gene_ingroups(self, genome, iden, score, gene_off, gd, self_id, thr):
+        """determineGroup (PEPPAN.py:1041-1056) and the gene score of initializing2 (:1074) for many genes at once.  Gene g is rows
+        gene_off[g] .. gene_off[g+1] of genome / iden / score (columns 1, 4 after :1070, 2 of its table in the order of :1069); gd: (keys, vals,
+        default) as orthofilter.gd_table makes them with allowed_sigma = nSigma; thr = (min_iden - 0.02) * 10000.
+        -> (keep bool[n_rows], gene_score int64[n_genes])"""
+        args, n_rows, n_genes, keep_alive = _ingroup_tables(genome, iden, score, gene_off, gd)
+        keep = np.zeros(max(n_rows, 1), dtype=np.uint8)
+        gene_score = np.zeros(max(n_genes, 1), dtype=np.int64)
+        self._check(self._lib.pep_gene_ingroups(self._h, *args, C.c_double(self_id), C.c_double(thr), _ptr(keep), _ptr(gene_score)), 'pep_gene_ingroups')
+        return keep[:n_rows].astype(bool), gene_score[:n_genes]
+
+    def gene_ingroups_times(self):
+        """of the newest pep_gene_ingroups: (float64[2] kernel times in ms - pairs, finish - when set_timing(2) is on, else zeros; bytes the call sent to the host)"""
+        ms, moved = (C.c_double * 2)(), C.c_uint64()
+        self._check(self._lib.pep_gene_ingroups_times(self._h, ms, C.byref(moved)), 'pep_gene_ingroups_times')
+        return np.array(list(ms)), int(moved.value)
 
     # ---- K13
     def sha1(self, seqs):

@@ -1173,6 +1173,32 @@ int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_t
     return PEP_OK;
 }
 
+int pep_gene_ingroups_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                            const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, char *msg, uint64_t msg_cap)
+{
+    std::string text;
+    const int rc = pep_k17_check(genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, text);
+    return message_out(rc, text, msg, msg_cap);
+}
+
+int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                      const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *keep, int64_t *gene_score)
+{
+    if (!ctx) return PEP_ERR_ARG;
+    if ((n_rows && !keep) || (n_genes && !gene_score)) return pep_fail(ctx, PEP_ERR_ARG, "pep_gene_ingroups: null table");
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return pep_k17_gene_ingroups(ctx, genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, keep, gene_score);
+}
+
+int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host)
+{
+    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
+    ms[0] = ctx->k17_ms[0];
+    ms[1] = ctx->k17_ms[1];
+    *bytes_to_host = ctx->k17_bytes_to_host;
+    return PEP_OK;
+}
+
 int pep_sha1(pep_ctx *ctx, const uint8_t *bytes, const uint64_t *off, uint32_t n, uint8_t *digest)
 {
     if (!ctx || (n && (!off || !digest))) return PEP_ERR_ARG;

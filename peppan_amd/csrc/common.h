@@ -255,6 +255,9 @@ struct pep_ctx {
     uint64_t k16_bytes_to_host = 0;          // ... and what it and the detail copies of its result sent to the host
     uint64_t k16_serial = 0;                 // counts pep_group_verdicts calls: a pep_verdict_result is live while its serial is the newest
     DevBuf k16_tri, k16_leader;              // grow-only: packed triangles and leaders of the newest pep_group_verdicts (read by pep_verdict_detail_copy)
+    double k17_ms[2] = {0., 0.};             // the newest pep_gene_ingroups: kernel times (pairs, finish) when pep_set_timing is 2 (ingroup.hip)
+    uint64_t k17_bytes_to_host = 0;          // ... and what it sent to the host
+    DevBuf k17[11];                          // grow-only: its tables, work list and outputs (the slots: ingroup.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
@@ -416,6 +419,12 @@ int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t
 int pep_k16_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs);
 int pep_k16_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uint32_t *h_leader);
 void pep_k16_result_free(pep_verdict_result *res);
+// ---- ingroup.hip (K17)
+int pep_k17_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off, const uint64_t *gd_key,
+                  const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, std::string &msg);      // every table check, no device
+int pep_k17_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                          const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *h_keep,
+                          int64_t *h_gene_score);
 // ---- dedup.hip (K13)
 int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest);
 int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep);

@@ -14,11 +14,12 @@
 // Every float decision is a chain of single correctly rounded double operations (__ddiv_rn / __dmul_rn: nothing to contract); the only
 // transcendental of the reference, exp, depends on the genome pair alone and arrives in a host-made table (gd0, denX, den) sorted by
 // g1 << 32 | g2, looked up by binary search.  Same-genome pairs use gd0 = fmax(self_id, 2 / aln) for all three.
-// The checks of the row and group tables, their layout and the device prologue up to allele_planes are K15's (grouptable.h); here: the gd table,
-// the grp_inparalog check, the edge-pair list and the 24-byte group record of the three kernels.
+// The checks of the row and group tables, their layout and the device prologue up to allele_planes are K15's (grouptable.h); here: the same-genome
+// rule of the gd table (the table, its search and its check: gdtable.h), the grp_inparalog check, the edge-pair list and the 24-byte group record of the three kernels.
 #include "common.h"
 #include "allelediff_tile.h"
 #include "grouptable.h"
+#include "gdtable.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -42,13 +43,6 @@ struct VGroup {                     // a GroupRec as the three kernels here read
     uint32_t n, words;
 };
 struct EdgePair { uint32_t g, a, b; };      // rows a, b (positions inside group g)
-struct GdTable {
-    const uint64_t *key;            // [n] sorted
-    const double *val;              // [n + 1][3]: gd0, denX, den; row n = the default
-    uint64_t n;
-    double self_id;
-};
-
 __device__ __forceinline__ void k16_gd(const GdTable &T, uint32_t ga, uint32_t gb, double aln, double &gd0, double &denX, double &den)
 {
     if (ga == gb) {
@@ -56,13 +50,7 @@ __device__ __forceinline__ void k16_gd(const GdTable &T, uint32_t ga, uint32_t g
         denX = den = gd0;                               // gd0 * exp(0 * x) == gd0
         return;
     }
-    const uint64_t key = ga < gb ? ((uint64_t)ga << 32 | gb) : ((uint64_t)gb << 32 | ga);
-    uint64_t lo = 0, hi = T.n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (T.key[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    const uint64_t row = (lo < T.n && T.key[lo] == key) ? lo : T.n;
+    const uint64_t row = gd_row(T, ga, gb);
     gd0 = T.val[3 * row]; denX = T.val[3 * row + 1]; den = T.val[3 * row + 2];
 }
 
@@ -187,8 +175,6 @@ struct Layout : GroupLayout {
 
 const GroupSpec K16_SPEC{"pep_group_verdicts: ", "triangles", "tiles or edge pairs", 2};
 
-bool k16_good(double v) { return std::isfinite(v) && v > 0.; }
-
 // every check of the tables, on the host, before anything is launched; also lays the device buffers out (the row and group tables: grouptable.h)
 int k16_check(const GroupTables &T, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
               const double *gd_default, double self_id, Layout &L, std::string &msg)
@@ -197,16 +183,9 @@ int k16_check(const GroupTables &T, const uint32_t *h_grp_genome, const uint8_t 
     if (!T.row_off || (T.n_rows && !T.row_len) || (T.n_groups && (!T.grp_off || !h_inparalog)) || (n_gd && (!gd_key || !gd_val)) || !gd_default) return bad(PEP_ERR_ARG, "null table");
     if (T.n_groups && T.grp_off[T.n_groups] && (!T.grp_rows || !h_grp_genome)) return bad(PEP_ERR_ARG, "null table");
     if (T.n_rows && T.row_off[T.n_rows] && !T.packed) return bad(PEP_ERR_ARG, "null table");
-    if (!k16_good(self_id)) return bad(PEP_ERR_ARG, "self_id must be finite and > 0");
-    for (uint64_t i = 0; i < n_gd; ++i) {
-        if ((gd_key[i] >> 32) > (gd_key[i] & 0xFFFFFFFFull)) return bad(PEP_ERR_ARG, "gd_key " + std::to_string(i) + " has g1 > g2");
-        if (i && gd_key[i] <= gd_key[i - 1]) return bad(PEP_ERR_ARG, "gd_key must be strictly increasing (entry " + std::to_string(i) + ")");
-    }
-    for (uint64_t i = 0; i <= n_gd; ++i) {
-        const double *v = i < n_gd ? gd_val + 3 * i : gd_default;
-        if (!k16_good(v[0]) || !k16_good(v[1]) || !k16_good(v[2]))
-            return bad(PEP_ERR_ARG, (i < n_gd ? "gd_val row " + std::to_string(i) : std::string("gd_default")) + " must be finite and > 0 in all three columns");
-    }
+    if (!gd_good(self_id)) return bad(PEP_ERR_ARG, "self_id must be finite and > 0");
+    const std::string fault = gd_table_fault(gd_key, gd_val, n_gd, gd_default);
+    if (!fault.empty()) return bad(PEP_ERR_ARG, fault);
     L.gd.assign(gd_val, gd_val + 3 * n_gd);
     L.gd.insert(L.gd.end(), gd_default, gd_default + 3);
     std::vector<std::pair<uint32_t, uint32_t>> by_genome;
