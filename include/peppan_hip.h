@@ -325,7 +325,7 @@ int pep_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *contig, const int64_t 
 typedef struct {
     uint32_t contig;          /* index into nt_off */
     uint32_t q_start;         /* 1-based first query position of the alignment (column 6) */
-    uint32_t rs, re;          /* 1-based reference start / end (columns 8, 9); rs > re = reverse strand */
+    uint32_t rs, re;          /* 1-based reference start / end (columns 8, 9); rs >= re = reverse strand */
     uint32_t cigar_runs, group;
     uint64_t cigar_off;
 } pep_locus;

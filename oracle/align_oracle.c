@@ -976,7 +976,7 @@ int oracle_linclust(const uint8_t *res, const uint64_t *off, uint32_t n, int bas
 /* ------------------------------------------------------------------ aligned-allele strings of the genome mapping (K12)
  * restates the per-hit loop of iter_map_bsn (PEPPAN.py:812-835) and the base-5 packing (PEPPAN.py:846-848).
  * PINNED: tests check it against the `bsn` arrays the reference's own iter_map_bsn wrote (tests/golden/g14_mapbsn.json).
- * row:   contig, q_start (1-based), rs/re (1-based, rs > re = reverse strand), CIGAR runs len<<2|op (0=M 1=I 2=D) in nt.
+ * row:   contig, q_start (1-based), rs/re (1-based, rs >= re = reverse strand), CIGAR runs len<<2|op (0=M 1=I 2=D) in nt.
  * per row:  ms = the contig bases under the M columns ('-' for I columns, D columns skipped); reverse rows read the
  *           reverse complement (any letter outside ACGT complements to 'N', configure.py:152-154);
  *           in_frame = max over the three frames of the M columns counted in it (frame shifts: D -> f-n, I -> f+n mod 3);
@@ -1003,7 +1003,7 @@ int oracle_alleles(const uint8_t *nt, const uint64_t *nt_off, uint32_t n_contigs
             if (L->contig >= n_contigs) { free(codes); return -1; }
             const uint8_t *c = nt + nt_off[L->contig];
             const int64_t cl = (int64_t)(nt_off[L->contig + 1] - nt_off[L->contig]);
-            const int rev = L->rs > L->re;
+            const int rev = L->rs >= L->re;                 /* forward is `tab[8] < tab[9]` (PEPPAN.py:814): one contig base reads the reverse strand */
             int64_t span = 0, rcons = 0;
             for (uint32_t k = 0; k < L->cigar_runs; ++k) {
                 const uint32_t run = cigar[L->cigar_off + k];

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void k12_codes(uint64_t n, const pep_locus *__
     if (h >= n) return;
     const pep_locus L = rows[h];
     const uint8_t *c = nt + nt_off[L.contig];
-    const bool rev = L.rs > L.re;
+    const bool rev = L.rs >= L.re;                       // forward is `tab[8] < tab[9]` (PEPPAN.py:814): a row of one contig base reads the reverse strand
     uint8_t *out = codes + row_off[h];
     long long at = 0, fr0 = 0, fr1 = 0, fr2 = 0;
     int f = 0;

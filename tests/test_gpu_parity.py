@@ -1247,51 +1247,7 @@ def test_map_workers_write_the_same_stores(tmp_path, monkeypatch):
 
 
 
-def _random_loci(rng, n_groups, contig_len=20000, n_contigs=3):
-    """random K12 input: contigs with N runs and planted stops, groups of 1-3 rows with indels, both strands"""
-    from peppan_amd import _native as N
-    contigs = []
-    for c in range(n_contigs):
-        s = rng.choice(list(b'ACGT'), contig_len).astype(np.uint8)
-        for _ in range(6):
-            p = int(rng.integers(0, contig_len - 40)); s[p:p + int(rng.integers(1, 30))] = ord('N')
-        for p in rng.integers(0, contig_len - 3, 300):
-            s[p:p + 3] = list(rng.choice([b'TAA', b'TAG', b'TGA']))
-        contigs.append(s.tobytes())
-    rows, cigar, grp_off, grp_qlen = [], [], [0], []
-    for g in range(n_groups):
-        ql = int(rng.integers(60, 2500))
-        q_at = 1
-        for k in range(int(rng.choice([1, 1, 1, 2, 3]))):
-            if q_at > ql - 30:
-                break
-            qs = max(1, q_at - int(rng.integers(0, 20)) * (k > 0))
-            budget = ql - qs + 1
-            runs, q_used, r_used = [], 0, 0
-            while q_used < budget:
-                m = int(min(budget - q_used, rng.integers(1, 400)))
-                runs.append((m, 0)); q_used += m; r_used += m
-                if q_used >= budget or rng.random() < 0.3:
-                    break
-                op = int(rng.choice([1, 2])); n = int(rng.integers(1, 8))
-                if op == 1:
-                    n = min(n, budget - q_used)
-                    if n == 0:
-                        break
-                    q_used += n
-                else:
-                    r_used += n
-                runs.append((n, op))
-            if runs[-1][1] == 2:
-                r_used -= runs[-1][0]; runs.pop()
-            c = int(rng.integers(0, n_contigs))
-            lo = int(rng.integers(1, contig_len - r_used))
-            rs, re_ = (lo, lo + r_used - 1) if rng.random() < 0.5 else (lo + r_used - 1, lo)
-            rows.append((c, qs, rs, re_, len(runs), g, len(cigar)))
-            cigar += [(n << 2) | op for n, op in runs]
-            q_at = qs + q_used
-        grp_off.append(len(rows)); grp_qlen.append(ql)
-    return contigs, np.array(rows, dtype=N.LOCUS_DTYPE), np.array(cigar, dtype=np.uint32), np.array(grp_off, dtype=np.uint64), np.array(grp_qlen, dtype=np.uint32)
+from small_kernel_cases import random_loci as _random_loci  # noqa: E402  (the generator lives beside the cases that complement it)
 
 
 def test_k12_alleles_vs_oracle(ctx):
