@@ -11,13 +11,100 @@ LIB_PATH = os.path.join(_HERE, 'libpeppan_hip.so')
 ABI_VERSION = 18
 MAX_SEQ_LEN = (1 << 23) - 256          # PEP_MAX_SEQ_LEN: longest single sequence of a packed set
 ALLELE_DIFF_MAX_BYTES = 1 << 31        # PEP_ALLELE_DIFF_MAX_BYTES: output (and bit planes) of one pep_allele_diff call
-EXPORTS = ['pep_version', 'pep_device_count', 'pep_ctx_create', 'pep_ctx_destroy', 'pep_live_resources', 'pep_last_error', 'pep_default_params', 'pep_set_sensitivity',
-           'pep_min_score', 'pep_min_score_ka', 'pep_set_query_nt', 'pep_set_ref_nt', 'pep_set_query_aa', 'pep_set_ref_aa', 'pep_translate', 'pep_use_nt_as_residues',
-           'pep_query_count', 'pep_target_count', 'pep_get_query_meta', 'pep_get_target_meta', 'pep_get_query_aa',
-           'pep_get_target_aa', 'pep_set_target_groups', 'pep_set_result_mode', 'pep_set_timing', 'pep_set_grouping', 'pep_result_labels', 'pep_invalidate_translation', 'pep_search', 'pep_result_size', 'pep_result_copy', 'pep_result_data', 'pep_result_device', 'pep_result_stats', 'pep_components_of_result', 'pep_result_free',
-           'pep_merge_hits', 'pep_rescore_nt', 'pep_rescore_codons', 'pep_rescore_codons_check', 'pep_components', 'pep_components_of_hits', 'pep_linclust', 'pep_overlaps', 'pep_alleles', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_group_verdicts_check', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_verdict_result_free', 'pep_group_verdicts_times', 'pep_gene_ingroups', 'pep_gene_ingroups_check', 'pep_gene_ingroups_times', 'pep_ovl_filter', 'pep_known_order', 'pep_linear_merge', 'pep_sha1', 'pep_dedup',
-           'pep_similar_classify', 'pep_similar_scan', 'pep_pair_support', 'pep_similar_resolve', 'pep_fasta_keep', 'pep_fasta_scan', 'pep_fasta_records', 'pep_store_mat_member', 'pep_store_seq_member', 'pep_store_tab_members', 'pep_store_tab_archive', 'pep_deflate_literals', 'pep_deflate_fast', 'pep_crc32', 'pep_pack_member', 'pep_argsort_object_order',
-           'pep_set_nt_match', 'pep_result_nt_match', 'pep_table_from_hits', 'pep_cols_fix_end', 'pep_cols_order', 'pep_cols_gather', 'pep_lex_order', 'pep_set_host_threads']
+
+# The C signature of every function of include/peppan_hip.h, stated once: name -> (return type, parameter types in the header's order).  load_library() hands them
+# to ctypes, which then converts plain Python ints and floats to the parameter's width, returns the full width, and refuses an argument of the wrong kind or a call
+# with too few before the library is entered; tests/test_abi.py reads the header's prototypes and holds this table to them.
+I, I32, U32, I64, U64, F64 = C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_double
+P, S = C.c_void_p, C.c_char_p            # P: every pointer, handle and array parameter (the writable char *msg too); S: a const char * string
+SIGNATURES = {
+    'pep_version': (I,),
+    'pep_device_count': (I,),
+    'pep_ctx_create': (I, I, P),
+    'pep_ctx_destroy': (None, P),
+    'pep_live_resources': (I, P, P, P),
+    'pep_last_error': (S, P),
+    'pep_default_params': (None, P),
+    'pep_set_sensitivity': (I, P, I),
+    'pep_min_score': (I32, U32, F64, F64),
+    'pep_min_score_ka': (I32, U32, F64, F64, F64, F64),
+    'pep_set_query_nt': (I, P, P, P, U32, I),
+    'pep_set_ref_nt': (I, P, P, P, U32, I, I),
+    'pep_set_query_aa': (I, P, P, P, U32),
+    'pep_set_ref_aa': (I, P, P, P, U32),
+    'pep_translate': (I, P, I),
+    'pep_invalidate_translation': (I, P),
+    'pep_use_nt_as_residues': (I, P, I),
+    'pep_query_count': (I, P, P, P),
+    'pep_target_count': (I, P, P, P),
+    'pep_get_query_meta': (I, P, P, U32),
+    'pep_get_target_meta': (I, P, P, U32),
+    'pep_get_query_aa': (I, P, P, U64, P),
+    'pep_get_target_aa': (I, P, P, U64, P),
+    'pep_set_target_groups': (I, P, P, U32),
+    'pep_set_result_mode': (I, P, I),
+    'pep_set_timing': (I, P, I),
+    'pep_search': (I, P, P, P),
+    'pep_result_size': (I, P, P, P),
+    'pep_result_copy': (I, P, P, P),
+    'pep_result_data': (I, P, P, P),
+    'pep_result_device': (I, P, P, P),
+    'pep_result_stats': (I, P, P),
+    'pep_result_free': (None, P),
+    'pep_merge_hits': (I, U64, P, P, U64, I32, I32, P, P, P, P),
+    'pep_rescore_nt': (I, P, U64, P, P, U64, P),
+    'pep_rescore_codons': (I, P, U64, P, P, U64, I32, P, P, P),
+    'pep_rescore_codons_check': (I, U64, P, P, U64, I32, P, P, P, U64, P, U64, P, U64),
+    'pep_set_nt_match': (I, P, I),
+    'pep_result_nt_match': (I, P, P),
+    'pep_components': (I, P, U32, U64, P, P, P),
+    'pep_components_of_hits': (I, P, U32, U64, P, U32, P, U64, P),
+    'pep_set_grouping': (I, P, U32, U32, P, U64),
+    'pep_result_labels': (I, P, P, U32),
+    'pep_components_of_result': (I, P, P, U32, U32, P, U64, P),
+    'pep_linclust': (I, P, P, P, U32, I, I, I, F64, F64, P, P),
+    'pep_overlaps': (I, P, U64, P, P, P, P, F64, F64, P, U64, P),
+    'pep_alleles': (I, P, P, P, U32, U64, P, P, U64, U32, P, P, I, P, P, P, U64),
+    'pep_allele_diff': (I, P, P, P, P, U64, U32, P, P, P, P, P, U64),
+    'pep_allele_diff_times': (I, P, P, P, P),
+    'pep_group_verdicts': (I, P, P, P, P, U64, U32, P, P, P, P, P, P, U64, P, F64, P, P),
+    'pep_group_verdicts_check': (I, P, P, P, U64, U32, P, P, P, P, P, P, U64, P, F64, P, U64),
+    'pep_verdict_detail_size': (I, P, U32, P),
+    'pep_verdict_detail_copy': (I, P, U32, P, P),
+    'pep_verdict_result_free': (None, P),
+    'pep_group_verdicts_times': (I, P, P, P),
+    'pep_gene_ingroups': (I, P, P, P, P, U64, U32, P, P, P, U64, P, F64, F64, P, P),
+    'pep_gene_ingroups_check': (I, P, P, P, U64, U32, P, P, P, U64, P, F64, F64, P, U64),
+    'pep_gene_ingroups_times': (I, P, P, P),
+    'pep_similar_classify': (I, U64, P, P, P, P, P, P, P, P, P, P, P, F64, F64, P, P, P),
+    'pep_similar_scan': (I, U64, P, P, P, P, P, U64, P, P, P, P, P, P, P, P, P, P),
+    'pep_pair_support': (I, P, U64, P, P, U64, U64, P, P, P, P, P),
+    'pep_similar_resolve': (I, U64, P, P, P, P, P, P),
+    'pep_fasta_keep': (I, S, P, U64, P, P),
+    'pep_fasta_scan': (I, P, U64, P, P, P, U64, P, P),
+    'pep_fasta_records': (I, P, U64, P, P, P, P, P, U64, P, P),
+    'pep_sha1': (I, P, P, P, U32, P),
+    'pep_dedup': (I, P, U32, P, P, P),
+    'pep_ovl_filter': (I, U64, P, P, P, P, P, P, P, P, F64, F64),
+    'pep_known_order': (I, U64, P, P, P, P, P, P, P, P, P, U64, P, P, P, P, P, P, P),
+    'pep_linear_merge': (I, U64, P, P, P, P, P, P, P, P, P, P, P, F64, F64, P, U64, P, P, P, P, P, P, P, P, P, U64, P),
+    'pep_store_mat_member': (I64, P, P, I64, S, P, I64),
+    'pep_store_seq_member': (I64, P, P, I64, S, P, I64),
+    'pep_store_tab_members': (I64, P, I64, P, P, P, I64, U32, U32, I32, P, I64, P, P, P, P),
+    'pep_store_tab_archive': (I64, P, I64, P, P, P, I64, U32, U32, I32, P, I64),
+    'pep_table_from_hits': (I64, I32, U64, P, P, U64, P, P, P, P, P, P, P, P, P, P, F64, F64, F64, P, P, P),
+    'pep_cols_fix_end': (I64, U64, P, P, U64, P, F64, F64),
+    'pep_cols_order': (I, U64, P, P, P, P),
+    'pep_lex_order': (I, U64, I32, P, P),
+    'pep_cols_gather': (I, I32, P, P, P, U64, U64),
+    'pep_set_host_threads': (I, I),
+    'pep_deflate_literals': (I64, P, I64, P, I64),
+    'pep_deflate_fast': (I64, P, I64, P, I64),
+    'pep_crc32': (U32, P, I64, U32),
+    'pep_pack_member': (I64, P, I64, I32, P, I64, P),
+    'pep_argsort_object_order': (I, P, I64, P),
+}
+EXPORTS = list(SIGNATURES)
 
 
 class PepError(RuntimeError):
@@ -107,21 +194,11 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name, (restype, *argtypes) in SIGNATURES.items():
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
-    lib.pep_last_error.restype = C.c_char_p
-    lib.pep_last_error.argtypes = [C.c_void_p]
-    lib.pep_min_score.restype = C.c_int32
-    lib.pep_min_score.argtypes = [C.c_uint32, C.c_double, C.c_double]
-    lib.pep_min_score_ka.restype = C.c_int32
-    lib.pep_min_score_ka.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double]
-    lib.pep_ctx_destroy.argtypes = [C.c_void_p]
-    lib.pep_ctx_destroy.restype = None
-    lib.pep_result_free.argtypes = [C.c_void_p]
-    lib.pep_result_free.restype = None
-    lib.pep_verdict_result_free.argtypes = [C.c_void_p]
-    lib.pep_verdict_result_free.restype = None
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.pep_version() != ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch')
     _lib = lib
@@ -249,6 +326,24 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr_or_null(a):
+    """NULL for an array without entries, where the library asks for that"""
+    return _ptr(a) if len(a) else None
+
+
+def _some(a):
+    """`a`, or one zero element of its type when it has no entries, where the library is handed no null pointer"""
+    return a if len(a) else np.zeros(1, a.dtype)
+
+
+def _check_only(name, *args):
+    """one of the device-free pep_*_check functions, its message buffer behind `args`: PepError with the library's code and text, else None"""
+    msg = C.create_string_buffer(512)
+    rc = getattr(load_library(), name)(*args, msg, len(msg))
+    if rc != 0:
+        raise PepError('%s failed (%d): %s' % (name, rc, msg.value.decode()))
+
+
 def _rows_of_groups(packed, row_off, row_len, groups, n):
     """the row table cut down to the rows `groups` (index arrays of n[g] entries, all in range) use -> (packed, row_off, row_len, groups re-indexed)"""
     idx = np.concatenate(groups)
@@ -275,7 +370,7 @@ def _group_tables(packed, row_len, groups, per_group=()):
     n = np.array([len(g) for g in groups], dtype=np.int64)
     grp_off = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
     grp_rows = np.ascontiguousarray(np.concatenate(groups), dtype=np.uint32) if grp_off[-1] else np.zeros(0, np.uint32)
-    return [a if len(a) else np.zeros(1, a.dtype) for a in (packed, row_len, grp_off, grp_rows) + tuple(per_group)]
+    return [_some(a) for a in (packed, row_len, grp_off, grp_rows) + tuple(per_group)]
 
 
 def _plan_batch(who, noun, need, row_len, groups, out_budget):
@@ -315,8 +410,8 @@ def _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd):
         raise ValueError('group_verdicts: one row of values per key')
     pk, rl, grp_off, grp_rows, grp_genome, ip, kk, vv = keep = _group_tables(packed, row_len, groups, (grp_genome, inparalog, keys, vals))
     keep += [row_off, default]
-    args = [_ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off), _ptr(grp_rows), _ptr(grp_genome), _ptr(ip),
-            _ptr(kk), _ptr(vv), C.c_uint64(len(keys)), _ptr(default)]
+    args = [_ptr(pk), _ptr(row_off), _ptr(rl), len(row_len), len(groups), _ptr(grp_off), _ptr(grp_rows), _ptr(grp_genome), _ptr(ip),
+            _ptr(kk), _ptr(vv), len(keys), _ptr(default)]
     return args, keep
 
 
@@ -331,13 +426,9 @@ def _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog):
 
 def group_verdicts_check(packed, row_off, row_len, groups, genomes, inparalog, gd, self_id):
     """the host checks of pep_group_verdicts alone (no context, no device): PepError with the library's code and text, else None"""
-    lib = load_library()
     packed, row_off, row_len, groups, genomes, inparalog = _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog)
     args, keep = _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd)
-    msg = C.create_string_buffer(512)
-    rc = lib.pep_group_verdicts_check(*args, C.c_double(self_id), msg, C.c_uint64(len(msg)))
-    if rc != 0:
-        raise PepError('pep_group_verdicts_check failed (%d): %s' % (rc, msg.value.decode()))
+    _check_only('pep_group_verdicts_check', *args, self_id)
 
 
 def _ingroup_tables(genome, iden, score, gene_off, gd):
@@ -357,20 +448,16 @@ def _ingroup_tables(genome, iden, score, gene_off, gd):
     if len(keys) != len(vals):
         raise ValueError('gene_ingroups: one row of values per key')
     n_rows, n_genes = len(genome), len(gene_off) - 1
-    keep = [a if len(a) else np.zeros(1, a.dtype) for a in (genome, iden, score, gene_off, keys, vals)] + [default]
+    keep = [_some(a) for a in (genome, iden, score, gene_off, keys, vals)] + [default]
     g, i, s, o, kk, vv, dd = keep
-    args = [_ptr(g), _ptr(i), _ptr(s), C.c_uint64(n_rows), C.c_uint32(n_genes), _ptr(o), _ptr(kk), _ptr(vv), C.c_uint64(len(keys)), _ptr(dd)]
+    args = [_ptr(g), _ptr(i), _ptr(s), n_rows, n_genes, _ptr(o), _ptr(kk), _ptr(vv), len(keys), _ptr(dd)]
     return args, n_rows, n_genes, keep
 
 
 def gene_ingroups_check(genome, iden, score, gene_off, gd, self_id, thr):
     """the host checks of pep_gene_ingroups alone (no context, no device): PepError with the library's code and text, else None"""
-    lib = load_library()
     args, _, _, keep = _ingroup_tables(genome, iden, score, gene_off, gd)
-    msg = C.create_string_buffer(512)
-    rc = lib.pep_gene_ingroups_check(*args, C.c_double(self_id), C.c_double(thr), msg, C.c_uint64(len(msg)))
-    if rc != 0:
-        raise PepError('pep_gene_ingroups_check failed (%d): %s' % (rc, msg.value.decode()))
+    _check_only('pep_gene_ingroups_check', *args, self_id, thr)
 
 
 def codon_tables(table_id=11):
@@ -395,23 +482,18 @@ def _codon_args(nt_hits, cigar, mode, tables):
     """the leading arguments of pep_rescore_codons / pep_rescore_codons_check behind the context + what keeps them alive; tables: (aa_of_word, sub) or None"""
     nt_hits = np.ascontiguousarray(nt_hits, dtype=NT_HIT_DTYPE)
     cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
-    cg = cigar if len(cigar) else np.zeros(1, np.uint32)
-    hh = nt_hits if len(nt_hits) else np.zeros(1, NT_HIT_DTYPE)
+    hh, cg = _some(nt_hits), _some(cigar)
     aa, sub = (None, None) if tables is None else (None if t is None else np.ascontiguousarray(t, dtype=d) for t, d in zip(tables, (np.uint8, np.int8)))
-    args = [C.c_uint64(len(nt_hits)), _ptr(hh), _ptr(cg), C.c_uint64(len(cigar)), C.c_int32(int(mode)), None if aa is None else _ptr(aa), None if sub is None else _ptr(sub)]
+    args = [len(nt_hits), _ptr(hh), _ptr(cg), len(cigar), int(mode), None if aa is None else _ptr(aa), None if sub is None else _ptr(sub)]
     return args, [hh, cg, aa, sub]
 
 
 def rescore_codons_check(nt_hits, cigar, mode, q_off, r_off, table_id=11, tables='module'):
     """the host checks of pep_rescore_codons alone (no context, no device): PepError with the library's code and text, else None.  q_off / r_off:
     offsets [n + 1] of the two nucleotide sets; tables: (aa_of_word, sub) instead of the module's own for table_id (None, or a None entry: a NULL pointer)"""
-    lib = load_library()
     args, keep = _codon_args(nt_hits, cigar, mode, codon_tables(table_id) if isinstance(tables, str) else tables)
     q_off, r_off = np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(r_off, dtype=np.uint64)
-    msg = C.create_string_buffer(512)
-    rc = lib.pep_rescore_codons_check(*args, _ptr(q_off), C.c_uint64(len(q_off) - 1), _ptr(r_off), C.c_uint64(len(r_off) - 1), msg, C.c_uint64(len(msg)))
-    if rc != 0:
-        raise PepError('pep_rescore_codons_check failed (%d): %s' % (rc, msg.value.decode()))
+    _check_only('pep_rescore_codons_check', *args, _ptr(q_off), len(q_off) - 1, _ptr(r_off), len(r_off) - 1)
 
 
 def ovl_filter(q, r, qs, qe, ss, se, score, iden, coverage, delta):
@@ -421,7 +503,7 @@ def ovl_filter(q, r, qs, qe, ss, se, score, iden, coverage, delta):
     arrs = [np.ascontiguousarray(a, dtype=np.int64) for a in (q, r, qs, qe, ss, se)]
     score = np.ascontiguousarray(score, dtype=np.float64)
     assert iden.dtype == np.float64 and iden.flags['C_CONTIGUOUS']
-    rc_ = lib.pep_ovl_filter(C.c_uint64(n), *[_ptr(a) for a in arrs], _ptr(score), _ptr(iden), C.c_double(coverage), C.c_double(delta))
+    rc_ = lib.pep_ovl_filter(n, *[_ptr(a) for a in arrs], _ptr(score), _ptr(iden), coverage, delta)
     if rc_ != 0:
         raise PepError('pep_ovl_filter failed (%d)' % rc_)
 
@@ -448,7 +530,7 @@ def known_order(T, genes_of):
     cols = [i64(a) for a in (T.ss, T.se, T.qs, T.qe, T.ql)]
     score = np.ascontiguousarray(T.score, dtype=np.float64)
     order, known = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.float64)
-    rc_ = lib.pep_known_order(C.c_uint64(n), _ptr(ri), _ptr(r_code), _ptr(q_code), *([_ptr(c) for c in cols] + [_ptr(score), C.c_uint64(n_contigs), _ptr(g_off), _ptr(g1), _ptr(g2),
+    rc_ = lib.pep_known_order(n, _ptr(ri), _ptr(r_code), _ptr(q_code), *([_ptr(c) for c in cols] + [_ptr(score), n_contigs, _ptr(g_off), _ptr(g1), _ptr(g2),
                               _ptr(plus), _ptr(is_sorted), _ptr(order), _ptr(known)]))
     if rc_ != 0:
         raise PepError('pep_known_order failed (%d)' % rc_)
@@ -472,9 +554,9 @@ def linear_merge(q, r, iden, qs, qe, ss, se, score, ql, sl, rid, gap_dist, len_d
         ids_off = np.zeros(n + 2, dtype=np.uint64)
         ids = np.zeros(ids_cap, dtype=np.int64)
         n_keep, n_query, n_ids = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        rc_ = lib.pep_linear_merge(C.c_uint64(n), _ptr(q), _ptr(r), _ptr(iden), _ptr(qs), _ptr(qe), _ptr(ss), _ptr(se), _ptr(score), _ptr(ql), _ptr(sl),
-                                   _ptr(rid), C.c_double(gap_dist), C.c_double(len_diff), _ptr(keep), C.c_uint64(keep_cap), C.byref(n_keep), _ptr(q_off),
-                                   _ptr(asc), C.byref(n_query), _ptr(g_score), _ptr(g_iden), _ptr(g_span), _ptr(ids_off), _ptr(ids), C.c_uint64(ids_cap),
+        rc_ = lib.pep_linear_merge(n, _ptr(q), _ptr(r), _ptr(iden), _ptr(qs), _ptr(qe), _ptr(ss), _ptr(se), _ptr(score), _ptr(ql), _ptr(sl),
+                                   _ptr(rid), gap_dist, len_diff, _ptr(keep), keep_cap, C.byref(n_keep), _ptr(q_off),
+                                   _ptr(asc), C.byref(n_query), _ptr(g_score), _ptr(g_iden), _ptr(g_span), _ptr(ids_off), _ptr(ids), ids_cap,
                                    C.byref(n_ids))
         if rc_ != 0:
             raise PepError('pep_linear_merge failed (%d)' % rc_)
@@ -515,7 +597,6 @@ def store_mat_member(cols, row_off, score_is_int):
     """pep_store_mat_member: the complete .npy member (header + pickle stream) of one chunk of the .mat store (PEPPAN.py:959-966).
     cols: the 18 arrays of MatCols in field order (q and r as int64 names per row); row_off int64[n_groups + 1]."""
     lib = load_library()
-    lib.pep_store_mat_member.restype = C.c_int64
     keep = [np.ascontiguousarray(a, dtype=dt) for a, dt in zip(cols, (np.int64, np.int64, np.float64) + (np.int64,) * 7 + (np.float64, np.float64, np.int64, np.int64,
                                                                                                                        np.uint32, np.int64, np.int64, np.int64))]
     mc = MatCols(*[a.ctypes.data for a in keep], int(bool(score_is_int)), 0)
@@ -526,7 +607,7 @@ def store_mat_member(cols, row_off, score_is_int):
     cap = 256 + 64 * n_groups + 200 * n_rows + 12 * int(keep[16][row_off[0]:row_off[-1]].sum() if n_rows else 0)
     for _ in range(2):
         buf = np.empty(len(head) + cap, dtype=np.uint8)
-        need = lib.pep_store_mat_member(C.byref(mc), _ptr(row_off), C.c_int64(n_groups), C.c_char_p(_recon_module()), C.c_void_p(buf.ctypes.data + len(head)), C.c_int64(cap))
+        need = lib.pep_store_mat_member(C.byref(mc), _ptr(row_off), n_groups, _recon_module(), buf.ctypes.data + len(head), cap)
         if need < 0:
             raise PepError('pep_store_mat_member failed (%d)' % need)
         if need <= cap:
@@ -539,14 +620,13 @@ def store_mat_member(cols, row_off, score_is_int):
 def store_seq_member(packed, pack_off):
     """pep_store_seq_member: the complete .npy member of one chunk of the .seq store (PEPPAN.py:950-957): object array of uint8 arrays"""
     lib = load_library()
-    lib.pep_store_seq_member.restype = C.c_int64
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     pack_off = np.ascontiguousarray(pack_off, dtype=np.int64)
     n_groups = len(pack_off) - 1
     head = _npy_object_header(n_groups)
     cap = 256 + 64 * n_groups + (int(pack_off[-1] - pack_off[0]) if n_groups else 0)
     buf = np.empty(len(head) + cap, dtype=np.uint8)
-    need = lib.pep_store_seq_member(_ptr(packed), _ptr(pack_off), C.c_int64(n_groups), C.c_char_p(_recon_module()), C.c_void_p(buf.ctypes.data + len(head)), C.c_int64(cap))
+    need = lib.pep_store_seq_member(_ptr(packed), _ptr(pack_off), n_groups, _recon_module(), buf.ctypes.data + len(head), cap)
     if need < 0 or need > cap:
         raise PepError('pep_store_seq_member failed (%d)' % need)
     buf[:len(head)] = np.frombuffer(head, dtype=np.uint8)
@@ -556,11 +636,10 @@ def store_seq_member(packed, pack_off):
 def deflate_literals(data):
     """pep_deflate_literals: bytes -> raw DEFLATE stream (zlib.decompress(x, -15) gives them back), Huffman coding only"""
     lib = load_library()
-    lib.pep_deflate_literals.restype = C.c_int64
     src = np.frombuffer(data, dtype=np.uint8)
     cap = len(src) + len(src) // 64 + 512
     out = np.empty(cap, dtype=np.uint8)
-    n = lib.pep_deflate_literals(_ptr(src) if len(src) else None, C.c_int64(len(src)), _ptr(out), C.c_int64(cap))
+    n = lib.pep_deflate_literals(_ptr_or_null(src), len(src), _ptr(out), cap)
     if n < 0 or n > cap:
         raise PepError('pep_deflate_literals failed (%d)' % n)
     return out[:n].tobytes()
@@ -569,20 +648,18 @@ def deflate_literals(data):
 def crc32(data, crc=0):
     """pep_crc32: zlib.crc32 of a bytes-like object, by carry-less multiplication where the CPU has it"""
     lib = load_library()
-    lib.pep_crc32.restype = C.c_uint32
     src = np.frombuffer(data, dtype=np.uint8)
-    return int(lib.pep_crc32(_ptr(src) if len(src) else None, C.c_int64(len(src)), C.c_uint32(crc)))
+    return int(lib.pep_crc32(_ptr_or_null(src), len(src), crc))
 
 
 def pack_member(data, coder):
     """pep_pack_member: bytes -> (raw DEFLATE stream, crc32 of the bytes); coder 0 = literals only (deflate_literals), 1 = single-probe matcher (deflate_fast)"""
     lib = load_library()
-    lib.pep_pack_member.restype = C.c_int64
     src = np.frombuffer(data, dtype=np.uint8)
     cap = len(src) + len(src) // 8 + 1024
     out = np.empty(cap, dtype=np.uint8)
-    crc = C.c_uint32(0)
-    n = lib.pep_pack_member(_ptr(src) if len(src) else None, C.c_int64(len(src)), C.c_int32(coder), _ptr(out), C.c_int64(cap), C.byref(crc))
+    crc = C.c_uint32()
+    n = lib.pep_pack_member(_ptr_or_null(src), len(src), coder, _ptr(out), cap, C.byref(crc))
     if n < 0 or n > cap:
         raise PepError('pep_pack_member failed (%d)' % n)
     return out[:n].tobytes(), int(crc.value)
@@ -591,11 +668,10 @@ def pack_member(data, coder):
 def deflate_fast(data):
     """pep_deflate_fast: bytes -> raw DEFLATE stream (zlib.decompress(x, -15) gives them back): single-probe matcher + dynamic Huffman blocks"""
     lib = load_library()
-    lib.pep_deflate_fast.restype = C.c_int64
     src = np.frombuffer(data, dtype=np.uint8)
     cap = len(src) + len(src) // 8 + 1024
     out = np.empty(cap, dtype=np.uint8)
-    n = lib.pep_deflate_fast(_ptr(src) if len(src) else None, C.c_int64(len(src)), _ptr(out), C.c_int64(cap))
+    n = lib.pep_deflate_fast(_ptr_or_null(src), len(src), _ptr(out), cap)
     if n < 0 or n > cap:
         raise PepError('pep_deflate_fast failed (%d)' % n)
     return out[:n].tobytes()
@@ -630,7 +706,6 @@ def table_from_hits(tool, hits, cigar, q_len, r_len, min_id, min_cov, min_ratio,
     nucleotide search (t_seq / t_rev [, windows = (offset, home_lo, home_hi) per target], evalue per hit).  nt_match (uint32 per hit, Context.last_nt_match):
     identity and score come out rescored (reScore mode 1)"""
     lib = load_library()
-    lib.pep_table_from_hits.restype = C.c_int64
     n = len(hits)
     hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
     cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
@@ -649,8 +724,8 @@ def table_from_hits(tool, hits, cigar, q_len, r_len, min_id, min_cov, min_ratio,
             raise ValueError('table_from_hits: one nt_match count per hit')
     p = lambda a: None if a is None else _ptr(a)
     hc = HitCols.over(cols)
-    m = lib.pep_table_from_hits(C.c_int32(tool), C.c_uint64(n), p(hits), p(cigar), C.c_uint64(len(cigar)), p(qm), p(tm), p(q_len), p(r_len), p(t_seq), p(t_rev),
-                                p(w[0]), p(w[1]), p(w[2]), p(evalue), C.c_double(min_id), C.c_double(min_cov), C.c_double(min_ratio), C.byref(hc), _ptr(arena), p(nt_match) if n else None)
+    m = lib.pep_table_from_hits(tool, n, p(hits), p(cigar), len(cigar), p(qm), p(tm), p(q_len), p(r_len), p(t_seq), p(t_rev),
+                                p(w[0]), p(w[1]), p(w[2]), p(evalue), min_id, min_cov, min_ratio, C.byref(hc), _ptr(arena), p(nt_match) if n else None)
     if m < 0:
         raise PepError('pep_table_from_hits failed (%d)' % m)
     return {f: a[:m] for f, a in cols.items()}, arena[:len(cigar)]
@@ -659,12 +734,11 @@ def table_from_hits(tool, hits, cigar, q_len, r_len, min_id, min_cov, min_ratio,
 def cols_fix_end(cols, arena, se_lim, ee_lim):
     """pep_cols_fix_end over {field: column} in place -> the rows' private arena (c_off rewritten)"""
     lib = load_library()
-    lib.pep_cols_fix_end.restype = C.c_int64
     n = len(cols['qs'])
     out = np.empty(max(int(cols['c_runs'].sum()) if n else 0, 1), dtype=np.uint32)
     hc = HitCols.over(cols)
     arena = np.ascontiguousarray(arena, dtype=np.uint32)
-    rc_ = lib.pep_cols_fix_end(C.c_uint64(n), C.byref(hc), _ptr(arena) if len(arena) else None, C.c_uint64(len(arena)), _ptr(out), C.c_double(se_lim), C.c_double(ee_lim))
+    rc_ = lib.pep_cols_fix_end(n, C.byref(hc), _ptr_or_null(arena), len(arena), _ptr(out), se_lim, ee_lim)
     if rc_ < 0:
         raise IndexError('fix_end: a row without CIGAR runs cannot be extended (the reference fails on cigar[0] here, uberBlast.py:468), or runs outside the arena')
     return out[:int(cols['c_runs'].sum()) if n else 0]
@@ -679,7 +753,7 @@ def lex_order(keys):
         return np.lexsort(keys)
     order = np.empty(n, dtype=np.int64)
     ptrs = (C.c_void_p * len(keys))(*[k.ctypes.data for k in keys])
-    rc_ = lib.pep_lex_order(C.c_uint64(n), C.c_int32(len(keys)), ptrs, _ptr(order))
+    rc_ = lib.pep_lex_order(n, len(keys), ptrs, _ptr(order))
     if rc_ != 0:
         return np.lexsort(keys)
     return order
@@ -687,7 +761,7 @@ def lex_order(keys):
 
 def set_host_threads(n):
     """pep_set_host_threads: the most threads a pass of the host chain may use (0: the default again); returns the value before"""
-    return int(load_library().pep_set_host_threads(C.c_int(int(n))))
+    return int(load_library().pep_set_host_threads(int(n)))
 
 
 def cols_order(q_code, r_code, score):
@@ -697,7 +771,7 @@ def cols_order(q_code, r_code, score):
     q_code, r_code = np.ascontiguousarray(q_code, dtype=np.int64), np.ascontiguousarray(r_code, dtype=np.int64)
     score = np.ascontiguousarray(score, dtype=np.float64)
     order = np.empty(n, dtype=np.int64)
-    if n and lib.pep_cols_order(C.c_uint64(n), _ptr(q_code), _ptr(r_code), _ptr(score), _ptr(order)) != 0:
+    if n and lib.pep_cols_order(n, _ptr(q_code), _ptr(r_code), _ptr(score), _ptr(order)) != 0:
         raise PepError('pep_cols_order failed (negative name codes?)')
     return order
 
@@ -713,7 +787,7 @@ def cols_gather(columns, idx):
     for a in columns:
         assert a.flags['C_CONTIGUOUS'] and a.dtype.itemsize == 8
     n_src = len(columns[0]) if k else 0
-    if lib.pep_cols_gather(C.c_int32(k), src, dst, _ptr(idx) if n else None, C.c_uint64(n), C.c_uint64(n_src)) != 0:
+    if lib.pep_cols_gather(k, src, dst, _ptr_or_null(idx), n, n_src) != 0:
         raise IndexError('take: row index outside the table')
     return [out[c][:n].view(a.dtype) for c, a in enumerate(columns)]
 
@@ -722,7 +796,6 @@ def store_tab_members(rows, off, keys, date_time, threads=None, order=None):
     """pep_store_tab_members: the finished zip entries of all members of the .tab store (PEPPAN.py:91-113, 972-975) ->
     (bytes of all entries, crc uint32[m], compressed size int64[m], size int64[m], offset of the entry int64[m])"""
     lib = load_library()
-    lib.pep_store_tab_members.restype = C.c_int64
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     off, keys = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(keys, dtype=np.int64)
     order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
@@ -738,8 +811,8 @@ def store_tab_members(rows, off, keys, date_time, threads=None, order=None):
     cap = rows.nbytes + rows.nbytes // 512 + 512 * m + 4096         # an upper bound (deflateBound + .npy header + entry header per member): one call; untouched pages cost nothing
     for _ in range(2):
         buf = np.empty(cap, dtype=np.uint8)
-        need = lib.pep_store_tab_members(_ptr(rows), C.c_int64(rows.shape[1]), None if order is None else _ptr(order), _ptr(off), _ptr(keys), C.c_int64(m), C.c_uint32(dos_time), C.c_uint32(dos_date), C.c_int32(threads),
-                                         _ptr(buf), C.c_int64(cap), _ptr(crc), _ptr(csize), _ptr(usize), _ptr(at))
+        need = lib.pep_store_tab_members(_ptr(rows), rows.shape[1], None if order is None else _ptr(order), _ptr(off), _ptr(keys), m, dos_time, dos_date, threads,
+                                         _ptr(buf), cap, _ptr(crc), _ptr(csize), _ptr(usize), _ptr(at))
         if need < 0:
             raise PepError('pep_store_tab_members failed (%d)' % need)
         if need <= cap:
@@ -763,7 +836,7 @@ def _argsort_matches_numpy():
         for n, k in ((17, 3), (200, 5), (1500, 30)):
             v = np.ascontiguousarray(rng.integers(0, k, size=n).astype(np.float64))
             out = np.empty(n, dtype=np.int64)
-            ok = ok and lib.pep_argsort_object_order(_ptr(v), C.c_int64(n), _ptr(out)) == 0 and np.array_equal(out, np.argsort(v.astype(object)))
+            ok = ok and lib.pep_argsort_object_order(_ptr(v), n, _ptr(out)) == 0 and np.array_equal(out, np.argsort(v.astype(object)))
         _ARGSORT_OK = bool(ok)
     return _ARGSORT_OK
 
@@ -774,7 +847,7 @@ def argsort_object_order(values):
     if (len(v) and np.isnan(v).any()) or not _argsort_matches_numpy():
         return np.argsort(v.astype(object))
     out = np.empty(len(v), dtype=np.int64)
-    rc_ = load_library().pep_argsort_object_order(_ptr(v), C.c_int64(len(v)), _ptr(out))
+    rc_ = load_library().pep_argsort_object_order(_ptr(v), len(v), _ptr(out))
     if rc_ == -3:                                    # the sort's depth limit: numpy goes on with heapsort there
         return np.argsort(v.astype(object))
     if rc_ != 0:
@@ -785,7 +858,6 @@ def argsort_object_order(values):
 def store_tab_archive(rows, off, keys, date_time, threads=None, order=None):
     """pep_store_tab_archive: the .tab store as one complete zip archive (uint8 array), or None when it would need zip64 (>= 65 535 members, >= 4 GiB)"""
     lib = load_library()
-    lib.pep_store_tab_archive.restype = C.c_int64
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     off, keys = np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(keys, dtype=np.int64)
     order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
@@ -798,8 +870,8 @@ def store_tab_archive(rows, off, keys, date_time, threads=None, order=None):
     cap = rows.nbytes + rows.nbytes // 512 + 640 * m + 4096         # an upper bound, as above, plus the directory: one call
     for _ in range(2):
         buf = np.empty(cap, dtype=np.uint8)
-        need = lib.pep_store_tab_archive(_ptr(rows), C.c_int64(rows.shape[1]), None if order is None else _ptr(order), _ptr(off), _ptr(keys), C.c_int64(m), C.c_uint32(dos_time),
-                                         C.c_uint32(dos_date), C.c_int32(threads), _ptr(buf), C.c_int64(cap))
+        need = lib.pep_store_tab_archive(_ptr(rows), rows.shape[1], None if order is None else _ptr(order), _ptr(off), _ptr(keys), m, dos_time,
+                                         dos_date, threads, _ptr(buf), cap)
         if need == -3:
             return None
         if need < 0:
@@ -820,7 +892,7 @@ def similar_classify(T, q, r, rank_ge, rank_le, near_identity, cover):
     iden = np.ascontiguousarray(T.iden, dtype=np.float64)
     ge, le = np.ascontiguousarray(rank_ge, dtype=np.uint8), np.ascontiguousarray(rank_le, dtype=np.uint8)
     action, forward, iden4 = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.int32)
-    rc_ = lib.pep_similar_classify(C.c_uint64(n), _ptr(q), _ptr(r), _ptr(iden), *([_ptr(c) for c in cols] + [_ptr(ge), _ptr(le), C.c_double(near_identity), C.c_double(cover),
+    rc_ = lib.pep_similar_classify(n, _ptr(q), _ptr(r), _ptr(iden), *([_ptr(c) for c in cols] + [_ptr(ge), _ptr(le), near_identity, cover,
                                    _ptr(action), _ptr(forward), _ptr(iden4)]))
     if rc_ != 0:
         raise PepError('pep_similar_classify failed (%d)' % rc_)
@@ -840,7 +912,7 @@ def similar_scan(q, r, action, forward, iden4, n_genes):
     ev_kind, ev_a, ev_b = np.zeros(n + 1, dtype=np.uint8), np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
     ev_row_off, ev_rows = np.zeros(n + 2, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
     na, ne = C.c_uint64(), C.c_uint64()
-    rc_ = lib.pep_similar_scan(C.c_uint64(n), _ptr(q), _ptr(r), _ptr(action), _ptr(forward), _ptr(iden4), C.c_uint64(n_genes), _ptr(alive), _ptr(seen),
+    rc_ = lib.pep_similar_scan(n, _ptr(q), _ptr(r), _ptr(action), _ptr(forward), _ptr(iden4), n_genes, _ptr(alive), _ptr(seen),
                                _ptr(absorbed), C.byref(na), _ptr(ev_kind), _ptr(ev_a), _ptr(ev_b), _ptr(ev_row_off), _ptr(ev_rows), C.byref(ne))
     if rc_ != 0:
         raise PepError('pep_similar_scan failed (%d)' % rc_)
@@ -856,7 +928,7 @@ def fasta_keep(path, ids):
     lib = load_library()
     ids = np.unique(np.asarray(ids, dtype=np.int64))
     nr, nk = C.c_uint64(), C.c_uint64()
-    rc_ = lib.pep_fasta_keep(os.fsencode(path), _ptr(ids if len(ids) else np.zeros(1, np.int64)), C.c_uint64(len(ids)), C.byref(nr), C.byref(nk))
+    rc_ = lib.pep_fasta_keep(os.fsencode(path), _ptr(_some(ids)), len(ids), C.byref(nr), C.byref(nk))
     if rc_ == -2:                                   # PEP_ERR_ARG: a name that is not a plain integer, or no such file
         return None
     if rc_ != 0:
@@ -873,7 +945,7 @@ def fasta_scan(data, table, n_records):
     codes = np.empty(max(len(data), 1), dtype=np.uint8)
     off = np.zeros(n_records + 2, dtype=np.uint64)
     nr, high = C.c_uint64(), C.c_int32()
-    rc_ = lib.pep_fasta_scan(C.c_char_p(data), C.c_uint64(len(data)), _ptr(table), _ptr(codes), _ptr(off), C.c_uint64(n_records), C.byref(nr), C.byref(high))
+    rc_ = lib.pep_fasta_scan(data, len(data), _ptr(table), _ptr(codes), _ptr(off), n_records, C.byref(nr), C.byref(high))
     if rc_ == -3 or (rc_ == 0 and (nr.value != n_records or high.value)):          # PEP_ERR_LIMIT: more records than the caller counted
         return None
     if rc_ != 0:
@@ -903,7 +975,7 @@ def fasta_records(data, as_dict=False):
     cap = max(1024, len(data) // 128)                # (a guess; a file of shorter records is counted and scanned again)
     while True:
         off, name_off, name_len = np.empty(cap + 1, dtype=np.uint64), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint32)
-        rc_ = lib.pep_fasta_records(C.c_char_p(data), C.c_uint64(len(data)), _ptr(_UPPER), _ptr(codes), _ptr(off), _ptr(name_off), _ptr(name_len), C.c_uint64(cap),
+        rc_ = lib.pep_fasta_records(data, len(data), _ptr(_UPPER), _ptr(codes), _ptr(off), _ptr(name_off), _ptr(name_len), cap,
                                     C.byref(nr), C.byref(high))
         if rc_ != -3 or cap >= len(data):            # PEP_ERR_LIMIT: more records than guessed
             break
@@ -932,7 +1004,7 @@ def similar_resolve(ev_kind, ev_a, ev_b, ev_value):
     ev_value = np.ascontiguousarray(ev_value, dtype=np.int32)
     out = np.zeros((n + 1, 3), dtype=np.int64)
     no = C.c_uint64()
-    rc_ = lib.pep_similar_resolve(C.c_uint64(n), _ptr(ev_kind), _ptr(ev_a), _ptr(ev_b), _ptr(ev_value), _ptr(out), C.byref(no))
+    rc_ = lib.pep_similar_resolve(n, _ptr(ev_kind), _ptr(ev_a), _ptr(ev_b), _ptr(ev_value), _ptr(out), C.byref(no))
     if rc_ != 0:
         raise PepError('pep_similar_resolve failed (%d)' % rc_)
     return out[:no.value]
@@ -955,8 +1027,8 @@ def merge_hits(hits, cigar, top_k, n_splits, out=None):
             out['c'] = np.empty(int(len(cigar) * 1.5) + 64, dtype=np.uint32)
         out_h, out_c = out['h'], out['c']
     nh, nc = C.c_uint64(), C.c_uint64()
-    rc_ = lib.pep_merge_hits(C.c_uint64(len(hits)), _ptr(hits) if len(hits) else None, _ptr(cigar) if len(cigar) else None, C.c_uint64(len(cigar)),
-                             C.c_int32(int(top_k)), C.c_int32(int(n_splits)), _ptr(out_h), _ptr(out_c), C.byref(nh), C.byref(nc))
+    rc_ = lib.pep_merge_hits(len(hits), _ptr_or_null(hits), _ptr_or_null(cigar), len(cigar),
+                             int(top_k), int(n_splits), _ptr(out_h), _ptr(out_c), C.byref(nh), C.byref(nc))
     if rc_ != 0:
         raise PepError('pep_merge_hits failed (%d)' % rc_)
     return out_h[:nh.value], out_c[:nc.value]
@@ -1010,96 +1082,109 @@ class Context(object):
         if rc != 0:
             raise PepError('%s failed (%d): %s' % (what, rc, self._lib.pep_last_error(self._h).decode()))
 
+    def _call(self, name, *args):
+        """the library's function `name` on this context; PepError with its name, its code and pep_last_error when it fails"""
+        rc = getattr(self._lib, name)(self._h, *args)
+        if rc != 0:
+            self._check(rc, name)
+
+    def _call_on(self, handle, name, *args):
+        """the same for a function that takes a result or verdict handle of this context in the context's place"""
+        rc = getattr(self._lib, name)(handle, *args)
+        if rc != 0:
+            self._check(rc, name)
+
     # ---- inputs
     def set_query_nt(self, seqs, gtable=11):
         self.upload_generation += 1
         self.q_nt_token = None
         nt, off = _pack(seqs)
-        self._check(self._lib.pep_set_query_nt(self._h, _ptr(nt), _ptr(off), C.c_uint32(_count(seqs)), C.c_int(gtable)), 'pep_set_query_nt')
+        self._call('pep_set_query_nt', _ptr(nt), _ptr(off), _count(seqs), gtable)
 
     def set_ref_nt(self, seqs, frames=6, gtable=11):
         self.upload_generation += 1
         self.r_nt_token = None
         nt, off = _pack(seqs)
-        self._check(self._lib.pep_set_ref_nt(self._h, _ptr(nt), _ptr(off), C.c_uint32(_count(seqs)), C.c_int(frames), C.c_int(gtable)), 'pep_set_ref_nt')
+        self._call('pep_set_ref_nt', _ptr(nt), _ptr(off), _count(seqs), frames, gtable)
 
     def set_query_aa(self, seqs):
         self.upload_generation += 1
         self.q_nt_token = None
         aa, off = _pack(seqs)
-        self._check(self._lib.pep_set_query_aa(self._h, _ptr(aa), _ptr(off), C.c_uint32(_count(seqs))), 'pep_set_query_aa')
+        self._call('pep_set_query_aa', _ptr(aa), _ptr(off), _count(seqs))
 
     def set_ref_aa(self, seqs):
         self.upload_generation += 1
         self.r_nt_token = None
         aa, off = _pack(seqs)
-        self._check(self._lib.pep_set_ref_aa(self._h, _ptr(aa), _ptr(off), C.c_uint32(_count(seqs))), 'pep_set_ref_aa')
+        self._call('pep_set_ref_aa', _ptr(aa), _ptr(off), _count(seqs))
 
     def set_target_groups(self, groups):
         """groups: one non-decreasing id per reference sequence (None / empty clears): batch of reference sets in one search"""
         g = np.ascontiguousarray(groups if groups is not None else [], dtype=np.uint32)
-        self._check(self._lib.pep_set_target_groups(self._h, _ptr(g) if len(g) else None, C.c_uint32(len(g))), 'pep_set_target_groups')
+        self._call('pep_set_target_groups', _ptr_or_null(g), len(g))
 
     def use_nt_as_residues(self, strands=2):
         """the device-resident nucleotide sets themselves become the residue sets (base codes; reference: forward strands, then reverse
         complements, per target group) - the inputs of the nucleotide search.  Until the next translate() / set_*."""
         self._drop_view()
-        self._check(self._lib.pep_use_nt_as_residues(self._h, C.c_int(strands)), 'pep_use_nt_as_residues')
+        self._call('pep_use_nt_as_residues', strands)
 
     def set_timing(self, level):
         """phase timers of the searches (the ms_* statistics): 0 none (default), 1 the score pass only, 2 every phase - each HIP event costs
         the GPU about 6 us of idle time between two kernels"""
-        self._check(self._lib.pep_set_timing(self._h, C.c_int(level)), 'pep_set_timing')
+        self._call('pep_set_timing', level)
 
     def set_grouping(self, n_nodes, node_of_target=None, q_base=0):
         """every search of this context ends with single linkage (K10) over its own hit table: edges (hit.q + q_base, node_of_target[hit.t]);
         the labels of the newest search are in self.labels afterwards.  n_nodes = 0 switches it off."""
         nn = np.ascontiguousarray(node_of_target if node_of_target is not None else [], dtype=np.uint32)
-        self._check(self._lib.pep_set_grouping(self._h, C.c_uint32(n_nodes), C.c_uint32(q_base), _ptr(nn) if len(nn) else None, C.c_uint64(len(nn))), 'pep_set_grouping')
+        self._call('pep_set_grouping', n_nodes, q_base, _ptr_or_null(nn), len(nn))
         self._grouping = int(n_nodes)
         self.labels = None
 
     def _take_labels(self, r):
         if getattr(self, '_grouping', 0):
             lab = np.empty(self._grouping, dtype=np.uint32)
-            self._check(self._lib.pep_result_labels(r, _ptr(lab), C.c_uint32(self._grouping)), 'pep_result_labels')
+            self._call_on(r, 'pep_result_labels', _ptr(lab), self._grouping)
             self.labels = lab
 
     def invalidate_translation(self):
         """the next search() runs K1 again, inside the search (cheaper than translate(force=True) in front of it: no host wait between K1 and the search)"""
-        self._check(self._lib.pep_invalidate_translation(self._h), 'pep_invalidate_translation')
+        self._call('pep_invalidate_translation')
 
     def translate(self, force=False):
-        self._check(self._lib.pep_translate(self._h, C.c_int(1 if force else 0)), 'pep_translate')
+        self._call('pep_translate', 1 if force else 0)
 
     # ---- K1 products
-    def query_meta(self):
+    def _counts(self, count_fn):
         n, r = C.c_uint32(), C.c_uint64()
-        self._check(self._lib.pep_query_count(self._h, C.byref(n), C.byref(r)), 'pep_query_count')
-        out = np.zeros(n.value, dtype=QUERY_META_DTYPE)
-        self._check(self._lib.pep_get_query_meta(self._h, _ptr(out), C.c_uint32(n.value)), 'pep_get_query_meta')
+        self._call(count_fn, C.byref(n), C.byref(r))
+        return n.value, r.value
+
+    def _get_meta(self, count_fn, get_fn, dtype):
+        out = np.zeros(self._counts(count_fn)[0], dtype=dtype)
+        self._call(get_fn, _ptr(out), len(out))
         return out
+
+    def query_meta(self):
+        return self._get_meta('pep_query_count', 'pep_get_query_meta', QUERY_META_DTYPE)
 
     def target_meta(self):
-        n, r = C.c_uint32(), C.c_uint64()
-        self._check(self._lib.pep_target_count(self._h, C.byref(n), C.byref(r)), 'pep_target_count')
-        out = np.zeros(n.value, dtype=TARGET_META_DTYPE)
-        self._check(self._lib.pep_get_target_meta(self._h, _ptr(out), C.c_uint32(n.value)), 'pep_get_target_meta')
-        return out
+        return self._get_meta('pep_target_count', 'pep_get_target_meta', TARGET_META_DTYPE)
 
-    def _get_aa(self, count_fn, get_fn, what):
-        n, r = C.c_uint32(), C.c_uint64()
-        self._check(count_fn(self._h, C.byref(n), C.byref(r)), what)
-        codes = np.zeros(max(1, r.value), dtype=np.uint8)
-        off = np.zeros(n.value + 1, dtype=np.uint64)
-        self._check(get_fn(self._h, _ptr(codes), C.c_uint64(r.value), _ptr(off)), what)
-        return codes[:r.value], off
+    def _get_aa(self, count_fn, get_fn):
+        n, r = self._counts(count_fn)
+        codes = np.zeros(max(1, r), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        self._call(get_fn, _ptr(codes), r, _ptr(off))
+        return codes[:r], off
 
     def query_aa(self):
-        return self._get_aa(self._lib.pep_query_count, self._lib.pep_get_query_aa, 'pep_get_query_aa')
+        return self._get_aa('pep_query_count', 'pep_get_query_aa')
 
     def target_aa(self):
-        return self._get_aa(self._lib.pep_target_count, self._lib.pep_get_target_aa, 'pep_get_target_aa')
+        return self._get_aa('pep_target_count', 'pep_get_target_aa')
 
     def _drop_view(self):
         if self._view is not None:                      # the handle behind the previous zero-copy views: released first, so that
@@ -1113,26 +1198,26 @@ class Context(object):
         until the next search on this context (for callers that consume the table at once, like hits_to_blastab)."""
         self._drop_view()
         r = C.c_void_p()
-        self._check(self._lib.pep_search(self._h, C.byref(params) if params is not None else None, C.byref(r)), 'pep_search')
+        self._call('pep_search', C.byref(params) if params is not None else None, C.byref(r))
         try:
             nh, nc = C.c_uint64(), C.c_uint64()
-            self._check(self._lib.pep_result_size(r, C.byref(nh), C.byref(nc)), 'pep_result_size')
+            self._call_on(r, 'pep_result_size', C.byref(nh), C.byref(nc))
             st = Stats()
-            self._check(self._lib.pep_result_stats(r, C.byref(st)), 'pep_result_stats')
+            self._call_on(r, 'pep_result_stats', C.byref(st))
             self._take_labels(r)
             self.last_nt_match = None
             if self._nt_match_on and nh.value:
                 pm = C.c_void_p()
-                self._check(self._lib.pep_result_nt_match(r, C.byref(pm)), 'pep_result_nt_match')
+                self._call_on(r, 'pep_result_nt_match', C.byref(pm))
                 if pm.value:
                     self.last_nt_match = np.frombuffer((C.c_char * (nh.value * 4)).from_address(pm.value), dtype=np.uint32).copy()
             if copy or nh.value == 0:
                 hits = np.empty(nh.value, dtype=HIT_DTYPE)
                 cig = np.empty(nc.value, dtype=np.uint32)
-                self._check(self._lib.pep_result_copy(r, _ptr(hits), _ptr(cig)), 'pep_result_copy')
+                self._call_on(r, 'pep_result_copy', _ptr(hits), _ptr(cig))
             else:
                 ph, pc = C.c_void_p(), C.c_void_p()
-                self._check(self._lib.pep_result_data(r, C.byref(ph), C.byref(pc)), 'pep_result_data')
+                self._call_on(r, 'pep_result_data', C.byref(ph), C.byref(pc))
                 hits = np.frombuffer((C.c_char * (nh.value * HIT_DTYPE.itemsize)).from_address(ph.value), dtype=HIT_DTYPE)
                 cig = (np.frombuffer((C.c_char * (nc.value * 4)).from_address(pc.value), dtype=np.uint32) if nc.value else np.empty(0, np.uint32))
                 self._view, r = r, None                 # keep the handle alive while the views may be in use
@@ -1148,34 +1233,34 @@ class Context(object):
         if self._view is not None:
             self._lib.pep_result_free(self._view)
             self._view = None
-        self._check(self._lib.pep_set_result_mode(self._h, C.c_int(1)), 'pep_set_result_mode')
+        self._call('pep_set_result_mode', 1)
         r = C.c_void_p()
         try:
-            self._check(self._lib.pep_search(self._h, C.byref(params) if params is not None else None, C.byref(r)), 'pep_search')
+            self._call('pep_search', C.byref(params) if params is not None else None, C.byref(r))
         finally:
-            self._lib.pep_set_result_mode(self._h, C.c_int(0))
+            self._lib.pep_set_result_mode(self._h, 0)
         nh, nc = C.c_uint64(), C.c_uint64()
         st = Stats()
         ph, pc = C.c_void_p(), C.c_void_p()
         self._view = r
-        self._check(self._lib.pep_result_size(r, C.byref(nh), C.byref(nc)), 'pep_result_size')
-        self._check(self._lib.pep_result_stats(r, C.byref(st)), 'pep_result_stats')
+        self._call_on(r, 'pep_result_size', C.byref(nh), C.byref(nc))
+        self._call_on(r, 'pep_result_stats', C.byref(st))
         if nh.value:
-            self._check(self._lib.pep_result_device(r, C.byref(ph), C.byref(pc)), 'pep_result_device')
+            self._call_on(r, 'pep_result_device', C.byref(ph), C.byref(pc))
         return nh.value, nc.value, {n: getattr(st, n) for n, _ in Stats._fields_}, (ph.value or 0, pc.value or 0)
 
     def result_to_host(self):
         """(hits, cigar) of the result search_on_device() is holding"""
         nh, nc = C.c_uint64(), C.c_uint64()
-        self._check(self._lib.pep_result_size(self._view, C.byref(nh), C.byref(nc)), 'pep_result_size')
+        self._call_on(self._view, 'pep_result_size', C.byref(nh), C.byref(nc))
         hits, cig = np.empty(nh.value, dtype=HIT_DTYPE), np.empty(nc.value, dtype=np.uint32)
-        self._check(self._lib.pep_result_copy(self._view, _ptr(hits), _ptr(cig)), 'pep_result_copy')
+        self._call_on(self._view, 'pep_result_copy', _ptr(hits), _ptr(cig))
         return hits, cig
 
     # ---- K7
     def set_nt_match(self, on):
         """pep_set_nt_match: the searches of this context also count the identical nucleotide columns of every hit (K7's n_match) -> last_nt_match after search()"""
-        self._check(self._lib.pep_set_nt_match(self._h, C.c_int(1 if on else 0)), 'pep_set_nt_match')
+        self._call('pep_set_nt_match', 1 if on else 0)
         self._nt_match_on = bool(on)
 
     def rescore_nt(self, nt_hits, cigar):
@@ -1183,8 +1268,8 @@ class Context(object):
         cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
         out = np.zeros((len(nt_hits), 5), dtype=np.int64)
         if len(nt_hits):
-            cg = cigar if len(cigar) else np.zeros(1, np.uint32)
-            self._check(self._lib.pep_rescore_nt(self._h, C.c_uint64(len(nt_hits)), _ptr(nt_hits), _ptr(cg), C.c_uint64(len(cigar)), _ptr(out)), 'pep_rescore_nt')
+            cg = _some(cigar)
+            self._call('pep_rescore_nt', len(nt_hits), _ptr(nt_hits), _ptr(cg), len(cigar), _ptr(out))
         return out
 
     def rescore_codons(self, nt_hits, cigar, mode, table_id=11):
@@ -1193,7 +1278,7 @@ class Context(object):
         turns them into identity and score.  The amino-acid and substitution tables of mode 2 are this package's (codon_tables)"""
         args, keep = _codon_args(nt_hits, cigar, mode, codon_tables(table_id) if mode == 2 else None)
         out = np.zeros((len(nt_hits), 7), dtype=np.int64)
-        self._check(self._lib.pep_rescore_codons(self._h, *args, _ptr(out if len(out) else np.zeros(7, np.int64))), 'pep_rescore_codons')
+        self._call('pep_rescore_codons', *args, _ptr(out if len(out) else np.zeros(7, np.int64)))
         return out
 
     # ---- K14
@@ -1207,10 +1292,9 @@ class Context(object):
         ng = len(grp_qlen)
         value = np.full(max(ng, 1), SUPPORT_NONE, dtype=np.int32)
         if ng:
-            cg = cigar if len(cigar) else np.zeros(1, np.uint32)
-            rr = rows if len(rows) else np.zeros(1, SUPPORT_ROW_DTYPE)
-            self._check(self._lib.pep_pair_support(self._h, C.c_uint64(len(rows)), _ptr(rr), _ptr(cg), C.c_uint64(len(cigar)), C.c_uint64(ng), _ptr(grp_off),
-                                                   _ptr(grp_qlen), _ptr(grp_rlen), C.byref(limits), _ptr(value)), 'pep_pair_support')
+            cg = _some(cigar)
+            rr = _some(rows)
+            self._call('pep_pair_support', len(rows), _ptr(rr), _ptr(cg), len(cigar), ng, _ptr(grp_off), _ptr(grp_qlen), _ptr(grp_rlen), C.byref(limits), _ptr(value))
         return value[:ng]
 
     # ---- K9
@@ -1222,8 +1306,7 @@ class Context(object):
         rep = np.zeros(n, dtype=np.uint32)
         stats = np.zeros(3, dtype=np.uint64)
         if n:
-            self._check(self._lib.pep_linclust(self._h, _ptr(codes), _ptr(off), C.c_uint32(n), C.c_int(base), C.c_int(k), C.c_int(m),
-                                               C.c_double(min_id), C.c_double(min_cov), _ptr(rep), _ptr(stats)), 'pep_linclust')
+            self._call('pep_linclust', _ptr(codes), _ptr(off), n, base, k, m, min_id, min_cov, _ptr(rep), _ptr(stats))
         return rep, dict(selected=int(stats[0]), verified=int(stats[1]), accepted=int(stats[2]))
 
     # ---- K11
@@ -1238,8 +1321,7 @@ class Context(object):
         cap = max(1024, 4 * n)
         for _ in range(2):
             out = np.zeros((cap, 3), dtype=np.int64)
-            self._check(self._lib.pep_overlaps(self._h, C.c_uint64(n), _ptr(contig), _ptr(start), _ptr(end), _ptr(row_id), C.c_double(ovl_l),
-                                               C.c_double(ovl_p), _ptr(out), C.c_uint64(cap), C.byref(m)), 'pep_overlaps')
+            self._call('pep_overlaps', n, _ptr(contig), _ptr(start), _ptr(end), _ptr(row_id), ovl_l, ovl_p, _ptr(out), cap, C.byref(m))
             if m.value <= cap:
                 return out[:m.value]
             cap = m.value
@@ -1258,10 +1340,9 @@ class Context(object):
         in_frame, orf = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
         total = int(((grp_qlen.astype(np.int64) + 2) // 3).sum())
         packed = np.zeros(max(total, 1), dtype=np.uint8)
-        cg = cigar if len(cigar) else np.zeros(1, np.uint32)
-        self._check(self._lib.pep_alleles(self._h, _ptr(nt), _ptr(off), C.c_uint32(len(contigs)), C.c_uint64(n), _ptr(rows), _ptr(cg), C.c_uint64(len(cigar)),
-                                          C.c_uint32(ng), _ptr(grp_off), _ptr(grp_qlen) if ng else None, C.c_int(gtable), _ptr(in_frame), _ptr(orf),
-                                          _ptr(packed), C.c_uint64(total)), 'pep_alleles')
+        cg = _some(cigar)
+        self._call('pep_alleles', _ptr(nt), _ptr(off), len(contigs), n, _ptr(rows), _ptr(cg), len(cigar), ng, _ptr(grp_off), _ptr_or_null(grp_qlen), gtable,
+                   _ptr(in_frame), _ptr(orf), _ptr(packed), total)
         return in_frame[:n], orf[:n], packed[:total]
 
     # ---- K15
@@ -1296,8 +1377,8 @@ class Context(object):
         out_off = np.concatenate([[0], np.cumsum(need)]).astype(np.uint64)
         total = int(out_off[-1])
         out = np.empty(max(total, 1), dtype=np.int32)
-        self._check(self._lib.pep_allele_diff(self._h, _ptr(pk), _ptr(row_off), _ptr(rl), C.c_uint64(len(row_len)), C.c_uint32(len(groups)), _ptr(grp_off),
-                                              _ptr(grp_rows), _ptr(md), _ptr(out), _ptr(out_off), C.c_uint64(total)), 'pep_allele_diff')
+        self._call('pep_allele_diff', _ptr(pk), _ptr(row_off), _ptr(rl), len(row_len), len(groups), _ptr(grp_off), _ptr(grp_rows), _ptr(md),
+                   _ptr(out), _ptr(out_off), total)
         res = []
         for g in range(len(groups)):
             a, ng = int(out_off[g]), int(n[g])
@@ -1310,7 +1391,7 @@ class Context(object):
         """of the newest allele_diff library call, in ms: (allele_planes, allele_diff) kernel times when set_timing(2) is on, else zeros, and the
         host's wall time from the end of the kernels until the output lay in the caller's buffer"""
         a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._check(self._lib.pep_allele_diff_times(self._h, C.byref(a), C.byref(b), C.byref(c)), 'pep_allele_diff_times')
+        self._call('pep_allele_diff_times', C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
     # ---- K16
@@ -1337,16 +1418,16 @@ class Context(object):
         args, keep = _verdict_tables(packed, row_off, row_len, groups, genomes, inparalog, gd)
         verdict = np.zeros(max(len(groups), 1), dtype=np.uint8)
         handle = C.c_void_p()
-        self._check(self._lib.pep_group_verdicts(self._h, *args, C.c_double(self_id), _ptr(verdict), C.byref(handle)), 'pep_group_verdicts')
+        self._call('pep_group_verdicts', *args, self_id, _ptr(verdict), C.byref(handle))
         try:
             res = []
             for g in range(len(groups)):
                 tri = leader = None
                 if detail and verdict[g] == 2:
                     pairs = C.c_uint64()
-                    self._check(self._lib.pep_verdict_detail_size(handle, C.c_uint32(g), C.byref(pairs)), 'pep_verdict_detail_size')
+                    self._call_on(handle, 'pep_verdict_detail_size', g, C.byref(pairs))
                     tri, leader = np.empty((pairs.value, 2), dtype=np.int32), np.empty(int(n[g]), dtype=np.uint32)
-                    self._check(self._lib.pep_verdict_detail_copy(handle, C.c_uint32(g), _ptr(tri), _ptr(leader)), 'pep_verdict_detail_copy')
+                    self._call_on(handle, 'pep_verdict_detail_copy', g, _ptr(tri), _ptr(leader))
                 res.append((int(verdict[g]), tri, leader))
             ms, moved = self.group_verdicts_times()
             self._verdict_stats[0] += ms
@@ -1359,7 +1440,7 @@ class Context(object):
         """of the newest pep_group_verdicts library call: (float64[4] kernel times in ms - bit planes, edge, pairs, leaders - when set_timing(2) is on,
         else zeros; bytes that call and the detail copies of its result sent to the host)"""
         ms, moved = (C.c_double * 4)(), C.c_uint64()
-        self._check(self._lib.pep_group_verdicts_times(self._h, ms, C.byref(moved)), 'pep_group_verdicts_times')
+        self._call('pep_group_verdicts_times', ms, C.byref(moved))
         return np.array(list(ms)), int(moved.value)
 
     def group_verdicts_totals(self):
@@ -1375,13 +1456,13 @@ class Context(object):
         args, n_rows, n_genes, keep_alive = _ingroup_tables(genome, iden, score, gene_off, gd)
         keep = np.zeros(max(n_rows, 1), dtype=np.uint8)
         gene_score = np.zeros(max(n_genes, 1), dtype=np.int64)
-        self._check(self._lib.pep_gene_ingroups(self._h, *args, C.c_double(self_id), C.c_double(thr), _ptr(keep), _ptr(gene_score)), 'pep_gene_ingroups')
+        self._call('pep_gene_ingroups', *args, self_id, thr, _ptr(keep), _ptr(gene_score))
         return keep[:n_rows].astype(bool), gene_score[:n_genes]
 
     def gene_ingroups_times(self):
         """of the newest pep_gene_ingroups: (float64[2] kernel times in ms - pairs, finish - when set_timing(2) is on, else zeros; bytes the call sent to the host)"""
         ms, moved = (C.c_double * 2)(), C.c_uint64()
-        self._check(self._lib.pep_gene_ingroups_times(self._h, ms, C.byref(moved)), 'pep_gene_ingroups_times')
+        self._call('pep_gene_ingroups_times', ms, C.byref(moved))
         return np.array(list(ms)), int(moved.value)
 
     # ---- K13
@@ -1390,7 +1471,7 @@ class Context(object):
         data, off = _pack(seqs)
         out = np.zeros((max(len(seqs), 1), 20), dtype=np.uint8)
         if len(seqs):
-            self._check(self._lib.pep_sha1(self._h, _ptr(data), _ptr(off), C.c_uint32(len(seqs)), _ptr(out)), 'pep_sha1')
+            self._call('pep_sha1', _ptr(data), _ptr(off), len(seqs), _ptr(out))
         return out[:len(seqs)]
 
     def dedup(self, lengths, digests):
@@ -1400,7 +1481,7 @@ class Context(object):
         assert len(lengths) == len(digests)
         rep = np.zeros(max(len(lengths), 1), dtype=np.uint32)
         if len(lengths):
-            self._check(self._lib.pep_dedup(self._h, C.c_uint32(len(lengths)), _ptr(lengths), _ptr(digests), _ptr(rep)), 'pep_dedup')
+            self._call('pep_dedup', len(lengths), _ptr(lengths), _ptr(digests), _ptr(rep))
         return rep[:len(lengths)]
 
     # ---- K10
@@ -1410,10 +1491,9 @@ class Context(object):
         node_of_target = np.ascontiguousarray(node_of_target, dtype=np.uint32)
         lab = np.zeros(n_nodes, dtype=np.uint32)
         if n_nodes:
-            hh = hits if len(hits) else np.zeros(1, HIT_DTYPE)
-            nn = node_of_target if len(node_of_target) else np.zeros(1, np.uint32)
-            self._check(self._lib.pep_components_of_hits(self._h, C.c_uint32(n_nodes), C.c_uint64(len(hits)), _ptr(hh), C.c_uint32(q_base), _ptr(nn),
-                                                         C.c_uint64(len(node_of_target)), _ptr(lab)), 'pep_components_of_hits')
+            hh = _some(hits)
+            nn = _some(node_of_target)
+            self._call('pep_components_of_hits', n_nodes, len(hits), _ptr(hh), q_base, _ptr(nn), len(node_of_target), _ptr(lab))
         return lab
 
     def components_of_search(self, n_nodes, node_of_target, q_base=0):
@@ -1424,9 +1504,8 @@ class Context(object):
         node_of_target = np.ascontiguousarray(node_of_target, dtype=np.uint32)
         lab = np.zeros(n_nodes, dtype=np.uint32)
         if n_nodes:
-            nn = node_of_target if len(node_of_target) else np.zeros(1, np.uint32)
-            self._check(self._lib.pep_components_of_result(self._h, self._view, C.c_uint32(n_nodes), C.c_uint32(q_base), _ptr(nn), C.c_uint64(len(node_of_target)),
-                                                           _ptr(lab)), 'pep_components_of_result')
+            nn = _some(node_of_target)
+            self._call('pep_components_of_result', self._view, n_nodes, q_base, _ptr(nn), len(node_of_target), _ptr(lab))
         return lab
 
     def components(self, n_nodes, a, b):
@@ -1434,7 +1513,7 @@ class Context(object):
         b = np.ascontiguousarray(b, dtype=np.uint32)
         lab = np.zeros(n_nodes, dtype=np.uint32)
         if n_nodes:
-            aa = a if len(a) else np.zeros(1, np.uint32)
-            bb = b if len(b) else np.zeros(1, np.uint32)
-            self._check(self._lib.pep_components(self._h, C.c_uint32(n_nodes), C.c_uint64(len(a)), _ptr(aa), _ptr(bb), _ptr(lab)), 'pep_components')
+            aa = _some(a)
+            bb = _some(b)
+            self._call('pep_components', n_nodes, len(a), _ptr(aa), _ptr(bb), _ptr(lab))
         return lab

@@ -20,6 +20,65 @@ def test_library_exports_every_declared_symbol():
     assert lib.pep_version() == N.ABI_VERSION
 
 
+SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'double': C.c_double}
+
+
+def _header_prototypes():
+    """[(return declaration, name, [parameter declaration])] of every prototype of the header, comments stripped"""
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read(), flags=re.S)
+    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
+    return [(ret.strip(), name, [] if params.strip() == 'void' else [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
+
+
+def _ctypes_of(decl, is_return=False):
+    """the ctypes types that may stand for a C declaration of the header: pointers and arrays c_void_p (a char pointer also c_char_p), scalars their own width"""
+    if decl == 'void':
+        return {None}
+    if '*' in decl or '[' in decl:
+        if re.match(r'(const )?char \*', decl):
+            return {C.c_char_p} if is_return else {C.c_char_p, C.c_void_p}
+        return {C.c_void_p}
+    return {SCALARS[decl.replace('const ', '').split()[0]]}
+
+
+def test_signature_table_is_the_header():
+    """peppan_amd._native.SIGNATURES states the return and parameter types of every prototype of include/peppan_hip.h, and load_library() has given them to ctypes"""
+    from peppan_amd import _native as N
+    protos = _header_prototypes()
+    assert len(protos) == 85 and sum(len(params) for _, _, params in protos) == 531          # (a prototype the pattern misses shows here)
+    assert {name for _, name, _ in protos} == set(N.SIGNATURES) == set(N.EXPORTS) and len(N.EXPORTS) == 85
+    lib = N.load_library()
+    for ret, name, params in protos:
+        restype, *argtypes = N.SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        assert restype in _ctypes_of(ret, is_return=True), name
+        for k, (decl, t) in enumerate(zip(params, argtypes)):
+            assert t in _ctypes_of(decl), (name, k, decl)
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+
+
+def test_typing_acts_before_the_library_does():
+    """a float for an int64_t parameter and a call with an argument missing are refused by ctypes: the library is never entered"""
+    from peppan_amd import _native as N
+    lib = N.load_library()
+    with pytest.raises((C.ArgumentError, TypeError)):
+        lib.pep_crc32(None, 1.5, 0)
+    with pytest.raises((C.ArgumentError, TypeError)):
+        lib.pep_set_host_threads()
+
+
+def test_direct_callers_get_the_full_return_width():
+    """the return types are set when the library is loaded, not by the wrappers: a call past them is not cut to a C int"""
+    import zlib
+    import numpy as np
+    from peppan_amd import _native as N
+    lib = N.load_library()
+    assert lib.pep_deflate_literals.restype is C.c_int64 and lib.pep_crc32.restype is C.c_uint32
+    data = np.random.default_rng(20261018).integers(0, 256, size=1000, dtype=np.uint8)
+    assert lib.pep_crc32(N._ptr(data), len(data), 0) == zlib.crc32(data.tobytes())
+
+
 def test_struct_layouts_match_header(tmp_path):
     """sizes and field offsets of every struct that crosses the boundary, taken from the header by a C compiler, equal the ctypes / numpy
     mirrors in peppan_amd/_native.py"""
