@@ -106,6 +106,19 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
+# ... and of include/peppan_synteny.h (K18), a header with a version of its own; tests/test_synteny_host.py holds this table to it
+SYNTENY_ABI_VERSION = 1
+SYNTENY_MAX_PAIRS = 1 << 27              # PEP_SYNTENY_MAX_PAIRS: pairs of one pep_synteny_pairs call
+SYNTENY_MAX_COUNTERS = 1 << 26           # PEP_SYNTENY_MAX_COUNTERS: rank counters of one call, n * (6 * longest list + 14) per group of two members and more
+SYNTENY_SIGNATURES = {
+    'pep_synteny_version': (I,),
+    'pep_synteny_pairs': (I, P, U32, P, P, U64, P, P, U64, I32, P, P, P, P),
+    'pep_synteny_pairs_copy': (I, P, P, U64, P, U64),
+    'pep_synteny_pairs_check': (I, U32, P, P, U64, P, P, U64, I32, P, U64),
+    'pep_synteny_pairs_times': (I, P, P, P),
+    'pep_synteny_walk': (I, U32, P, P, P, P, P, P, P, P, P, P, P, U64),
+}
+
 
 class PepError(RuntimeError):
     pass
@@ -194,13 +207,15 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in SIGNATURES.items():
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.pep_version() != ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch')
+    if lib.pep_synteny_version() != SYNTENY_ABI_VERSION:
+        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_synteny.h)')
     _lib = lib
     return lib
 
@@ -458,6 +473,61 @@ def gene_ingroups_check(genome, iden, score, gene_off, gd, self_id, thr):
     """the host checks of pep_gene_ingroups alone (no context, no device): PepError with the library's code and text, else None"""
     args, _, _, keep = _ingroup_tables(genome, iden, score, gene_off, gd)
     _check_only('pep_gene_ingroups_check', *args, self_id, thr)
+
+
+def _synteny_tables(member_off, genome, nb_off, nb, n_neighbor):
+    """the arrays of one pep_synteny_pairs / pep_synteny_pairs_check call as the library's types -> (arguments, n_groups, what keeps them alive)"""
+    member_off = np.ascontiguousarray(member_off, dtype=np.uint64).reshape(-1)
+    genome = np.ascontiguousarray(genome, dtype=np.uint32).reshape(-1)
+    nb_off = np.ascontiguousarray(nb_off, dtype=np.uint64).reshape(-1)
+    nb = np.ascontiguousarray(nb, dtype=np.uint32).reshape(-1)
+    if len(member_off) < 1:
+        raise ValueError('synteny_pairs: member_off needs one entry more than there are groups')
+    if len(nb_off) != len(genome) + 1:
+        raise ValueError('synteny_pairs: nb_off needs one entry more than there are members')
+    if int(n_neighbor) != n_neighbor or not -2 ** 31 <= int(n_neighbor) < 2 ** 31:
+        raise ValueError('synteny_pairs: n_neighbor must be an integer that fits 32 bits, not %r' % (n_neighbor,))
+    keep = [member_off, _some(genome), nb_off, _some(nb)]
+    args = [len(member_off) - 1, _ptr(keep[0]), _ptr(keep[1]), len(genome), _ptr(keep[2]), _ptr(keep[3]), len(nb), int(n_neighbor)]
+    return args, len(member_off) - 1, keep
+
+
+def synteny_pairs_check(member_off, genome, nb_off, nb, n_neighbor):
+    """the host checks of pep_synteny_pairs alone (no context, no device): PepError with the library's code and text, else None"""
+    args, _, keep = _synteny_tables(member_off, genome, nb_off, nb, n_neighbor)
+    _check_only('pep_synteny_pairs_check', *args)
+
+
+def synteny_walk(member_off, conf_off, conf, walk_off, walk):
+    """pep_synteny_walk (host C++, no context): the merge walk of ite_synteny_resolver (PEPPAN.py:1118-1151) over the two pair lists of
+    Context.synteny_pairs -> (verdict uint8[G]: 0 none, 1 refused, 2 partition; components: per group None or the list of its components as
+    (root, int64 array of member numbers in the reference's order), by ascending root - the root is the member whose id keys the component in
+    the reference's dictionary)"""
+    member_off = np.ascontiguousarray(member_off, dtype=np.uint64).reshape(-1)
+    conf_off = np.ascontiguousarray(conf_off, dtype=np.uint64).reshape(-1)
+    walk_off = np.ascontiguousarray(walk_off, dtype=np.uint64).reshape(-1)
+    conf = np.ascontiguousarray(conf, dtype=np.uint32).reshape(-1, 2)
+    walk = np.ascontiguousarray(walk, dtype=np.uint32).reshape(-1, 2)
+    n_groups = len(member_off) - 1
+    if n_groups < 0 or len(conf_off) != n_groups + 1 or len(walk_off) != n_groups + 1:
+        raise ValueError('synteny_walk: one offset more than there are groups in each of the three offset tables')
+    if int(conf_off[-1]) != len(conf) or int(walk_off[-1]) != len(walk):
+        raise ValueError('synteny_walk: the offsets must end at the length of their list')
+    n_members = int(member_off[-1])
+    verdict, n_comp = np.zeros(max(n_groups, 1), np.uint8), np.zeros(max(n_groups, 1), np.uint32)
+    comp_root, comp_len, members = (np.zeros(max(n_members, 1), np.uint32) for _ in range(3))
+    cc, ww = _some(conf), _some(walk)
+    _check_only('pep_synteny_walk', n_groups, _ptr(member_off), _ptr(conf_off), _ptr(cc), _ptr(walk_off), _ptr(ww), _ptr(verdict), _ptr(n_comp), _ptr(comp_root),
+                _ptr(comp_len), _ptr(members))
+    comps = []
+    for g in range(n_groups):
+        if verdict[g] != 2:
+            comps.append(None)
+            continue
+        lo = int(member_off[g])
+        cuts = np.cumsum(comp_len[lo:lo + int(n_comp[g])])[:-1]
+        comps.append(list(zip(comp_root[lo:lo + int(n_comp[g])].tolist(), np.split(members[lo:int(member_off[g + 1])].astype(np.int64), cuts))))
+    return verdict[:n_groups], comps
 
 
 def codon_tables(table_id=11):
@@ -1463,6 +1533,27 @@ class Context(object):
         """of the newest pep_gene_ingroups: (float64[2] kernel times in ms - pairs, finish - when set_timing(2) is on, else zeros; bytes the call sent to the host)"""
         ms, moved = (C.c_double * 2)(), C.c_uint64()
         self._call('pep_gene_ingroups_times', ms, C.byref(moved))
+        return np.array(list(ms)), int(moved.value)
+
+    # ---- K18
+    def synteny_pairs(self, member_off, genome, nb_off, nb, n_neighbor):
+        """the pair loop of ite_synteny_resolver (PEPPAN.py:1101-1117) for a batch of paralogous names.  Group g is members member_off[g] ..
+        member_off[g+1] of genome and of the neighbour lists nb[nb_off[i] .. nb_off[i+1]] (strictly ascending).
+        -> (has_conflict bool[G], dc int32[G], conf_off int64[G+1], conf uint32[., 2], walk_off int64[G+1], walk uint32[., 2]): the conflict pairs
+        (m, k) ascending and the pairs with d < dc in the order (d, flag, m, k), as include/peppan_synteny.h states them"""
+        args, n_groups, keep_alive = _synteny_tables(member_off, genome, nb_off, nb, n_neighbor)
+        has, dc = np.zeros(max(n_groups, 1), np.uint8), np.zeros(max(n_groups, 1), np.int32)
+        conf_off, walk_off = np.zeros(n_groups + 1, np.uint64), np.zeros(n_groups + 1, np.uint64)
+        self._call('pep_synteny_pairs', *args, _ptr(has), _ptr(dc), _ptr(conf_off), _ptr(walk_off))
+        n_conf, n_walk = int(conf_off[-1]), int(walk_off[-1])
+        conf, walk = np.zeros((max(n_conf, 1), 2), np.uint32), np.zeros((max(n_walk, 1), 2), np.uint32)
+        self._call('pep_synteny_pairs_copy', _ptr(conf), n_conf, _ptr(walk), n_walk)
+        return has[:n_groups].astype(bool), dc[:n_groups], conf_off.astype(np.int64), conf[:n_conf], walk_off.astype(np.int64), walk[:n_walk]
+
+    def synteny_times(self):
+        """of the newest pep_synteny_pairs: (float64[3] kernel times in ms - count, scans, emit - when set_timing(2) is on, else zeros; bytes it sent to the host)"""
+        ms, moved = (C.c_double * 3)(), C.c_uint64()
+        self._call('pep_synteny_pairs_times', ms, C.byref(moved))
         return np.array(list(ms)), int(moved.value)
 
     # ---- K13

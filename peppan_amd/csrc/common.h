@@ -258,6 +258,10 @@ struct pep_ctx {
     double k17_ms[2] = {0., 0.};             // the newest pep_gene_ingroups: kernel times (pairs, finish) when pep_set_timing is 2 (ingroup.hip)
     uint64_t k17_bytes_to_host = 0;          // ... and what it sent to the host
     DevBuf k17[11];                          // grow-only: its tables, work list and outputs (the slots: ingroup.hip)
+    double k18_ms[3] = {0., 0., 0.};         // the newest pep_synteny_pairs: kernel times (count, scans, emit) when pep_set_timing is 2 (synteny.hip)
+    uint64_t k18_bytes_to_host = 0;          // ... and what it and its pep_synteny_pairs_copy sent to the host
+    uint64_t k18_n_conf = 0, k18_n_walk = 0; // the pairs its two lists hold, waiting on the device for pep_synteny_pairs_copy
+    DevBuf k18[18];                          // grow-only: its tables, counters and the two lists (the slots: synteny.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
