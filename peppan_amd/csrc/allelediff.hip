@@ -98,10 +98,18 @@ void pep_k15_queue_planes(hipStream_t st, uint64_t n_rows, const uint8_t *d_pack
     hipLaunchKernelGGL(allele_planes, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, st, n_rows, d_packed, d_row_off, d_row_len, d_plane_off, d_planes, d_bad_row);
 }
 
-int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
-                        uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
-                        int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap)
+extern "C" {
+
+int pep_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
+                    uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
+                    int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap)
 {
+    if (!ctx) return PEP_ERR_ARG;
+    if (!h_row_off || (n_rows && !h_row_len) || (n_groups && (!h_grp_off || !h_grp_mode || !h_out_off)) || (out_cap && !h_out))
+        return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    if (n_groups && h_grp_off[n_groups] && !h_grp_rows) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    if (n_rows && h_row_off[n_rows] && !h_packed) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     ctx->k15_ms[0] = ctx->k15_ms[1] = ctx->k15_ms[2] = 0.;
     if (n_groups == 0) return PEP_OK;
     const GroupTables T{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows};
@@ -132,8 +140,7 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
         return PEP_OK;
     }
     DevBuf *W = ctx->ws;
-    PEP_TRY(dev_reserve(ctx, W[K15_WS_OUT], (L.pairs + 1) * 8));
-    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {}, ctx->k15_ms[0]));
+    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 8, 0}}, ctx->k15_ms[0]));
     pep_timed_stage(ctx, ctx->k15_ms[1], [&] {
         hipLaunchKernelGGL(allele_diff, dim3((unsigned)L.tiles.size()), dim3(256), 0, ctx->stream, W[K15_WS_TILES].as<const DiffTile>(), W[K15_WS_GROUPS].as<const GroupRec>(),
                            W[K15_WS_GRP_ROWS].as<const uint32_t>(), W[K15_WS_PLANE_OFF].as<const uint64_t>(), W[K15_WS_PLANES].as<const unsigned long long>(), W[K15_WS_OUT].as<int2>());
@@ -158,3 +165,14 @@ int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h
     ctx->k15_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - copy_t0).count();
     return PEP_OK;
 }
+
+int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back)
+{
+    if (!ctx || !ms_planes || !ms_pairs || !ms_copy_back) return PEP_ERR_ARG;
+    *ms_planes = ctx->k15_ms[0];
+    *ms_pairs = ctx->k15_ms[1];
+    *ms_copy_back = ctx->k15_ms[2];
+    return PEP_OK;
+}
+
+}  // extern "C"

@@ -118,12 +118,20 @@ __global__ __launch_bounds__(256) void k12_pack(uint32_t n_groups, const uint64_
     }
 }
 
+// the slots of pep_ctx::ws
+enum { K12_NT = 0, K12_NT_OFF, K12_ROWS, K12_CIGAR, K12_ROW_OFF, K12_CODES, K12_FRAME_ORF, K12_GRP_OFF, K12_GRP_QLEN, K12_PACK_OFF, K12_PACKED };
+
 }  // namespace
 
-int pep_k12_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off, uint32_t n_contigs, uint64_t n, const pep_locus *h_rows,
-                    const uint32_t *h_cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_qlen,
-                    int gtable, int64_t *h_in_frame, int64_t *h_orf, uint8_t *h_packed, uint64_t packed_cap)
+extern "C" int pep_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off, uint32_t n_contigs, uint64_t n, const pep_locus *h_rows,
+                           const uint32_t *h_cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_qlen,
+                           int gtable, int64_t *h_in_frame, int64_t *h_orf, uint8_t *h_packed, uint64_t packed_cap)
 {
+    if (!ctx || !h_nt_off || (n && (!h_rows || !h_cigar || !h_in_frame || !h_orf)) || (n_groups && (!h_grp_off || !h_grp_qlen || !h_packed))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    for (uint32_t i = 0; i < n_contigs; ++i)
+        if (h_nt_off[i + 1] < h_nt_off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
+    if (n_contigs && h_nt_off[n_contigs] && !h_nt) return PEP_ERR_ARG;
     if (n_groups == 0) {
         if (n != 0) return pep_fail(ctx, PEP_ERR_ARG, "pep_alleles: rows without groups");
         return PEP_OK;
@@ -158,40 +166,33 @@ int pep_k12_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off,
     const uint64_t nt_total = h_nt_off[n_contigs], code_total = row_off[n];
     DevBuf *W = ctx->ws;
     hipStream_t st = ctx->stream;
-    PEP_TRY(dev_reserve(ctx, W[0], nt_total + 1));
-    PEP_TRY(dev_reserve(ctx, W[1], ((size_t)n_contigs + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[2], (n + 1) * sizeof(pep_locus)));
-    PEP_TRY(dev_reserve(ctx, W[3], (n_cigar + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[4], (n + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[5], code_total + 1));
-    PEP_TRY(dev_reserve(ctx, W[6], (n + 1) * 16));
-    PEP_TRY(dev_reserve(ctx, W[7], ((size_t)n_groups + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[8], ((size_t)n_groups + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[9], ((size_t)n_groups + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[10], pack_off[n_groups] + 1));
-    PEP_TRY(pep_h2d(ctx, W[0].p, h_nt, nt_total));
-    PEP_TRY(pep_h2d(ctx, W[1].p, h_nt_off, ((size_t)n_contigs + 1) * 8));
-    PEP_TRY(pep_h2d(ctx, W[2].p, h_rows, n * sizeof(pep_locus)));
-    PEP_TRY(pep_h2d(ctx, W[3].p, h_cigar, n_cigar * 4));
-    PEP_TRY(pep_h2d(ctx, W[4].p, row_off.data(), (n + 1) * 8));        // (22 000 groups of a 50 000-exemplar genome: these tables pass the runtime's staging limit too)
-    PEP_TRY(pep_h2d(ctx, W[7].p, h_grp_off, ((size_t)n_groups + 1) * 8));
-    PEP_TRY(pep_h2d(ctx, W[8].p, h_grp_qlen, (size_t)n_groups * 4));
-    PEP_TRY(pep_h2d(ctx, W[9].p, pack_off.data(), ((size_t)n_groups + 1) * 8));
-    long long *d_frame = W[6].as<long long>(), *d_orf = W[6].as<long long>() + n;
+    // (22 000 groups of a 50 000-exemplar genome: the group tables pass the runtime's staging limit too)
+    PEP_TRY(pep_tables_to_device(ctx, W, {{K12_NT, h_nt, nt_total, 1},
+                                          {K12_NT_OFF, h_nt_off, ((size_t)n_contigs + 1) * 8, 0},
+                                          {K12_ROWS, h_rows, n * sizeof(pep_locus), sizeof(pep_locus)},
+                                          {K12_CIGAR, h_cigar, n_cigar * 4, 4},
+                                          {K12_ROW_OFF, row_off.data(), (n + 1) * 8, 0},
+                                          {K12_CODES, nullptr, code_total + 1, 0},
+                                          {K12_FRAME_ORF, nullptr, (n + 1) * 16, 0},
+                                          {K12_GRP_OFF, h_grp_off, ((size_t)n_groups + 1) * 8, 0},
+                                          {K12_GRP_QLEN, h_grp_qlen, (size_t)n_groups * 4, 4},
+                                          {K12_PACK_OFF, pack_off.data(), ((size_t)n_groups + 1) * 8, 0},
+                                          {K12_PACKED, nullptr, pack_off[n_groups] + 1, 0}}));
+    long long *d_frame = W[K12_FRAME_ORF].as<long long>(), *d_orf = W[K12_FRAME_ORF].as<long long>() + n;
     if (n) {
-        hipLaunchKernelGGL(k12_codes, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, n, W[2].as<const pep_locus>(), W[3].as<const uint32_t>(),
-                           W[0].as<const uint8_t>(), W[1].as<const uint64_t>(), W[4].as<const uint64_t>(), W[5].as<uint8_t>(), d_frame);
-        hipLaunchKernelGGL(k12_orf, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, n, W[4].as<const uint64_t>(), W[5].as<const uint8_t>(),
+        hipLaunchKernelGGL(k12_codes, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, n, W[K12_ROWS].as<const pep_locus>(), W[K12_CIGAR].as<const uint32_t>(),
+                           W[K12_NT].as<const uint8_t>(), W[K12_NT_OFF].as<const uint64_t>(), W[K12_ROW_OFF].as<const uint64_t>(), W[K12_CODES].as<uint8_t>(), d_frame);
+        hipLaunchKernelGGL(k12_orf, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, st, n, W[K12_ROW_OFF].as<const uint64_t>(), W[K12_CODES].as<const uint8_t>(),
                            gtable != 4 ? 1 : 0, d_orf);
     }
-    hipLaunchKernelGGL(k12_pack, dim3((unsigned)ceil_div(n_groups, 4)), dim3(256), 0, st, n_groups, W[7].as<const uint64_t>(), W[8].as<const uint32_t>(),
-                       W[9].as<const uint64_t>(), W[2].as<const pep_locus>(), W[4].as<const uint64_t>(), W[5].as<const uint8_t>(), W[10].as<uint8_t>());
+    hipLaunchKernelGGL(k12_pack, dim3((unsigned)ceil_div(n_groups, 4)), dim3(256), 0, st, n_groups, W[K12_GRP_OFF].as<const uint64_t>(), W[K12_GRP_QLEN].as<const uint32_t>(),
+                       W[K12_PACK_OFF].as<const uint64_t>(), W[K12_ROWS].as<const pep_locus>(), W[K12_ROW_OFF].as<const uint64_t>(), W[K12_CODES].as<const uint8_t>(), W[K12_PACKED].as<uint8_t>());
     PEP_HIP(ctx, hipGetLastError());
     if (n) {
         PEP_TRY(pep_d2h_queue(ctx, h_in_frame, d_frame, n * 8));
         PEP_TRY(pep_d2h_queue(ctx, h_orf, d_orf, n * 8));
     }
-    PEP_TRY(pep_d2h_queue(ctx, h_packed, W[10].p, pack_off[n_groups]));
+    PEP_TRY(pep_d2h_queue(ctx, h_packed, W[K12_PACKED].p, pack_off[n_groups]));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
     return PEP_OK;

@@ -1,4 +1,4 @@
-// C ABI of libpeppan_hip.so (declared in include/peppan_hip.h): context, inputs, orchestration of K1..K8.
+// C ABI of libpeppan_hip.so (declared in include/peppan_hip.h): context, inputs, search, results, pep_merge_hits.  The entry points of a kernel are in the kernel's file.
 #include "common.h"
 #include <chrono>
 #include <time.h>
@@ -35,6 +35,16 @@ int dev_reserve(pep_ctx *ctx, DevBuf &b, size_t bytes)
     const hipError_t e = b.alloc(want);
     if (e != hipSuccess) return pep_fail(ctx, PEP_ERR_HIP, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
     return PEP_OK;
+}
+
+int pep_message_out(int rc, const std::string &text, char *msg, uint64_t msg_cap)
+{
+    if (msg && msg_cap) {
+        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
+        memcpy(msg, text.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
 }
 
 int pin_reserve(pep_ctx *ctx, PinBuf &b, size_t bytes)
@@ -406,17 +416,6 @@ int download_aa(pep_ctx *ctx, const SeqSet &s, uint8_t *codes, uint64_t cap, uin
     }
     off[s.n] = pos;
     return PEP_OK;
-}
-
-// the text of a device-free table check (pep_*_check) into the caller's char[msg_cap], cut to fit; passes `rc` on
-int message_out(int rc, const std::string &text, char *msg, uint64_t msg_cap)
-{
-    if (msg && msg_cap) {
-        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
-        memcpy(msg, text.data(), k);
-        msg[k] = 0;
-    }
-    return rc;
 }
 
 }  // namespace
@@ -857,13 +856,6 @@ int pep_set_timing(pep_ctx *ctx, int level)
     return PEP_OK;
 }
 
-int pep_set_grouping(pep_ctx *ctx, uint32_t n_nodes, uint32_t q_base, const uint32_t *node_of_target, uint64_t n_targets)
-{
-    if (!ctx || (n_nodes && n_targets && !node_of_target)) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k10_set_grouping(ctx, n_nodes, q_base, node_of_target, n_targets);
-}
-
 int pep_result_labels(const pep_result *r, uint32_t *label, uint32_t n_nodes)
 {
     if (!r || (n_nodes && !label)) return PEP_ERR_ARG;
@@ -1032,189 +1024,6 @@ int pep_merge_hits(uint64_t n, const pep_hit *hits, const uint32_t *cigar, uint6
     }
     *n_out = no; *n_cigar_out = nc;
     return PEP_OK;
-}
-
-int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int64_t *out)
-{
-    if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k7_table(ctx, "pep_rescore_nt", n, hits, cigar, n_cigar, 1, nullptr, nullptr, 5, out);
-}
-
-int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
-                       const int8_t *sub, int64_t *out)
-{
-    if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k7_table(ctx, "pep_rescore_codons", n, hits, cigar, n_cigar, mode, aa_of_word, sub, 7, out);
-}
-
-int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
-                             const int8_t *sub, const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, char *msg, uint64_t msg_cap)
-{
-    std::string text;
-    const int rc = pep_k7_codons_check(n, hits, cigar, n_cigar, mode, aa_of_word, sub, q_off, n_q, r_off, n_r, text);
-    return message_out(rc, text, msg, msg_cap);
-}
-
-int pep_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *a, const uint32_t *b, uint32_t *label)
-{
-    if (!ctx || (n_nodes && !label) || (n_edges && (!a || !b))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k10_components(ctx, n_nodes, n_edges, a, b, label);
-}
-
-int pep_components_of_hits(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, const pep_hit *hits, uint32_t q_base,
-                           const uint32_t *node_of_target, uint64_t n_targets, uint32_t *label)
-{
-    if (!ctx || (n_nodes && !label) || (n_hits && (!hits || !node_of_target))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint32_t> a(n_hits + 1), b(n_hits + 1);
-    for (uint64_t h = 0; h < n_hits; ++h) {
-        if (hits[h].t >= n_targets) return pep_fail(ctx, PEP_ERR_ARG, "pep_components_of_hits: target index out of range");
-        a[h] = hits[h].q + q_base;
-        b[h] = node_of_target[hits[h].t];
-    }
-    return pep_k10_components(ctx, n_nodes, n_hits, a.data(), b.data(), label);
-}
-
-int pep_linclust(pep_ctx *ctx, const uint8_t *codes, const uint64_t *off, uint32_t n, int base, int k, int m, double min_id, double min_cov,
-                 uint32_t *rep, uint64_t *stats)
-{
-    if (!ctx || (n && (!codes || !off || !rep))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
-    return pep_k9_linclust(ctx, codes, off, n, base, k, m, min_id, min_cov, rep, stats);
-}
-
-int pep_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *contig, const int64_t *start, const int64_t *end, const int64_t *row_id,
-                 double ovl_l, double ovl_p, int64_t *out, uint64_t cap, uint64_t *n_pairs)
-{
-    if (!ctx || !n_pairs || (n && (!contig || !start || !end || !row_id)) || (cap && !out)) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k11_overlaps(ctx, n, contig, start, end, row_id, ovl_l, ovl_p, out, cap, n_pairs);
-}
-
-int pep_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *nt_off, uint32_t n_contigs, uint64_t n_rows, const pep_locus *rows,
-                const uint32_t *cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_qlen, int gtable,
-                int64_t *in_frame, int64_t *orf, uint8_t *packed, uint64_t packed_cap)
-{
-    if (!ctx || !nt_off || (n_rows && (!rows || !cigar || !in_frame || !orf)) || (n_groups && (!grp_off || !grp_qlen || !packed))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    for (uint32_t i = 0; i < n_contigs; ++i)
-        if (nt_off[i + 1] < nt_off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
-    if (n_contigs && nt_off[n_contigs] && !nt) return PEP_ERR_ARG;
-    return pep_k12_alleles(ctx, nt, nt_off, n_contigs, n_rows, rows, cigar, n_cigar, n_groups, grp_off, grp_qlen, gtable, in_frame, orf, packed, packed_cap);
-}
-
-int pep_allele_diff(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows,
-                    uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_rows, const uint8_t *grp_mode,
-                    int32_t *out, const uint64_t *out_off, uint64_t out_cap)
-{
-    if (!ctx) return PEP_ERR_ARG;
-    if (!row_off || (n_rows && !row_len) || (n_groups && (!grp_off || !grp_mode || !out_off)) || (out_cap && !out))
-        return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
-    if (n_groups && grp_off[n_groups] && !grp_rows) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
-    if (n_rows && row_off[n_rows] && !packed) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k15_allele_diff(ctx, packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_mode, out, out_off, out_cap);
-}
-
-int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back)
-{
-    if (!ctx || !ms_planes || !ms_pairs || !ms_copy_back) return PEP_ERR_ARG;
-    *ms_planes = ctx->k15_ms[0];
-    *ms_pairs = ctx->k15_ms[1];
-    *ms_copy_back = ctx->k15_ms[2];
-    return PEP_OK;
-}
-
-int pep_group_verdicts_check(const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *grp_off,
-                             const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key, const double *gd_val,
-                             uint64_t n_gd, const double *gd_default, double self_id, char *msg, uint64_t msg_cap)
-{
-    std::string text;
-    const int rc = pep_k16_check(packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_genome, grp_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, text);
-    return message_out(rc, text, msg, msg_cap);
-}
-
-int pep_group_verdicts(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,
-                       const uint64_t *grp_off, const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key,
-                       const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *verdict, pep_verdict_result **detail)
-{
-    if (!ctx) return PEP_ERR_ARG;
-    if (!detail || (n_groups && !verdict)) return pep_fail(ctx, PEP_ERR_ARG, "pep_group_verdicts: null table");
-    *detail = nullptr;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k16_group_verdicts(ctx, packed, row_off, row_len, n_rows, n_groups, grp_off, grp_rows, grp_genome, grp_inparalog, gd_key, gd_val, n_gd, gd_default, self_id,
-                                  verdict, detail);
-}
-
-int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs)
-{
-    if (!res || !n_pairs) return PEP_ERR_ARG;
-    return pep_k16_detail_size(res, g, n_pairs);
-}
-
-int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *tri, uint32_t *leader)
-{
-    if (!res) return PEP_ERR_ARG;
-    return pep_k16_detail_copy(res, g, tri, leader);
-}
-
-void pep_verdict_result_free(pep_verdict_result *res) { pep_k16_result_free(res); }
-
-int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
-    for (int k = 0; k < 4; ++k) ms[k] = ctx->k16_ms[k];
-    *bytes_to_host = ctx->k16_bytes_to_host;
-    return PEP_OK;
-}
-
-int pep_gene_ingroups_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
-                            const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, char *msg, uint64_t msg_cap)
-{
-    std::string text;
-    const int rc = pep_k17_check(genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, text);
-    return message_out(rc, text, msg, msg_cap);
-}
-
-int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
-                      const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *keep, int64_t *gene_score)
-{
-    if (!ctx) return PEP_ERR_ARG;
-    if ((n_rows && !keep) || (n_genes && !gene_score)) return pep_fail(ctx, PEP_ERR_ARG, "pep_gene_ingroups: null table");
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k17_gene_ingroups(ctx, genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, keep, gene_score);
-}
-
-int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
-    ms[0] = ctx->k17_ms[0];
-    ms[1] = ctx->k17_ms[1];
-    *bytes_to_host = ctx->k17_bytes_to_host;
-    return PEP_OK;
-}
-
-int pep_sha1(pep_ctx *ctx, const uint8_t *bytes, const uint64_t *off, uint32_t n, uint8_t *digest)
-{
-    if (!ctx || (n && (!off || !digest))) return PEP_ERR_ARG;
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
-    if (n && off[n] && !bytes) return PEP_ERR_ARG;
-    return pep_k13_sha1(ctx, bytes, off, n, digest);
-}
-
-int pep_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *len, const uint8_t *digest, uint32_t *rep)
-{
-    if (!ctx || (n && (!len || !digest || !rep))) return PEP_ERR_ARG;
-    if (n >= 0x7FFFFFFFu) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_dedup: at most 2^31 - 2 genes");
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k13_dedup(ctx, n, len, digest, rep);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <atomic>
+#include <optional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -332,6 +333,30 @@ void pep_drop_dev_result(pep_ctx *ctx);
 int dev_reserve(pep_ctx *ctx, DevBuf &b, size_t bytes);
 inline void dev_release(DevBuf &b) { b.release(); }      // the explicit early release
 
+// a table of a call for slot `slot` of a DevBuf array: bytes + pad are reserved and `bytes` uploaded from src; src == nullptr: reserved only (an output or scratch buffer)
+struct WsTable { int slot; const void *src; size_t bytes, pad; };
+// every reserve before the first upload, so that no buffer grows with a copy queued in front of it; the uploads go on the stream in the list's order
+inline int pep_tables_to_device(pep_ctx *ctx, DevBuf *W, const std::vector<WsTable> &tables)
+{
+    for (const WsTable &t : tables) PEP_TRY(dev_reserve(ctx, W[t.slot], t.bytes + t.pad));
+    for (const WsTable &t : tables)
+        if (t.src) PEP_TRY(pep_h2d(ctx, W[t.slot].p, t.src, t.bytes));
+    return PEP_OK;
+}
+
+// one kernel stage on the context's stream, its HIP-event time left in `ms` when pep_set_timing is 2
+template <class Launch>
+void pep_timed_stage(pep_ctx *ctx, double &ms, const Launch &launch)
+{
+    std::optional<EventTimer> tm;
+    if (ctx->timing_level >= 2) tm.emplace(ctx->stream);
+    launch();
+    if (tm) ms = tm->stop();
+}
+
+// the text of a device-free table check (pep_*_check) into the caller's char[msg_cap], cut to fit; passes `rc` on
+int pep_message_out(int rc, const std::string &text, char *msg, uint64_t msg_cap);
+
 // Layout of pep_ctx::d_zero: every small counter block a search needs starts from zero, and one fill at the start of the search clears
 // them all (each used to be a fill of its own in front of its kernel: eleven tiny launches per search).  A stage that runs without the
 // seed stage in front (K9 drives the alignment stage alone) finds its flag in zero_ok unset and clears its own block.
@@ -384,60 +409,11 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
 int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n_cands, const int32_t *h_min_score, pep_result *res, bool defer = false);
 int pep_extend_finish(pep_ctx *ctx);
 int pep_selftest_dpp(pep_ctx *ctx);
-// ---- rescore.hip (K7)
-// pep_rescore_nt (mode 1, no tables, width 5) and pep_rescore_codons (its mode and tables, width 7): checks, upload, k7_table<mode>, h_out[n, width]; `who` leads the messages
-int pep_k7_table(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode,
-                 const uint8_t *aa_of_word, const int8_t *sub, uint32_t width, int64_t *h_out);
-// the host checks of a table of hits, shared by pep_rescore_nt and pep_rescore_codons (`who` leads the message)
-int pep_k7_check(const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, const uint64_t *q_off, uint64_t n_q,
-                 const uint64_t *r_off, uint64_t n_r, std::string &msg);
-int pep_k7_codons_check(uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word, const int8_t *sub,
-                        const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, std::string &msg);
-// ---- unionfind.hip (K10)
-int pep_k10_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *h_a, const uint32_t *h_b, uint32_t *h_label);
-int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, const pep_hit *d_hits, uint32_t q_base, const uint32_t *h_node_of_target,
-                           uint64_t n_targets, uint32_t *h_label);
-
+// ---- what another translation unit calls of a kernel's file (an exported function is defined in the file of its kernel and declared in the public header alone)
 int pep_k7_hits_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const uint32_t *d_cigar, const uint32_t *d_n_hits = nullptr);   // K7's match counts of a search's own hits -> ctx->pin_nt_match (no wait; rescore.hip)
-int pep_k10_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const uint32_t *d_n_hits = nullptr);   // d_n_hits: the count lives on the device, n_hits bounds it       // K10 behind a search, labels -> ctx->pin_labels (no wait)
-int pep_k10_set_grouping(pep_ctx *ctx, uint32_t n_nodes, uint32_t q_base, const uint32_t *h_node_of_target, uint64_t n_targets);
-
-// ---- overlaps.hip (K11)
-int pep_k11_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *h_contig, const int64_t *h_start, const int64_t *h_end, const int64_t *h_rid,
-                     double ovl_l, double ovl_p, int64_t *h_out, uint64_t cap, uint64_t *n_pairs);
-// ---- alleles.hip (K12)
-int pep_k12_alleles(pep_ctx *ctx, const uint8_t *h_nt, const uint64_t *h_nt_off, uint32_t n_contigs, uint64_t n, const pep_locus *h_rows,
-                    const uint32_t *h_cigar, uint64_t n_cigar, uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_qlen,
-                    int gtable, int64_t *h_in_frame, int64_t *h_orf, uint8_t *h_packed, uint64_t packed_cap);
-// ---- allelediff.hip (K15)
-int pep_k15_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows,
-                        uint32_t n_groups, const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint8_t *h_grp_mode,
-                        int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap);
-// ---- divergence.hip (K16)
-int pep_k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *h_grp_off,
-                  const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
-                  const double *gd_default, double self_id, std::string &msg);      // every table check, no device
-int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
-                           const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key,
-                           const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *h_verdict, pep_verdict_result **detail);
-int pep_k16_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs);
-int pep_k16_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uint32_t *h_leader);
-void pep_k16_result_free(pep_verdict_result *res);
-// ---- ingroup.hip (K17)
-int pep_k17_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off, const uint64_t *gd_key,
-                  const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, std::string &msg);      // every table check, no device
-int pep_k17_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
-                          const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *h_keep,
-                          int64_t *h_gene_score);
-// ---- dedup.hip (K13)
-int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest);
-int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep);
-// ---- similar.hip (K14)
-int pep_k14_pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *h_rows, const uint32_t *h_cigar, uint64_t n_cigar, uint64_t n_groups,
-                         const uint64_t *h_grp_off, const uint32_t *h_qlen, const uint32_t *h_rlen, const pep_support_limits *lim, int32_t *h_value);
-// ---- linclust.hip (K9)
-int pep_k9_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, uint32_t n, int base, int k, int m, double min_id, double min_cov,
-                    uint32_t *h_rep, uint64_t *h_stats);
+int pep_k10_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const uint32_t *d_n_hits = nullptr);   // d_n_hits: the count lives on the device, n_hits bounds it       // K10 behind a search, labels -> ctx->pin_labels (no wait; unionfind.hip)
+int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, const pep_hit *d_hits, uint32_t q_base, const uint32_t *h_node_of_target,
+                           uint64_t n_targets, uint32_t *h_label);      // pep_components_of_result over a hit table that is still on the device (unionfind.hip)
 
 static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 int pep_upload_blk2seq(pep_ctx *ctx, SeqSet &s);

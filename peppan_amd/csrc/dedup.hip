@@ -126,8 +126,15 @@ __global__ void k13_table(uint32_t n, const uint32_t *__restrict__ run_excl, con
 
 }  // namespace
 
-int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest)
+extern "C" {
+
+int pep_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32_t n, uint8_t *h_digest)
 {
+    if (!ctx || (n && (!h_off || !h_digest))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_off[i + 1] < h_off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
+    if (n && h_off[n] && !h_bytes) return PEP_ERR_ARG;
     if (n == 0) return PEP_OK;
     DevBuf *W = ctx->ws;
     hipStream_t st = ctx->stream;
@@ -149,8 +156,11 @@ int pep_k13_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, ui
     return PEP_OK;
 }
 
-int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep)
+int pep_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_digest, uint32_t *h_rep)
 {
+    if (!ctx || (n && (!h_len || !h_digest || !h_rep))) return PEP_ERR_ARG;
+    if (n >= 0x7FFFFFFFu) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_dedup: at most 2^31 - 2 genes");
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return PEP_OK;
     DevBuf *W = ctx->ws;
     hipStream_t st = ctx->stream;
@@ -186,3 +196,5 @@ int pep_k13_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t
     if (n_fail) return pep_fail(ctx, PEP_ERR_INTERNAL, "pep_dedup: hash table probe failed");
     return PEP_OK;
 }
+
+}  // extern "C"

@@ -219,18 +219,28 @@ int k16_check(const GroupTables &T, const uint32_t *h_grp_genome, const uint8_t 
 
 }  // namespace
 
-int pep_k16_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *h_grp_off,
-                  const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val, uint64_t n_gd,
-                  const double *gd_default, double self_id, std::string &msg)
+extern "C" {
+
+// every table check, no device
+int pep_group_verdicts_check(const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups, const uint64_t *h_grp_off,
+                             const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key, const double *gd_val,
+                             uint64_t n_gd, const double *gd_default, double self_id, char *msg, uint64_t msg_cap)
 {
     Layout L;
-    return k16_check(GroupTables{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows}, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default, self_id, L, msg);
+    std::string text;
+    const int rc = k16_check(GroupTables{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows}, h_grp_genome, h_inparalog, gd_key, gd_val, n_gd, gd_default,
+                             self_id, L, text);
+    return pep_message_out(rc, text, msg, msg_cap);
 }
 
-int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
-                           const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key,
-                           const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *h_verdict, pep_verdict_result **detail)
+int pep_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
+                       const uint64_t *h_grp_off, const uint32_t *h_grp_rows, const uint32_t *h_grp_genome, const uint8_t *h_inparalog, const uint64_t *gd_key,
+                       const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *h_verdict, pep_verdict_result **detail)
 {
+    if (!ctx) return PEP_ERR_ARG;
+    if (!detail || (n_groups && !h_verdict)) return pep_fail(ctx, PEP_ERR_ARG, "pep_group_verdicts: null table");
+    *detail = nullptr;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     for (double &ms : ctx->k16_ms) ms = 0.;
     ctx->k16_bytes_to_host = 0;
     ++ctx->k16_serial;                                              // whatever an earlier result held on the device is about to be overwritten
@@ -254,14 +264,13 @@ int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t
         hipStream_t st = ctx->stream;
         std::vector<VGroup> dev_groups(n_groups);
         for (uint32_t g = 0; g < n_groups; ++g) dev_groups[g] = VGroup{L.groups[g].rows_off, L.groups[g].tri_off, L.groups[g].n, L.groups[g].words};
-        PEP_TRY(dev_reserve(ctx, W[K16_WS_FLAGS], (size_t)n_groups * 4));
-        PEP_TRY(dev_reserve(ctx, W[K16_WS_VERDICT], (size_t)n_groups));
-        PEP_TRY(dev_reserve(ctx, W[K16_WS_SPILL], (n_idx + 1) * 4));
         PEP_TRY(dev_reserve(ctx, ctx->k16_tri, (L.pairs + 1) * 8));
         PEP_TRY(dev_reserve(ctx, ctx->k16_leader, (n_idx + 1) * 4));
         PEP_TRY(group_tables_to_device(ctx, T, L, dev_groups.data(), (size_t)n_groups * sizeof(VGroup),
                                        {{K16_WS_GENOME, h_grp_genome, n_idx * 4, 4}, {K16_WS_EDGES, L.edges.data(), L.edges.size() * sizeof(EdgePair), sizeof(EdgePair)},
-                                        {K16_WS_GD_KEY, gd_key, n_gd * 8, 8}, {K16_WS_GD_VAL, L.gd.data(), L.gd.size() * 8, 0}}, ctx->k16_ms[0]));
+                                        {K16_WS_GD_KEY, gd_key, n_gd * 8, 8}, {K16_WS_GD_VAL, L.gd.data(), L.gd.size() * 8, 0},
+                                        {K16_WS_FLAGS, nullptr, (size_t)n_groups * 4, 0}, {K16_WS_VERDICT, nullptr, (size_t)n_groups, 0}, {K16_WS_SPILL, nullptr, (n_idx + 1) * 4, 0}},
+                                       ctx->k16_ms[0]));
         PEP_HIP(ctx, hipMemsetAsync(W[K16_WS_FLAGS].p, 0, (size_t)n_groups * 4, st));
         const GdTable gd{W[K16_WS_GD_KEY].as<const uint64_t>(), W[K16_WS_GD_VAL].as<const double>(), n_gd, self_id};
         const VGroup *d_groups = W[K15_WS_GROUPS].as<const VGroup>();
@@ -297,16 +306,18 @@ int pep_k16_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t
     return PEP_OK;
 }
 
-int pep_k16_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs)
+int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs)
 {
+    if (!res || !n_pairs) return PEP_ERR_ARG;
     if (g >= res->verdict.size()) return PEP_ERR_ARG;
     const uint64_t n = res->n[g];
     *n_pairs = res->verdict[g] == 2 ? n * (n - 1) / 2 : 0;
     return PEP_OK;
 }
 
-int pep_k16_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uint32_t *h_leader)
+int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uint32_t *h_leader)
 {
+    if (!res) return PEP_ERR_ARG;
     pep_ctx *ctx = res->ctx;
     if (g >= res->verdict.size()) return pep_fail(ctx, PEP_ERR_ARG, "pep_verdict_detail_copy: no such group");
     if (res->serial != ctx->k16_serial) return pep_fail(ctx, PEP_ERR_STATE, "pep_verdict_detail_copy: a newer pep_group_verdicts of this context has replaced the device data of this result");
@@ -320,4 +331,14 @@ int pep_k16_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri, uin
     return PEP_OK;
 }
 
-void pep_k16_result_free(pep_verdict_result *res) { delete res; }
+void pep_verdict_result_free(pep_verdict_result *res) { delete res; }
+
+int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host)
+{
+    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
+    for (int k = 0; k < 4; ++k) ms[k] = ctx->k16_ms[k];
+    *bytes_to_host = ctx->k16_bytes_to_host;
+    return PEP_OK;
+}
+
+}  // extern "C"

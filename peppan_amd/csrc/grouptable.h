@@ -5,7 +5,6 @@
 #include "common.h"
 #include "allelediff_tile.h"
 #include <initializer_list>
-#include <optional>
 
 struct GroupRec {                   // what the checker lays out per group, and the record allele_diff reads (K16's kernels read a shorter one: divergence.hip)
     uint64_t rows_off;              // first entry of the group in grp_rows (K16: also in grp_genome / leader)
@@ -107,21 +106,9 @@ int group_tables_check(const GroupTables &T, const GroupSpec &S, Check check, La
     return PEP_OK;
 }
 
-// one kernel stage on the context's stream, its HIP-event time left in `ms` when pep_set_timing is 2
-template <class Launch>
-void pep_timed_stage(pep_ctx *ctx, double &ms, const Launch &launch)
-{
-    std::optional<EventTimer> tm;
-    if (ctx->timing_level >= 2) tm.emplace(ctx->stream);
-    launch();
-    if (tm) ms = tm->stop();
-}
-
-struct WsTable { int slot; const void *src; size_t bytes, pad; };     // a host table for a workspace slot: `bytes` are uploaded, bytes + pad reserved
-
-// The device prologue of both kernels (n_groups >= 1): the tables, the layout and the caller's own tables (`more`) go to their workspace slots - every
-// reserve before the first upload, so that no buffer grows with a copy queued in front of it -, the bad-row word is cleared and allele_planes is
-// queued (its time -> ms_planes).  dev_groups: the group records as the caller's kernels read them.
+// The device prologue of both kernels (n_groups >= 1): the tables, the layout and the caller's own tables and buffers (`more`) go to their workspace
+// slots (pep_tables_to_device), the bad-row word is cleared and allele_planes is queued (its time -> ms_planes).  dev_groups: the group records as the
+// caller's kernels read them.
 inline int group_tables_to_device(pep_ctx *ctx, const GroupTables &T, const GroupLayout &L, const void *dev_groups, size_t groups_bytes,
                                   std::initializer_list<WsTable> more, double &ms_planes)
 {
@@ -130,12 +117,10 @@ inline int group_tables_to_device(pep_ctx *ctx, const GroupTables &T, const Grou
                              {K15_WS_ROW_OFF, T.row_off, (T.n_rows + 1) * 8, 0}, {K15_WS_ROW_LEN, T.row_len, T.n_rows * 4, 4},
                              {K15_WS_PLANE_OFF, L.plane_off.data(), (T.n_rows + 1) * 8, 0}, {K15_WS_GRP_ROWS, T.grp_rows, T.grp_off[T.n_groups] * 4, 4},
                              {K15_WS_GROUPS, dev_groups, groups_bytes, 0},
-                             {K15_WS_TILES, L.tiles.data(), L.tiles.size() * sizeof(DiffTile), sizeof(DiffTile)}};
+                             {K15_WS_TILES, L.tiles.data(), L.tiles.size() * sizeof(DiffTile), sizeof(DiffTile)},
+                             {K15_WS_PLANES, nullptr, (L.plane_off[T.n_rows] + 1) * 8, 0}, {K15_WS_BAD_ROW, nullptr, 256, 0}};
     put.insert(put.end(), more);
-    for (const WsTable &t : put) PEP_TRY(dev_reserve(ctx, W[t.slot], t.bytes + t.pad));
-    PEP_TRY(dev_reserve(ctx, W[K15_WS_PLANES], (L.plane_off[T.n_rows] + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[K15_WS_BAD_ROW], 256));
-    for (const WsTable &t : put) PEP_TRY(pep_h2d(ctx, W[t.slot].p, t.src, t.bytes));
+    PEP_TRY(pep_tables_to_device(ctx, W, put));
     PEP_HIP(ctx, hipMemsetAsync(W[K15_WS_BAD_ROW].p, 0xFF, 4, ctx->stream));
     if (T.n_rows)
         pep_timed_stage(ctx, ms_planes, [&] {

@@ -17,7 +17,6 @@
 // ingroup_pairs is quadratic in the rows of a gene in the worst case - many rows below thr that no seed lets in -, as the reference is.
 #include "common.h"
 #include "gdtable.h"
-#include "grouptable.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -155,17 +154,25 @@ int k17_check(const uint32_t *genome, const int32_t *iden, const int64_t *score,
 
 }  // namespace
 
-int pep_k17_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off, const uint64_t *gd_key,
-                  const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, std::string &msg)
+extern "C" {
+
+// every table check, no device
+int pep_gene_ingroups_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                            const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, char *msg, uint64_t msg_cap)
 {
     Layout L;
-    return k17_check(genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, L, msg);
+    std::string text;
+    const int rc = k17_check(genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, L, text);
+    return pep_message_out(rc, text, msg, msg_cap);
 }
 
-int pep_k17_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
-                          const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *h_keep,
-                          int64_t *h_gene_score)
+int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
+                      const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *h_keep,
+                      int64_t *h_gene_score)
 {
+    if (!ctx) return PEP_ERR_ARG;
+    if ((n_rows && !h_keep) || (n_genes && !h_gene_score)) return pep_fail(ctx, PEP_ERR_ARG, "pep_gene_ingroups: null table");
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     ctx->k17_ms[0] = ctx->k17_ms[1] = 0.;
     ctx->k17_bytes_to_host = 0;
     Layout L;
@@ -180,16 +187,12 @@ int pep_k17_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *i
     }
     DevBuf *W = ctx->k17;
     hipStream_t st = ctx->stream;
-    const WsTable put[] = {{K17_GENOME, genome, n_rows * 4, 0},          {K17_IDEN, iden, n_rows * 4, 0},
-                           {K17_SCORE, score, n_rows * 8, 0},            {K17_FIRST, L.first.data(), n_rows * 4, 0},
-                           {K17_GENE_OFF, gene_off, ((size_t)n_genes + 1) * 8, 0}, {K17_WORK, L.work.data(), L.work.size() * sizeof(IgWork), 0},
-                           {K17_GD_KEY, gd_key, n_gd * 8, 8},            {K17_GD_VAL, L.gd.data(), L.gd.size() * 8, 0}};
-    // every reserve before the first upload, so that no buffer grows with a copy queued in front of it
-    for (const WsTable &t : put) PEP_TRY(dev_reserve(ctx, W[t.slot], t.bytes + t.pad));
-    PEP_TRY(dev_reserve(ctx, W[K17_RAW], n_rows));
-    PEP_TRY(dev_reserve(ctx, W[K17_KEEP], n_rows));
-    PEP_TRY(dev_reserve(ctx, W[K17_GENE_SCORE], (size_t)n_genes * 8));
-    for (const WsTable &t : put) PEP_TRY(pep_h2d(ctx, W[t.slot].p, t.src, t.bytes));
+    PEP_TRY(pep_tables_to_device(ctx, W, {{K17_GENOME, genome, n_rows * 4, 0},          {K17_IDEN, iden, n_rows * 4, 0},
+                                          {K17_SCORE, score, n_rows * 8, 0},            {K17_FIRST, L.first.data(), n_rows * 4, 0},
+                                          {K17_GENE_OFF, gene_off, ((size_t)n_genes + 1) * 8, 0}, {K17_WORK, L.work.data(), L.work.size() * sizeof(IgWork), 0},
+                                          {K17_GD_KEY, gd_key, n_gd * 8, 8},            {K17_GD_VAL, L.gd.data(), L.gd.size() * 8, 0},
+                                          {K17_RAW, nullptr, n_rows, 0},                {K17_KEEP, nullptr, n_rows, 0},
+                                          {K17_GENE_SCORE, nullptr, (size_t)n_genes * 8, 0}}));
     PEP_HIP(ctx, hipMemsetAsync(W[K17_GENE_SCORE].p, 0, (size_t)n_genes * 8, st));
     const GdTable gd{W[K17_GD_KEY].as<const uint64_t>(), W[K17_GD_VAL].as<const double>(), n_gd, self_id};
     const IgWork *d_work = W[K17_WORK].as<const IgWork>();
@@ -216,3 +219,14 @@ int pep_k17_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *i
     ctx->k17_bytes_to_host = n_rows + 8ull * n_genes;
     return PEP_OK;
 }
+
+int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host)
+{
+    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
+    ms[0] = ctx->k17_ms[0];
+    ms[1] = ctx->k17_ms[1];
+    *bytes_to_host = ctx->k17_bytes_to_host;
+    return PEP_OK;
+}
+
+}  // extern "C"

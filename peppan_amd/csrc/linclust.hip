@@ -342,9 +342,13 @@ int k9_gapped(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, int bas
 
 }  // namespace
 
-int pep_k9_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, uint32_t n, int base, int k, int m, double min_id, double min_cov,
-                    uint32_t *h_rep, uint64_t *h_stats)
+extern "C" int pep_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, uint32_t n, int base, int k, int m, double min_id, double min_cov,
+                            uint32_t *h_rep, uint64_t *h_stats)
 {
+    if (!ctx || (n && (!h_res || !h_off || !h_rep))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_off[i + 1] < h_off[i]) return pep_fail(ctx, PEP_ERR_ARG, "offsets must be non-decreasing");
     if (n == 0) return PEP_OK;
     if (m < 1 || m > MAX_M || k < 1 || k > 32 || base < 2) return pep_fail(ctx, PEP_ERR_ARG, "pep_linclust: invalid k / m / base");
     {

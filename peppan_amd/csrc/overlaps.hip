@@ -38,12 +38,17 @@ __global__ __launch_bounds__(256) void ovl_sweep(OvlArgs a, uint64_t *__restrict
     if (!WRITE) cnt[i] = k;
 }
 
+// the slots of pep_ctx::ws
+enum { K11_CONTIG = 0, K11_START, K11_END, K11_RID, K11_CNT, K11_OFF, K11_OUT, K11_SCAN_TMP };
+
 }  // namespace
 
 // h_out receives up to cap triples (id1, id2, overlap); *n_pairs is always the full count
-int pep_k11_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *h_contig, const int64_t *h_start, const int64_t *h_end, const int64_t *h_rid,
-                     double ovl_l, double ovl_p, int64_t *h_out, uint64_t cap, uint64_t *n_pairs)
+extern "C" int pep_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *h_contig, const int64_t *h_start, const int64_t *h_end, const int64_t *h_rid,
+                            double ovl_l, double ovl_p, int64_t *h_out, uint64_t cap, uint64_t *n_pairs)
 {
+    if (!ctx || !n_pairs || (n && (!h_contig || !h_start || !h_end || !h_rid)) || (cap && !h_out)) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     *n_pairs = 0;
     if (n == 0) return PEP_OK;
     for (uint64_t i = 1; i < n; ++i) {
@@ -52,31 +57,23 @@ int pep_k11_overlaps(pep_ctx *ctx, uint64_t n, const int32_t *h_contig, const in
     }
     hipStream_t st = ctx->stream;
     DevBuf *W = ctx->ws;
-    PEP_TRY(dev_reserve(ctx, W[0], n * 4));
-    PEP_TRY(dev_reserve(ctx, W[1], n * 8));
-    PEP_TRY(dev_reserve(ctx, W[2], n * 8));
-    PEP_TRY(dev_reserve(ctx, W[3], n * 8));
-    PEP_TRY(dev_reserve(ctx, W[4], (n + 2) * 8));
-    PEP_TRY(dev_reserve(ctx, W[5], (n + 2) * 8));
-    PEP_TRY(pep_h2d(ctx, W[0].p, h_contig, n * 4));
-    PEP_TRY(pep_h2d(ctx, W[1].p, h_start, n * 8));
-    PEP_TRY(pep_h2d(ctx, W[2].p, h_end, n * 8));
-    PEP_TRY(pep_h2d(ctx, W[3].p, h_rid, n * 8));
+    PEP_TRY(pep_tables_to_device(ctx, W, {{K11_CONTIG, h_contig, n * 4, 0}, {K11_START, h_start, n * 8, 0}, {K11_END, h_end, n * 8, 0}, {K11_RID, h_rid, n * 8, 0},
+                                          {K11_CNT, nullptr, (n + 2) * 8, 0}, {K11_OFF, nullptr, (n + 2) * 8, 0}}));
     OvlArgs a;
-    a.contig = W[0].as<const int32_t>(); a.start = W[1].as<const int64_t>(); a.end = W[2].as<const int64_t>(); a.rid = W[3].as<const int64_t>();
+    a.contig = W[K11_CONTIG].as<const int32_t>(); a.start = W[K11_START].as<const int64_t>(); a.end = W[K11_END].as<const int64_t>(); a.rid = W[K11_RID].as<const int64_t>();
     a.n = n; a.ovl_l = ovl_l; a.ovl_p = ovl_p;
     const unsigned g = (unsigned)ceil_div(n, 256);
-    hipLaunchKernelGGL(ovl_sweep<false>, dim3(g), dim3(256), 0, st, a, W[4].as<uint64_t>(), (const uint64_t *)nullptr, (int64_t *)nullptr);
-    PEP_TRY(pep_scan_u64(ctx, W[4].as<uint64_t>(), W[5].as<uint64_t>(), n, W[7]));
+    hipLaunchKernelGGL(ovl_sweep<false>, dim3(g), dim3(256), 0, st, a, W[K11_CNT].as<uint64_t>(), (const uint64_t *)nullptr, (int64_t *)nullptr);
+    PEP_TRY(pep_scan_u64(ctx, W[K11_CNT].as<uint64_t>(), W[K11_OFF].as<uint64_t>(), n, W[K11_SCAN_TMP]));
     uint64_t total = 0;
-    PEP_HIP(ctx, hipMemcpyAsync(&total, W[5].as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    PEP_HIP(ctx, hipMemcpyAsync(&total, W[K11_OFF].as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     *n_pairs = total;
     if (total == 0 || total > cap) return PEP_OK;          // caller re-calls with a buffer of *n_pairs triples
-    PEP_TRY(dev_reserve(ctx, W[6], total * 24));
-    hipLaunchKernelGGL(ovl_sweep<true>, dim3(g), dim3(256), 0, st, a, (uint64_t *)nullptr, (const uint64_t *)W[5].as<uint64_t>(), W[6].as<int64_t>());
+    PEP_TRY(dev_reserve(ctx, W[K11_OUT], total * 24));
+    hipLaunchKernelGGL(ovl_sweep<true>, dim3(g), dim3(256), 0, st, a, (uint64_t *)nullptr, (const uint64_t *)W[K11_OFF].as<uint64_t>(), W[K11_OUT].as<int64_t>());
     PEP_HIP(ctx, hipGetLastError());
-    PEP_TRY(pep_d2h_queue(ctx, h_out, W[6].p, total * 24));
+    PEP_TRY(pep_d2h_queue(ctx, h_out, W[K11_OUT].p, total * 24));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
     return PEP_OK;

@@ -8,7 +8,7 @@
 //   wave_sum               the xor-shuffle sum over the wavefront
 //   k7_table<MODE>         a table of hits: MODE 1 = match walk, 2 + 3 counts per hit; MODE 2 / 3 = the codon grid (uberBlast.py:250-269), 4 + 3 counts
 //   k7_hits<TOOL>          the match walk over the hits of a search where they lie, bounded by a count on the device, one uint32 per hit
-//   pep_k7_table           the one host call behind pep_rescore_nt and pep_rescore_codons
+//   k7_rescore             the one host call behind pep_rescore_nt and pep_rescore_codons
 // Mode 1 scans 2 x aligned length bytes per hit; the sequences of a search (tens of MB) stay in the L2 / Infinity Cache, so what bounds it is the latency of
 // the byte loads, not HBM bandwidth.  Tried in round 2 and dropped: 16 columns per lane and trip through unaligned 16-byte loads (+ a byte-swapped window
 // for reverse-strand hits) - 2 to 2.7x SLOWER (216 - 290 us instead of 107 us per call on the mapping workload of tools/other_kernels.py): the unaligned
@@ -82,7 +82,7 @@ __device__ __forceinline__ HitStart k7_start(const pep_hit &hit, const uint32_t 
 }
 
 // the lane's share of the hit's identical columns.  32 bits hold it, and the sum over the wavefront: the M columns of a table row are at most its reference
-// range, rhi - rlo + 1 <= 2^32 - 1 of uint32 coordinates with rlo >= 1 (pep_k7_check); a search's hit aligns packed sequences of at most PEP_MAX_SEQ_LEN = 2^23 - 256 residues, of 3 bases at the most
+// range, rhi - rlo + 1 <= 2^32 - 1 of uint32 coordinates with rlo >= 1 (k7_check); a search's hit aligns packed sequences of at most PEP_MAX_SEQ_LEN = 2^23 - 256 residues, of 3 bases at the most
 __device__ __forceinline__ uint32_t k7_match_columns(const HitStart &s, int lane)
 {
     const uint8_t *q = s.q, *r = s.r;
@@ -240,8 +240,8 @@ int pep_k7_hits_queue(pep_ctx *ctx, uint64_t n, const pep_hit *d_hits, const uin
 
 // what both entry points hold a table of hits to before anything is uploaded, so that a bad table is an error, not an out-of-bounds read: indices,
 // CIGAR slices, op codes, and coordinates that agree with the runs and lie inside the two sequences (q_off / r_off: offsets of the nucleotide sets)
-int pep_k7_check(const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, const uint64_t *q_off, uint64_t n_q,
-                 const uint64_t *r_off, uint64_t n_r, std::string &msg)
+static int k7_check(const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, const uint64_t *q_off, uint64_t n_q,
+                    const uint64_t *r_off, uint64_t n_r, std::string &msg)
 {
     for (uint64_t i = 0; i < n; ++i) {
         const pep_nt_hit &h = h_hits[i];
@@ -273,25 +273,27 @@ static int k7_codons_check_tables(int32_t mode, const uint8_t *aa_of_word, const
     return PEP_OK;
 }
 
-int pep_k7_codons_check(uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word, const int8_t *sub,
-                        const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, std::string &msg)
+// every check of pep_rescore_codons, no device
+static int k7_codons_check(uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word, const int8_t *sub,
+                           const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, std::string &msg)
 {
     const int rc = k7_codons_check_tables(mode, aa_of_word, sub, msg);
     if (rc != PEP_OK || n == 0) return rc;
     if (!h_hits || !h_cigar || !q_off || !r_off) { msg = "pep_rescore_codons: NULL table"; return PEP_ERR_ARG; }
-    return pep_k7_check("pep_rescore_codons", n, h_hits, h_cigar, n_cigar, q_off, n_q, r_off, n_r, msg);
+    return k7_check("pep_rescore_codons", n, h_hits, h_cigar, n_cigar, q_off, n_q, r_off, n_r, msg);
 }
 
+// pep_rescore_nt (mode 1, no tables, width 5) and pep_rescore_codons (its mode and tables, width 7): checks, upload, k7_table<mode>, h_out[n, width]; `who` leads the messages.
 // width 5: mode is 1 and no table is read.  width 7: the mode and the tables are the caller's and are judged first, also for n == 0 and before the state.
-int pep_k7_table(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode,
-                 const uint8_t *aa_of_word, const int8_t *sub, uint32_t width, int64_t *h_out)
+static int k7_rescore(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode,
+                      const uint8_t *aa_of_word, const int8_t *sub, uint32_t width, int64_t *h_out)
 {
     std::string msg;
     int rc = width == 7 ? k7_codons_check_tables(mode, aa_of_word, sub, msg) : PEP_OK;
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
     if (n == 0) return PEP_OK;
     if (!ctx->q_nt.nt.p || !ctx->r_nt.nt.p) return pep_fail(ctx, PEP_ERR_STATE, std::string(who) + " needs pep_set_query_nt and pep_set_ref_nt first");
-    rc = pep_k7_check(who, n, h_hits, h_cigar, n_cigar, ctx->q_nt.h_off.data(), ctx->q_nt.n, ctx->r_nt.h_off.data(), ctx->r_nt.n, msg);
+    rc = k7_check(who, n, h_hits, h_cigar, n_cigar, ctx->q_nt.h_off.data(), ctx->q_nt.n, ctx->r_nt.h_off.data(), ctx->r_nt.n, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
     PEP_TRY(dev_reserve(ctx, ctx->ws[0], n * sizeof(pep_nt_hit)));
     PEP_TRY(dev_reserve(ctx, ctx->ws[1], (n_cigar + 1) * 4));
@@ -313,3 +315,30 @@ int pep_k7_table(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_
     pep_d2h_finish(ctx);
     return PEP_OK;
 }
+
+extern "C" {
+
+int pep_rescore_nt(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int64_t *out)
+{
+    if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return k7_rescore(ctx, "pep_rescore_nt", n, hits, cigar, n_cigar, 1, nullptr, nullptr, 5, out);
+}
+
+int pep_rescore_codons(pep_ctx *ctx, uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
+                       const int8_t *sub, int64_t *out)
+{
+    if (!ctx || (n && (!hits || !cigar || !out))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return k7_rescore(ctx, "pep_rescore_codons", n, hits, cigar, n_cigar, mode, aa_of_word, sub, 7, out);
+}
+
+int pep_rescore_codons_check(uint64_t n, const pep_nt_hit *hits, const uint32_t *cigar, uint64_t n_cigar, int32_t mode, const uint8_t *aa_of_word,
+                             const int8_t *sub, const uint64_t *q_off, uint64_t n_q, const uint64_t *r_off, uint64_t n_r, char *msg, uint64_t msg_cap)
+{
+    std::string text;
+    const int rc = k7_codons_check(n, hits, cigar, n_cigar, mode, aa_of_word, sub, q_off, n_q, r_off, n_r, text);
+    return pep_message_out(rc, text, msg, msg_cap);
+}
+
+}  // extern "C"

@@ -210,8 +210,8 @@ __global__ __launch_bounds__(64) void k14_pair_support(SupportArgs a)
 
 }  // namespace
 
-int pep_k14_pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *h_rows, const uint32_t *h_cigar, uint64_t n_cigar, uint64_t n_groups,
-                         const uint64_t *h_grp_off, const uint32_t *h_qlen, const uint32_t *h_rlen, const pep_support_limits *lim, int32_t *h_value)
+static int pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *h_rows, const uint32_t *h_cigar, uint64_t n_cigar, uint64_t n_groups,
+                        const uint64_t *h_grp_off, const uint32_t *h_qlen, const uint32_t *h_rlen, const pep_support_limits *lim, int32_t *h_value)
 {
     if (n_groups == 0) return PEP_OK;
     if (n_groups > 0x7FFFFFFFull) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_pair_support: more than 2^31 - 1 groups");
@@ -280,7 +280,7 @@ int pep_pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *rows,
 {
     if (!ctx || !lim || (n_groups && (!grp_off || !grp_qlen || !grp_rlen || !value)) || (n_rows && !rows) || (n_cigar && !cigar)) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return pep_k14_pair_support(ctx, n_rows, rows, cigar, n_cigar, n_groups, grp_off, grp_qlen, grp_rlen, lim, value);
+    return pair_support(ctx, n_rows, rows, cigar, n_cigar, n_groups, grp_off, grp_qlen, grp_rlen, lim, value);
 }
 
 // Host side, no context.  Rows in the order of the table RunBlast.run returns (query, reference, score).  q / r: gene codes in

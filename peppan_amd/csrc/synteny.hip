@@ -16,7 +16,6 @@
 // Integers only, plain vector stores, no LDS: the lists of a group of 4 000 members are 100 KB and stay in L2.  What bounds it: a row is one
 // wavefront's, so a group's longest row (n - 1 pairs) is serial in chunks of 64, and a tiny group fills one lane per pair.
 #include "common.h"
-#include "grouptable.h"
 #include "../../include/peppan_synteny.h"
 #include <algorithm>
 #include <cstring>
@@ -222,16 +221,6 @@ struct Layout {
 
 const char *const K18_ME = "pep_synteny_pairs: ";
 
-int text_out(int rc, const std::string &text, char *msg, uint64_t msg_cap)
-{
-    if (msg && msg_cap) {
-        const size_t k = std::min<size_t>(text.size(), (size_t)msg_cap - 1);
-        memcpy(msg, text.data(), k);
-        msg[k] = 0;
-    }
-    return rc;
-}
-
 // every check of the tables, on the host, before anything is launched; also makes the layout of the counters
 int k18_check(uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb, uint64_t n_nb,
               int32_t n_neighbor, Layout &L, std::string &msg)
@@ -296,21 +285,14 @@ int k18_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const
     DevBuf *W = ctx->k18;
     hipStream_t st = ctx->stream;
     const uint64_t n_cnt = L.cnt_base[n_groups];
-    const WsTable put[] = {{K18_MEMBER_OFF, member_off, ((size_t)n_groups + 1) * 8, 0}, {K18_GRP_OF, L.grp_of.data(), n_members * 4, 0},
-                           {K18_GENOME, genome, n_members * 4, 0},                     {K18_NB_OFF, nb_off, (n_members + 1) * 8, 0},
-                           {K18_NB, nb, n_nb * 4, 4},                                  {K18_CNT_BASE, L.cnt_base.data(), ((size_t)n_groups + 1) * 8, 0},
-                           {K18_SMAX, L.smax.data(), (size_t)n_groups * 4, 0}};
-    // every reserve before the first upload, so that no buffer grows with a copy queued in front of it
-    for (const WsTable &t : put) PEP_TRY(dev_reserve(ctx, W[t.slot], t.bytes + t.pad));
-    PEP_TRY(dev_reserve(ctx, W[K18_DC], (size_t)n_groups * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_CNT], (n_cnt + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_POS], (n_cnt + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_CONF_CNT], (n_members + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_CONF_POS], (n_members + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_WALK_OFF], ((size_t)n_groups + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_CONF_OFF], ((size_t)n_groups + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[K18_FAULT], 4));
-    for (const WsTable &t : put) PEP_TRY(pep_h2d(ctx, W[t.slot].p, t.src, t.bytes));
+    PEP_TRY(pep_tables_to_device(ctx, W, {{K18_MEMBER_OFF, member_off, ((size_t)n_groups + 1) * 8, 0}, {K18_GRP_OF, L.grp_of.data(), n_members * 4, 0},
+                                          {K18_GENOME, genome, n_members * 4, 0},                     {K18_NB_OFF, nb_off, (n_members + 1) * 8, 0},
+                                          {K18_NB, nb, n_nb * 4, 4},                                  {K18_CNT_BASE, L.cnt_base.data(), ((size_t)n_groups + 1) * 8, 0},
+                                          {K18_SMAX, L.smax.data(), (size_t)n_groups * 4, 0},         {K18_DC, nullptr, (size_t)n_groups * 4, 0},
+                                          {K18_CNT, nullptr, (n_cnt + 1) * 4, 0},                     {K18_POS, nullptr, (n_cnt + 1) * 4, 0},
+                                          {K18_CONF_CNT, nullptr, (n_members + 1) * 4, 0},            {K18_CONF_POS, nullptr, (n_members + 1) * 4, 0},
+                                          {K18_WALK_OFF, nullptr, ((size_t)n_groups + 1) * 4, 0},     {K18_CONF_OFF, nullptr, ((size_t)n_groups + 1) * 4, 0},
+                                          {K18_FAULT, nullptr, 4, 0}}));
     PEP_HIP(ctx, hipMemsetAsync(W[K18_DC].p, 0xFF, (size_t)n_groups * 4, st));
     PEP_HIP(ctx, hipMemsetAsync(W[K18_CNT].p, 0, (n_cnt + 1) * 4, st));
     PEP_HIP(ctx, hipMemsetAsync(W[K18_CONF_CNT].p, 0, (n_members + 1) * 4, st));
@@ -395,7 +377,7 @@ int pep_synteny_pairs_check(uint32_t n_groups, const uint64_t *member_off, const
     Layout L;
     std::string text;
     const int rc = k18_check(n_groups, member_off, genome, n_members, nb_off, nb, n_nb, n_neighbor, L, text);
-    return text_out(rc, text, msg, msg_cap);
+    return pep_message_out(rc, text, msg, msg_cap);
 }
 
 int pep_synteny_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb,
@@ -438,7 +420,7 @@ int pep_synteny_pairs_times(const pep_ctx *ctx, double ms[3], uint64_t *bytes_to
 int pep_synteny_walk(uint32_t n_groups, const uint64_t *member_off, const uint64_t *conf_off, const uint32_t *conf, const uint64_t *walk_off, const uint32_t *walk,
                      uint8_t *verdict, uint32_t *n_comp, uint32_t *comp_root, uint32_t *comp_len, uint32_t *members, char *msg, uint64_t msg_cap)
 {
-    const auto bad = [&](const std::string &text) { return text_out(PEP_ERR_ARG, "pep_synteny_walk: " + text, msg, msg_cap); };
+    const auto bad = [&](const std::string &text) { return pep_message_out(PEP_ERR_ARG, "pep_synteny_walk: " + text, msg, msg_cap); };
     if (!member_off || !conf_off || !walk_off || (n_groups && (!verdict || !n_comp))) return bad("null table");
     if (member_off[0] != 0 || conf_off[0] != 0 || walk_off[0] != 0) return bad("offsets must start at 0");
     for (uint32_t g = 0; g < n_groups; ++g)
@@ -524,7 +506,7 @@ int pep_synteny_walk(uint32_t n_groups, const uint64_t *member_off, const uint64
         }
         n_comp[g] = comps;
     }
-    return text_out(PEP_OK, "", msg, msg_cap);
+    return pep_message_out(PEP_OK, "", msg, msg_cap);
 }
 
 }  // extern "C"

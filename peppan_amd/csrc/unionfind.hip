@@ -62,7 +62,8 @@ __global__ __launch_bounds__(256) void uf_flatten(uint32_t *parent, uint32_t *__
 
 }  // namespace
 
-int pep_k10_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *h_a, const uint32_t *h_b, uint32_t *h_label)
+// the body of pep_components and pep_components_of_hits: the edge columns are on the host
+static int k10_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *h_a, const uint32_t *h_b, uint32_t *h_label)
 {
     if (n_nodes == 0) return PEP_OK;
     for (uint64_t e = 0; e < n_edges; ++e)
@@ -145,8 +146,33 @@ int pep_k10_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const ui
     return PEP_OK;
 }
 
-int pep_k10_set_grouping(pep_ctx *ctx, uint32_t n_nodes, uint32_t q_base, const uint32_t *h_node_of_target, uint64_t n_targets)
+extern "C" {
+
+int pep_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, const uint32_t *a, const uint32_t *b, uint32_t *label)
 {
+    if (!ctx || (n_nodes && !label) || (n_edges && (!a || !b))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    return k10_components(ctx, n_nodes, n_edges, a, b, label);
+}
+
+int pep_components_of_hits(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, const pep_hit *hits, uint32_t q_base,
+                           const uint32_t *node_of_target, uint64_t n_targets, uint32_t *label)
+{
+    if (!ctx || (n_nodes && !label) || (n_hits && (!hits || !node_of_target))) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> a(n_hits + 1), b(n_hits + 1);
+    for (uint64_t h = 0; h < n_hits; ++h) {
+        if (hits[h].t >= n_targets) return pep_fail(ctx, PEP_ERR_ARG, "pep_components_of_hits: target index out of range");
+        a[h] = hits[h].q + q_base;
+        b[h] = node_of_target[hits[h].t];
+    }
+    return k10_components(ctx, n_nodes, n_hits, a.data(), b.data(), label);
+}
+
+int pep_set_grouping(pep_ctx *ctx, uint32_t n_nodes, uint32_t q_base, const uint32_t *h_node_of_target, uint64_t n_targets)
+{
+    if (!ctx || (n_nodes && n_targets && !h_node_of_target)) return PEP_ERR_ARG;
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
     ctx->grp_nodes = 0;
     if (n_nodes == 0) return PEP_OK;
     if (ctx->uf_nodes_host.size() != n_targets || (n_targets && memcmp(ctx->uf_nodes_host.data(), h_node_of_target, n_targets * 4) != 0)) {
@@ -163,3 +189,5 @@ int pep_k10_set_grouping(pep_ctx *ctx, uint32_t n_nodes, uint32_t q_base, const 
     ctx->grp_q_base = q_base;
     return PEP_OK;
 }
+
+}  // extern "C"

@@ -79,6 +79,22 @@ def test_direct_callers_get_the_full_return_width():
     assert lib.pep_crc32(N._ptr(data), len(data), 0) == zlib.crc32(data.tobytes())
 
 
+HANDLE_FIRST = ['pep_rescore_nt', 'pep_rescore_codons', 'pep_components', 'pep_components_of_hits', 'pep_set_grouping', 'pep_linclust', 'pep_overlaps', 'pep_alleles',
+                'pep_sha1', 'pep_dedup', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_verdict_detail_size', 'pep_verdict_detail_copy',
+                'pep_group_verdicts_times', 'pep_gene_ingroups', 'pep_gene_ingroups_times']
+
+
+def test_null_handle_is_an_argument_error():
+    """every entry point of K7 and K9 - K17 that takes a pep_ctx * or a pep_verdict_result * first answers a null one with PEP_ERR_ARG, whatever else it is given: the
+    check of the handle comes before anything that would need a device"""
+    from peppan_amd import _native as N
+    lib = N.load_library()
+    for name in HANDLE_FIRST:
+        restype, *argtypes = N.SIGNATURES[name]
+        assert restype is C.c_int and argtypes[0] is C.c_void_p, name
+        assert getattr(lib, name)(*[None if t is C.c_void_p else t(0) for t in argtypes]) == -2, name          # PEP_ERR_ARG
+
+
 def test_struct_layouts_match_header(tmp_path):
     """sizes and field offsets of every struct that crosses the boundary, taken from the header by a C compiler, equal the ctypes / numpy
     mirrors in peppan_amd/_native.py"""

@@ -34,7 +34,7 @@ def say(text):
 
 def code_id():
     h = hashlib.sha1()
-    for f in ('peppan_amd/csrc/allelediff.hip', 'peppan_amd/csrc/capi.hip', 'peppan_amd/_native.py', 'peppan_amd/orthofilter.py'):
+    for f in ('peppan_amd/csrc/allelediff.hip', 'peppan_amd/csrc/grouptable.h', 'peppan_amd/csrc/common.h', 'peppan_amd/_native.py', 'peppan_amd/orthofilter.py'):
         with open(os.path.join(ROOT, f), 'rb') as src:
             h.update(src.read())
     try:
@@ -43,7 +43,7 @@ def code_id():
         head = 'commit %s%s' % (head, ' + uncommitted changes' if dirty else '')
     except Exception:
         head = 'tree without git metadata'
-    return '%s, sources of the stage (allelediff.hip capi.hip _native.py orthofilter.py) sha1 %s' % (head, h.hexdigest()[:12])
+    return '%s, sources of the stage (allelediff.hip grouptable.h common.h _native.py orthofilter.py) sha1 %s' % (head, h.hexdigest()[:12])
 
 
 def median_wall(fn, repeats):

@@ -17,7 +17,7 @@ from peppan_amd import _native as N, orthofilter as OF                     # noq
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
 n_genes = int(sys.argv[2]) if len(sys.argv) > 2 else 10000
 GENOMES, SELF_ID, SIGMA, THR = 500, 0.005, 3., (0.9 - 0.02) * 10000
-SOURCES = ('peppan_amd/csrc/ingroup.hip', 'peppan_amd/csrc/gdtable.h', 'peppan_amd/csrc/capi.hip', 'peppan_amd/_native.py')
+SOURCES = ('peppan_amd/csrc/ingroup.hip', 'peppan_amd/csrc/gdtable.h', 'peppan_amd/csrc/common.h', 'peppan_amd/_native.py')
 lines = []
 
 

@@ -17,7 +17,7 @@ from peppan_amd import _native as N, synteny as SY                         # noq
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
 GENOMES = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
 SMALL, NN = 3000, 2
-SOURCES = ('peppan_amd/csrc/synteny.hip', 'peppan_amd/csrc/scan.hip', 'peppan_amd/synteny.py', 'peppan_amd/_native.py')
+SOURCES = ('peppan_amd/csrc/synteny.hip', 'peppan_amd/csrc/scan.hip', 'peppan_amd/csrc/common.h', 'peppan_amd/synteny.py', 'peppan_amd/_native.py')
 lines = []
 
 
