@@ -119,6 +119,18 @@ SYNTENY_SIGNATURES = {
     'pep_synteny_walk': (I, U32, P, P, P, P, P, P, P, P, P, P, P, U64),
 }
 
+# ... and of include/peppan_genestruct.h (K19), likewise a header with a version of its own; tests/test_genestruct_host.py holds this table to it
+GENESTRUCT_ABI_VERSION = 1
+GENESTRUCT_MAX_WINDOW = 1 << 31          # PEP_GENESTRUCT_MAX_WINDOW: a window holds fewer nucleotides than this
+GENESTRUCT_NO_STOP = 0xFFFFFFFF          # PEP_GENESTRUCT_NO_STOP: stop_aa of a frame without a stop codon
+GENESTRUCT_KINDS = ('CDS', 'nostart', 'nostop', 'premature_stop')      # PEP_GENESTRUCT_CDS .. PEP_GENESTRUCT_PREMATURE
+GENESTRUCT_SIGNATURES = {
+    'pep_genestruct_version': (I,),
+    'pep_gene_structure': (I, P, P, P, U32, U32, P, P, P, P, P, P, P, I, P, P, P, P),
+    'pep_gene_structure_check': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64),
+    'pep_gene_structure_times': (I, P, P, P, P),
+}
+
 
 class PepError(RuntimeError):
     pass
@@ -207,7 +219,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()):
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()) + list(GENESTRUCT_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -216,6 +228,8 @@ def load_library():
         raise PepError('libpeppan_hip.so ABI version mismatch')
     if lib.pep_synteny_version() != SYNTENY_ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch (peppan_synteny.h)')
+    if lib.pep_genestruct_version() != GENESTRUCT_ABI_VERSION:
+        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_genestruct.h)')
     _lib = lib
     return lib
 
@@ -528,6 +542,38 @@ def synteny_walk(member_off, conf_off, conf, walk_off, walk):
         cuts = np.cumsum(comp_len[lo:lo + int(n_comp[g])])[:-1]
         comps.append(list(zip(comp_root[lo:lo + int(n_comp[g])].tolist(), np.split(members[lo:int(member_off[g + 1])].astype(np.int64), cuts))))
     return verdict[:n_groups], comps
+
+
+def _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len):
+    """the tables of one pep_gene_structure / pep_gene_structure_check call as the library's types -> (arguments behind the nucleotides, n_pred, what
+    keeps them alive).  Values that do not fit their column raise ValueError here: ctypes and numpy would cut them silently"""
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64).reshape(-1)
+    if len(seq_off) < 1:
+        raise ValueError('gene_structure: seq_off needs one entry more than there are sequences')
+    cols = []
+    for name, col, dtype in (('seq', seq, np.uint32), ('win_off', win_off, np.uint64), ('win_len', win_len, np.uint32), ('flags', flags, np.uint8), ('lp', lp, np.uint32),
+                             ('allowed_vary', allowed_vary, np.uint32), ('ref_len', ref_len, np.uint32)):
+        a = np.asarray(col).reshape(-1)
+        if a.dtype != dtype:
+            if len(a) and a.dtype.kind not in 'iu':
+                raise ValueError('gene_structure: %s must hold integers' % name)
+            if len(a) and (int(a.min()) < 0 or int(a.max()) > np.iinfo(dtype).max):
+                raise ValueError('gene_structure: %s holds values outside [0, %d]' % (name, np.iinfo(dtype).max))
+            a = a.astype(dtype)
+        cols.append(np.ascontiguousarray(a))
+    n_pred = len(cols[0])
+    if any(len(c) != n_pred for c in cols):
+        raise ValueError('gene_structure: one entry per prediction in each of the seven columns')
+    if n_pred >= 1 << 32 or len(seq_off) - 1 >= 1 << 32:
+        raise ValueError('gene_structure: more than 2^32 - 1 predictions or sequences in one call')
+    keep = [seq_off] + [_some(c) for c in cols]
+    return [_ptr(keep[0]), len(seq_off) - 1, n_pred] + [_ptr(c) for c in keep[1:]], n_pred, keep
+
+
+def gene_structure_check(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len):
+    """the host checks of pep_gene_structure alone (no context, no device, the nucleotides are not read): PepError with the library's code and text, else None"""
+    args, _, keep = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
+    _check_only('pep_gene_structure_check', *args)
 
 
 def codon_tables(table_id=11):
@@ -1555,6 +1601,29 @@ class Context(object):
         ms, moved = (C.c_double * 3)(), C.c_uint64()
         self._call('pep_synteny_pairs_times', ms, C.byref(moved))
         return np.array(list(ms)), int(moved.value)
+
+    # ---- K19
+    def gene_structure(self, nt, seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len, table4=False):
+        """determineGeneStructure (PEPPAN.py:1193-1229) for a batch of predictions.  nt: the nucleotide set as ASCII bytes (bytes or uint8 array), sequence i
+        at nt[seq_off[i] .. seq_off[i+1]].  Prediction p reads win_len[p] nucleotides from the 0-based win_off[p] of sequence seq[p]; flags[p]: bit 0 = read
+        backward and complemented, bits 1-3 = the tried frames 0, 1, 2.  table4: TGA is no stop.
+        -> (frame int32[n]: the lowest tried frame that is a CDS or -1; start_aa, stop_aa uint32[n]: of that frame, of the first tried one when there is
+        none, GENESTRUCT_NO_STOP without a stop; kind uint8[n]: the outcome of the first tried frame, an index of GENESTRUCT_KINDS), as
+        include/peppan_genestruct.h states them"""
+        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        args, n, keep_alive = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
+        if len(nt) != int(keep_alive[0][-1]):
+            raise ValueError('gene_structure: seq_off must end at the length of nt')
+        frame, kind = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        start_aa, stop_aa = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        self._call('pep_gene_structure', _ptr(_some(nt)), *args, 1 if table4 else 0, _ptr(frame), _ptr(start_aa), _ptr(stop_aa), _ptr(kind))
+        return frame[:n], start_aa[:n], stop_aa[:n], kind[:n]
+
+    def gene_structure_times(self):
+        """of the newest pep_gene_structure: (kernel time in ms when set_timing(2) is on, else 0; bytes it sent to the device; bytes it sent to the host)"""
+        ms, up, down = C.c_double(), C.c_uint64(), C.c_uint64()
+        self._call('pep_gene_structure_times', C.byref(ms), C.byref(up), C.byref(down))
+        return float(ms.value), int(up.value), int(down.value)
 
     # ---- K13
     def sha1(self, seqs):

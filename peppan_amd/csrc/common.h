@@ -263,6 +263,9 @@ struct pep_ctx {
     uint64_t k18_bytes_to_host = 0;          // ... and what it and its pep_synteny_pairs_copy sent to the host
     uint64_t k18_n_conf = 0, k18_n_walk = 0; // the pairs its two lists hold, waiting on the device for pep_synteny_pairs_copy
     DevBuf k18[18];                          // grow-only: its tables, counters and the two lists (the slots: synteny.hip)
+    double k19_ms = 0.;                      // the newest pep_gene_structure: kernel time when pep_set_timing is 2 (genestruct.hip)
+    uint64_t k19_bytes_to_device = 0, k19_bytes_to_host = 0;   // ... and what it sent each way
+    DevBuf k19[5];                           // grow-only: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
