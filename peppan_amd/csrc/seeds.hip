@@ -696,22 +696,23 @@ __global__ __launch_bounds__(256) void seed_match_stride(JoinArgs a)
 // predicated residues: as long as ONE lane of a wavefront was extending all of it was issued - 1 100 scalar and 650 vector instructions
 // per wavefront and slice (SQ_INSTS_SALU 44.6 M against SQ_INSTS_VALU 26.2 M per launch at 10 k genes), most of them for the one or two
 // lanes whose extension went beyond its first sixteen residues.
-struct XDrop { int s, best, live, pass; };      // live / pass: 0 or 1
-// one residue pair, for every lane and without a branch: the state of a lane that is not extending (on = 0) does not change.
-//   s = running score, best = its maximum so far, base = what the other side of the seed has secured (0 on the right side)
-//   pass: base + best reached the threshold;  an extension ends when it passes or falls more than xdrop below its best
-__device__ __forceinline__ void xdrop_step(XDrop &x, int sc, int on, int base, int thr, int xdrop)
+// The x-drop state a lane carries from block to block: s = running score, best = its maximum so far (s <= best at all times).  What decides
+// an extension is kept out of the registers:
+//   live   a lane mask of the block (every extension in flight enters a block alive).  Per residue, with s' = s + score and best' = max(best, s'):
+//          the oracle ends an extension that did not rise when best - s' > xdrop; when it rose best' = s' and xdrop >= 0 (pep_search's checks),
+//          so "best' - s' > xdrop" says the same without asking whether it rose.  A lane that has dropped gets the SCORE 0 from then on - one
+//          select on the mask - and s and best stay where they were by themselves: later residues, however good, do not count.
+//   pass   base + best reached the threshold (base = what the other side has secured, 0 on the right side).  An extension in flight has
+//          base + best < threshold at the start of every block (it starts at best = 0 with base < threshold - a right side that reached it has
+//          passed and left, a threshold <= 0 never extends - and stays in flight only while it has not passed), and best never falls: whether it
+//          passed inside a block is "best >= threshold - base" AFTER the block.  A lane that passed is not frozen; what it does with the rest
+//          of the block is not looked at.
+struct XDrop { int s, best; };
+__device__ __forceinline__ void xdrop_step(XDrop &x, bool &live, int sc, int xdrop)
 {
-    const int act = x.live & on;
-    const int s2 = x.s + sc;
-    const int up = s2 > x.best ? 1 : 0;
-    const int nb = up ? s2 : x.best;
-    const int p = up & (base + nb >= thr ? 1 : 0);
-    const int d = (up ^ 1) & (x.best - s2 > xdrop ? 1 : 0);
-    x.s = act ? s2 : x.s;
-    x.best = act ? nb : x.best;
-    x.pass |= act & p;
-    x.live &= (act & (p | d)) ^ 1;
+    x.s += live ? sc : 0;
+    x.best = max(x.best, x.s);
+    live = live && !(x.best - x.s > xdrop);
 }
 
 constexpr int RUN_TRIP = 4;                     // rounds of 64 hits a wavefront turns into runs at a time (their look-up chains overlap)
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
     uint32_t n_pass = 0;
     // the extension a lane has in flight
     int busy = 0, side = 0, k = 0, br = 0;
-    XDrop X = {0, 0, 0, 0};
+    XDrop X = {0, 0};
     uint64_t ck = 0, first = 0;
     uint32_t len = 0, h = 0, qp = 0, tp = 0;
     for (;;) {
@@ -813,7 +814,7 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
                 else {
                     const uint64_t hit = len == 1 ? first : a.hits[first];
                     qp = (uint32_t)(hit >> 32); tp = (uint32_t)hit; h = 0;
-                    busy = 1; side = 0; k = 0; X = XDrop{0, 0, 1, 0};
+                    busy = 1; side = 0; k = 0; X = XDrop{0, 0};
                 }
             }
             q_take = min(q_n, q_take + (uint32_t)__popcll(idle));
@@ -823,9 +824,10 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
             continue;
         }
         // ---- one block of XB residues for every extension in flight: right side block k = residues XB k .. XB k + XB - 1 from the seed start,
-        // left side block k = residues XB k + 1 .. XB k + XB before it (read from the seed outwards).  XB = 16: the first block IS stage 1
-        // (pep_search_params.stage1_min; oracle: ungapped_score).  Padding bytes (>= 16 around every sequence) score -64, which ends an
-        // extension exactly where the sequence ends (x-drop < 64): no bounds are needed.
+        // left side block k = residues XB k + 1 .. XB k + XB before it (read from the seed outwards).  Stage 1 (pep_search_params.stage1_min;
+        // oracle: ungapped_score) is asked after the first sixteen residues of the right side: with XB = 16, after its first block.  Padding
+        // bytes (>= 16 around every sequence) score -64, which ends an extension exactly where the sequence ends (x-drop < 64): no bounds
+        // are needed.
         constexpr int XB = 16;
         uint32_t qw[XB / 4], tw[XB / 4];
 #pragma unroll
@@ -842,28 +844,42 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
                 for (int w = 0; w < XB / 4; ++w) { qw[w] = q[w]; tw[w] = t[w]; }
             }
         }
-        const int r0 = side ? XB * k + 1 : XB * k, lim = side ? a.ext_left + 1 : a.ext_right, base_score = side ? br : 0;
+        // The limit (ext_right residues from the seed start, ext_left before it) is put into the DATA: the query residues of this block at and
+        // beyond it become the padding code, whose scores are <= -64 against every code while xdrop <= 48 (pep_search's checks of the table and
+        // of the parameters): the lane drops at the first of them with best unchanged - all that the "residue inside the limit" test per
+        // residue did - and a lane that dropped or passed before is not touched.  After the block the lane takes the branch the limit took:
+        // when the limit lies inside block k, XB (k + 1) >= ext_right on the right and XB (k + 1) + 1 > ext_left on the left, whatever `live`
+        // says.  A wavefront none of whose extensions is in its last block - most - skips this.
+        const int n_in = (side ? a.ext_left : a.ext_right) - XB * k;           // residues of this block inside the limit
+        if (__ballot(busy && n_in < XB)) {
+#pragma unroll
+            for (int w = 0; w < XB / 4; ++w) {
+                const int in_w = n_in - 4 * w;
+                if (in_w < 4) qw[w] = in_w <= 0 ? PAD4 : (qw[w] | (0xFFFFFFFFu << (8 * in_w)));
+            }
+        }
+        bool live = busy != 0;
 #pragma unroll
         for (int j = 0; j < XB; ++j) {
             const int qc = (int)((qw[j >> 2] >> ((j & 3) * 8)) & 31u), tc = (int)((tw[j >> 2] >> ((j & 3) * 8)) & 31u);
-            xdrop_step(X, sub[qc * 32 + tc], busy & (r0 + j < lim ? 1 : 0), base_score, a.ungapped_min, a.xdrop);
+            xdrop_step(X, live, sub[qc * 32 + tc], a.xdrop);
         }
         // ---- where the extension stands after the block
         if (busy) {
             ++k;
             bool next_hit = false;
-            if (X.pass) { ++n_pass; set_insert(a, ck); busy = 0; }
+            if (X.best >= a.ungapped_min - (side ? br : 0)) { ++n_pass; set_insert(a, ck); busy = 0; }
             else if (side == 0) {
                 // stage 1: after sixteen residues to the right (or wherever the extension ended before) it must have reached stage1_min
-                const bool over = !X.live || XB * k >= a.ext_right;
-                if (k == 1 && X.best < a.stage1_min) next_hit = true;
-                else if (over) { side = 1; k = 0; br = X.best; X = XDrop{0, 0, 1, 0}; }
-            } else if (!X.live || XB * k + 1 > a.ext_left) next_hit = true;
+                const bool over = !live || XB * k >= a.ext_right;
+                if ((over || XB * k >= 16) && X.best < a.stage1_min) next_hit = true;       // (best only grows: asking again after a later block changes nothing)
+                else if (over) { side = 1; k = 0; br = X.best; X = XDrop{0, 0}; }
+            } else if (!live || XB * k + 1 > a.ext_left) next_hit = true;
             if (next_hit) {
                 if (++h < len) {
                     const uint64_t hit = a.hits[first + h];
                     qp = (uint32_t)(hit >> 32); tp = (uint32_t)hit;
-                    side = 0; k = 0; X = XDrop{0, 0, 1, 0};
+                    side = 0; k = 0; X = XDrop{0, 0};
                 } else busy = 0;
             }
         }
