@@ -429,7 +429,7 @@ int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to
  * pep_pair_support (K14): get_similar (PEPPAN.py:195-224) for many groups of forward alignments at once.  Group g = rows
  *   [grp_off[g], grp_off[g+1]) in table order, all of one (query, reference) pair of lengths grp_qlen / grp_rlen.  value[g] =
  *   PEP_SUPPORT_NONE (no decision), 0 (similar but too short a support) or int(mean identity * 10000), with the mean taken over the
- *   covered query positions exactly as numpy.mean takes it (pairwise summation in first-cover order).  At most 255 rows per group.
+ *   covered query positions exactly as numpy.mean takes it (first-cover order; pairwise summation inside buffers of 8192 positions, the buffers' sums added up left to right).  At most 255 rows per group.
  * pep_similar_resolve (host, no context): the dictionary ortho_pairs from the events and the values K14 returned for them (ev_value[e]
  *   is ignored for conflicts): out = (a, b, value) triples with value != 0 in first-insertion order (capacity 3 n_events). */
 #define PEP_ROW_ORDINARY 0

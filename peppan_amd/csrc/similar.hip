@@ -12,8 +12,11 @@
 //                                    insertion order kept) over the events and their values.
 //
 // The mean.  The reference computes int(np.mean(list(matched_aa.values())) * 10000): a float64 sum over the positions in dictionary
-// (first-insertion) order by numpy's pairwise summation - blocks of at most 128 elements summed through 8 interleaved accumulators,
-// combined by a fixed binary tree (n2 = n / 2 - (n / 2) % 8) - divided by n.  A plain running sum differs from it in the last bit for
+// (first-insertion) order, divided by n.  numpy's reduction hands its inner loop at most one buffer of 8192 elements (numpy.getbufsize())
+// at a time and adds the buffers' sums up from left to right; inside a buffer the sum is numpy's pairwise summation - blocks of at most 128
+// elements summed through 8 interleaved accumulators, combined by a fixed binary tree (n2 = n / 2 - (n / 2) % 8).  (Up to 8192 positions
+// that is one pairwise sum; beyond, a pairwise sum over all positions gives another last bit: 0.57 over 40 000 positions makes 5699
+// instead of the reference's 5700, golden G24.)  A plain running sum differs from it in the last bit for
 // almost every n (300 of 300 random cases), and int() truncation turns a last-bit difference at x.9999999999 into a different integer, so
 // K14 reproduces the summation tree operation for operation: 8 lanes per leaf block hold the 8 accumulators, their combination is the
 // same ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) + tail, and one lane folds the leaf sums along the tree.  IEEE float64 additions and one
@@ -31,7 +34,8 @@
 
 namespace {
 
-constexpr int LEAF_MAX = 512;            // leaf blocks (<= 128 elements, >= 64 once there are several) kept in LDS: n <= 32768 positions
+constexpr int NP_BUFFER = 8192;          // elements numpy's reduction sums in one go (its default buffer size)
+constexpr int LEAF_MAX = 128;            // leaf blocks (<= 128 elements) of one buffer, kept in LDS: at most 65 for n <= 8192
 constexpr int ROW_MAX = 255;             // rows per group (the reference never judges 50 or more, PEPPAN.py:266)
 constexpr int PW_BLOCK = 128;
 
@@ -52,21 +56,10 @@ struct SupportArgs {
 
 __device__ __forceinline__ int split_left(int n) { const int h = n / 2; return h - h % 8; }
 
-// numpy's pairwise sum of v[0 .. n) where v(k) = iden[val_row[k] - 1]; every lane returns the sum
+// numpy's pairwise sum of v[0 .. n), n <= NP_BUFFER, where v(k) = iden[val_row[k] - 1]; every lane returns the sum
 __device__ double numpy_sum(const uint8_t *val_row, const double *iden, int n, int lane, uint32_t *leaf_off, uint32_t *leaf_n, double *leaf_sum)
 {
     auto v = [&](int k) { return iden[val_row[k] - 1]; };
-    auto leaf_serial = [&](int off, int m) {
-        if (m < 8) { double r = 0.; for (int i = 0; i < m; ++i) r += v(off + i); return r; }
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = v(off + j);
-        int i = 8;
-        for (; i < m - (m % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += v(off + i + j);
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < m; ++i) res += v(off + i);
-        return res;
-    };
     // phase A (lane 0): the leaves of the summation tree, left to right
     int n_leaf = 0;
     if (lane == 0) {
@@ -79,13 +72,12 @@ __device__ double numpy_sum(const uint8_t *val_row, const double *iden, int n, i
             else { const int l = split_left(m); st_off[sp] = off + l; st_n[sp] = m - l; ++sp; st_off[sp] = off; st_n[sp] = l; ++sp; }
         }
     }
-    n_leaf = __shfl(n_leaf, 0, 64);
-    const bool in_lds = n_leaf <= LEAF_MAX;
+    n_leaf = min(__shfl(n_leaf, 0, 64), LEAF_MAX);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     // phase B: leaf sums, 8 lanes per leaf = its 8 accumulators
-    if (in_lds) {
+    {
         const int j = lane & 7, w = lane >> 3;
         for (int l0 = 0; l0 < n_leaf; l0 += 8) {                // wave-uniform trip count
             const int l = l0 + w;
@@ -120,7 +112,7 @@ __device__ double numpy_sum(const uint8_t *val_row, const double *iden, int n, i
         while (sp > 0) {
             const int top = sp - 1;
             if (!have_val) {
-                if (fr_n[top] <= PW_BLOCK) { val = in_lds ? leaf_sum[li] : leaf_serial(fr_off[top], fr_n[top]); ++li; have_val = true; --sp; }
+                if (fr_n[top] <= PW_BLOCK) { val = leaf_sum[min(li, LEAF_MAX - 1)]; ++li; have_val = true; --sp; }
                 else { fr_stage[top] = 1; const int l = split_left(fr_n[top]); fr_off[sp] = fr_off[top]; fr_n[sp] = l; fr_stage[sp] = 0; ++sp; }
             } else if (fr_stage[top] == 1) {
                 fr_left[top] = val; fr_stage[top] = 2; have_val = false;
@@ -192,7 +184,14 @@ __global__ __launch_bounds__(64) void k14_pair_support(SupportArgs a)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                const double sum = numpy_sum(val_row, iden, n_cov, lane, leaf_off, leaf_n, leaf_sum);
+                double sum = 0.;
+                for (int c0 = 0; c0 < n_cov; c0 += NP_BUFFER) {                           // buffer by buffer, left to right
+                    const double part = numpy_sum(val_row + c0, iden, min(NP_BUFFER, n_cov - c0), lane, leaf_off, leaf_n, leaf_sum);
+                    sum = c0 ? sum + part : part;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                }
                 const double mean = sum / (double)n_cov;
                 const int ave = (int)(mean * 10000.0);                                    // PEPPAN.py:212
                 if ((double)ave >= a.lim.identity_x1e4) {

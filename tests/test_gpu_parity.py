@@ -652,7 +652,7 @@ def _random_support_groups(rng, n_groups, long_group=False):
     for g in range(n_groups):
         ql = int(rng.choice([90, 300, 1002, 2400, 9000])) + int(rng.integers(0, 30))
         if long_group and g == 0:
-            ql = 120000                                          # more than 32 768 covered positions: the serial leaf path of the summation
+            ql = 120000                                          # more than 8192 covered positions: several of numpy's reduction buffers
         rl = max(30, int(ql * rng.choice([1., 1., 0.9, 1.3, 0.04])))
         n_rows = int(rng.choice([1, 1, 2, 2, 3, 6])) if g % 37 else 49
         for _ in range(n_rows):
