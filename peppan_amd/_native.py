@@ -131,6 +131,20 @@ GENESTRUCT_SIGNATURES = {
     'pep_gene_structure_times': (I, P, P, P, P),
 }
 
+# ... and of include/peppan_parser.h (K20), likewise a header with a version of its own; tests/test_parser_host.py holds this table to it
+PARSER_ABI_VERSION = 1
+PARSER_MAX_GENES = 1 << 31               # PEP_PARSER_MAX_GENES: a presence matrix or a profile holds fewer genes than this
+PARSER_MAX_CURVE_POINTS = 1 << 28        # PEP_PARSER_MAX_CURVE_POINTS: n_genomes * n_iter of one pep_rarefaction_curves call stays below this
+PARSER_MAX_PROFILES = 16384              # PEP_PARSER_MAX_PROFILES: profiles of one pep_profile_pairs call
+PARSER_SIGNATURES = {
+    'pep_parser_version': (I,),
+    'pep_rarefaction_curves': (I, P, P, U32, U64, P, U32, P),
+    'pep_rarefaction_curves_check': (I, P, U32, U64, P, U32, P, U64),
+    'pep_profile_pairs': (I, P, P, U32, U64, P, P),
+    'pep_profile_pairs_check': (I, U32, U64, P, U64),
+    'pep_parser_times': (I, P, P, P, P, P),
+}
+
 
 class PepError(RuntimeError):
     pass
@@ -219,7 +233,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()) + list(GENESTRUCT_SIGNATURES.items()):
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()) + list(GENESTRUCT_SIGNATURES.items()) + list(PARSER_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -230,6 +244,8 @@ def load_library():
         raise PepError('libpeppan_hip.so ABI version mismatch (peppan_synteny.h)')
     if lib.pep_genestruct_version() != GENESTRUCT_ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch (peppan_genestruct.h)')
+    if lib.pep_parser_version() != PARSER_ABI_VERSION:
+        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_parser.h)')
     _lib = lib
     return lib
 
@@ -574,6 +590,57 @@ def gene_structure_check(seq_off, seq, win_off, win_len, flags, lp, allowed_vary
     """the host checks of pep_gene_structure alone (no context, no device, the nucleotides are not read): PepError with the library's code and text, else None"""
     args, _, keep = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
     _check_only('pep_gene_structure_check', *args)
+
+
+def pack_presence(presence):
+    """a presence matrix bool[n_genomes, n_genes] as the bit rows of include/peppan_parser.h: uint64[n_genomes, W], gene e at bit e % 64 of word e // 64, padding zero"""
+    presence = np.asarray(presence, dtype=bool)
+    if presence.ndim != 2:
+        raise ValueError('pack_presence: a matrix [n_genomes, n_genes]')
+    n, n_genes = presence.shape
+    words = (n_genes + 63) // 64
+    padded = np.zeros((n, words * 64), dtype=bool)
+    padded[:, :n_genes] = presence
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder='little')).view('<u8').reshape(n, words)
+
+
+def _curve_tables(bits, n_genes, orders):
+    """the tables of one pep_rarefaction_curves / pep_rarefaction_curves_check call as the library's types -> (arguments, n_genomes, n_iter, what keeps them alive).
+    Shapes that do not fit each other and values that do not fit their column raise ValueError here: ctypes and numpy would cut them silently"""
+    bits = np.asarray(bits)
+    orders = np.asarray(orders)
+    if bits.ndim != 2 or orders.ndim != 2:
+        raise ValueError('rarefaction_curves: bits is [n_genomes, W] and orders [n_iter, n_genomes]')
+    if bits.dtype != np.uint64:
+        raise ValueError('rarefaction_curves: bits must be uint64 words (pack_presence)')
+    n_genes = int(n_genes)
+    if n_genes < 0 or n_genes >= 1 << 64 or bits.shape[1] != (n_genes + 63) // 64:
+        raise ValueError('rarefaction_curves: %d genes need %d words per genome, not %d' % (n_genes, (n_genes + 63) // 64, bits.shape[1]))
+    if orders.shape[1] != bits.shape[0]:
+        raise ValueError('rarefaction_curves: an order names every genome once: %d entries for %d genomes' % (orders.shape[1], bits.shape[0]))
+    if orders.dtype != np.uint32:
+        if orders.size and orders.dtype.kind not in 'iu':
+            raise ValueError('rarefaction_curves: orders must hold integers')
+        if orders.size and (int(orders.min()) < 0 or int(orders.max()) >= 1 << 32):
+            raise ValueError('rarefaction_curves: orders holds values outside [0, 2^32)')
+        orders = orders.astype(np.uint32)
+    if bits.shape[0] >= 1 << 32 or orders.shape[0] >= 1 << 32:
+        raise ValueError('rarefaction_curves: more than 2^32 - 1 genomes or orders in one call')
+    keep = [_some(np.ascontiguousarray(bits).reshape(-1)), _some(np.ascontiguousarray(orders).reshape(-1))]
+    return [_ptr(keep[0]), bits.shape[0], n_genes, _ptr(keep[1]), orders.shape[0]], bits.shape[0], orders.shape[0], keep
+
+
+def rarefaction_curves_check(bits, n_genes, orders):
+    """the host checks of pep_rarefaction_curves alone (no context, no device): PepError with the library's code and text, else None"""
+    args, _, _, keep = _curve_tables(bits, n_genes, orders)
+    _check_only('pep_rarefaction_curves_check', *args)
+
+
+def profile_pairs_check(n, n_genes):
+    """the host checks of pep_profile_pairs alone (the sizes; no context, no device): PepError with the library's code and text, else None"""
+    if not (0 <= int(n) < 1 << 32 and 0 <= int(n_genes) < 1 << 64):
+        raise ValueError('profile_pairs: sizes outside their columns')
+    _check_only('pep_profile_pairs_check', int(n), int(n_genes))
 
 
 def codon_tables(table_id=11):
@@ -1624,6 +1691,45 @@ class Context(object):
         ms, up, down = C.c_double(), C.c_uint64(), C.c_uint64()
         self._call('pep_gene_structure_times', C.byref(ms), C.byref(up), C.byref(down))
         return float(ms.value), int(up.value), int(down.value)
+
+    # ---- K20
+    def rarefaction_curves(self, bits, n_genes, orders):
+        """the loop of writeCurve (PEPPAN_parser.py:74-80).  bits: the presence matrix as bit rows uint64[n_genomes, W] (pack_presence), n_genes its genes,
+        orders: [n_iter, n_genomes], every row a permutation of the genomes.
+        -> int64[n_genomes, n_iter, 2]: genes in at least one / in all of the first k + 1 genomes of order t at [k, t], the reference's `curves`, as
+        include/peppan_parser.h states them"""
+        args, n, n_iter, keep_alive = _curve_tables(bits, n_genes, orders)
+        curves = np.zeros((max(n, 1), max(n_iter, 1), 2), np.int32)
+        self._call('pep_rarefaction_curves', *args, _ptr(curves))
+        return curves[:n, :n_iter].astype(np.int64)
+
+    def profile_pairs(self, profiles):
+        """the pair loop of getDistance (PEPPAN_parser.py:172-179).  profiles: int32[n, n_genes], > 0 an allele.
+        -> (shared, presence) int32[n, n], symmetric with a zero diagonal: the genes both profiles carry with the same allele / carry at all"""
+        profiles = np.asarray(profiles)
+        if profiles.ndim != 2:
+            raise ValueError('profile_pairs: a matrix [n, n_genes]')
+        if profiles.dtype != np.int32:
+            if profiles.size and profiles.dtype.kind not in 'iu':
+                raise ValueError('profile_pairs: profiles must hold integers')
+            if profiles.size and (int(profiles.min()) < -2 ** 31 or int(profiles.max()) >= 2 ** 31):
+                raise ValueError('profile_pairs: profiles holds values outside int32')
+            profiles = profiles.astype(np.int32)
+        profiles = np.ascontiguousarray(profiles)
+        n, n_genes = profiles.shape
+        if n >= 1 << 32:
+            raise ValueError('profile_pairs: more than 2^32 - 1 profiles in one call')
+        shared, presence = np.zeros((max(n, 1), max(n, 1)), np.int32), np.zeros((max(n, 1), max(n, 1)), np.int32)
+        self._call('pep_profile_pairs', _ptr(_some(profiles.reshape(-1))), n, n_genes, _ptr(shared), _ptr(presence))
+        shared, presence = shared[:n, :n], presence[:n, :n]
+        return shared + shared.T, presence + presence.T                  # (the library stores the pairs i < j)
+
+    def parser_times(self):
+        """of the newest pep_rarefaction_curves and pep_profile_pairs: (their kernel times in ms when set_timing(2) is on, else 0; bytes the newer of the two
+        calls sent to the device; bytes it sent to the host)"""
+        ms_curves, ms_pairs, up, down = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()
+        self._call('pep_parser_times', C.byref(ms_curves), C.byref(ms_pairs), C.byref(up), C.byref(down))
+        return float(ms_curves.value), float(ms_pairs.value), int(up.value), int(down.value)
 
     # ---- K13
     def sha1(self, seqs):

@@ -266,6 +266,9 @@ struct pep_ctx {
     double k19_ms = 0.;                      // the newest pep_gene_structure: kernel time when pep_set_timing is 2 (genestruct.hip)
     uint64_t k19_bytes_to_device = 0, k19_bytes_to_host = 0;   // ... and what it sent each way
     DevBuf k19[5];                           // grow-only: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
+    double k20_ms[2] = {0., 0.};             // the newest pep_rarefaction_curves and pep_profile_pairs: their kernel times when pep_set_timing is 2 (parser.hip)
+    uint64_t k20_bytes_to_device = 0, k20_bytes_to_host = 0;   // ... and what the newer of the two sent each way
+    DevBuf k20[6];                           // grow-only: bit rows, orders and curves; profiles and the two pair matrices (the slots: parser.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
