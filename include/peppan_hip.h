@@ -42,6 +42,14 @@
  *   pep_similar_classify / pep_similar_scan / pep_pair_support / pep_similar_resolve   the pass of get_similar_pairs over the all-vs-all table and its
  *                           get_similar (row-local tests, host state machine, K14 on the GPU, host dictionary)   PEPPAN.py:195-224, 231-276, 294
  *   pep_known_order         compare_prediction over a genome's hit table (host C++)   PEPPAN.py:869-901
+ *   pep_synteny_pairs (+ _copy, _check)   the pair loop of ite_synteny_resolver: distance, conflict pairs, the sort of the pairs   PEPPAN.py:1101-1117
+ *   pep_synteny_walk                      its merge walk and verdict (host C++, no context)                                     PEPPAN.py:1118-1151
+ *   pep_gene_structure (+ _check)   determineGeneStructure for every intact prediction of write_output: the marked-start translation
+ *                                   of the window in the tried frames and the search for start and stop   PEPPAN.py:1193-1229
+ *   pep_rarefaction_curves (+ _check)   the n_iter x n_genomes loop of writeCurve: genes seen in at least one / in all of the first
+ *                                       k + 1 genomes of every random genome order                      PEPPAN_parser.py:74-80
+ *   pep_profile_pairs (+ _check)        the pair loop of getDistance: per pair of allelic profiles the genes both carry and the
+ *                                       genes where both carry the same allele                          PEPPAN_parser.py:172-179
  */
 #ifndef PEPPAN_HIP_H
 #define PEPPAN_HIP_H
@@ -52,8 +60,10 @@ extern "C" {
 
 /* 17 gained, additively, the K16 entry points: pep_group_verdicts, pep_group_verdicts_check, pep_verdict_detail_size, pep_verdict_detail_copy,
  * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check.
- * 18 gained pep_live_resources; and, additively, the K17 entry points: pep_gene_ingroups, pep_gene_ingroups_check, pep_gene_ingroups_times. */
-#define PEP_ABI_VERSION 18
+ * 18 gained pep_live_resources; and, additively, the K17 entry points: pep_gene_ingroups, pep_gene_ingroups_check, pep_gene_ingroups_times.
+ * 19 took in the sections of K18, K19 and K20, which had headers and version numbers of their own (pep_synteny_version, pep_genestruct_version and
+ * pep_parser_version are gone), and replaced the six pep_*_times read-outs of K15 - K20 by pep_call_times. */
+#define PEP_ABI_VERSION 19
 
 #define PEP_OK 0
 #define PEP_ERR_HIP (-1)       /* a HIP runtime call failed */
@@ -221,6 +231,19 @@ int pep_set_result_mode(pep_ctx *ctx, int on_device);
  * leaves the GPU idle for about 6 us between the two kernels it separates.  level 0 (the default): none, the fields stay 0;
  * 1: the Smith-Waterman score pass only (ms_sw); 2: every phase (sixteen events per search).  ms_k1 (pep_translate) follows the same switch. */
 int pep_set_timing(pep_ctx *ctx, int level);
+/* The times of the context's newest call of one of K15 - K20: ms[] are kernel times on the context's stream, measured when pep_set_timing is 2 (else 0) unless
+ * the kernel's section says otherwise, and the byte counts are what the call moved each way.  What each slot holds is stated in the kernel's section below; a slot
+ * or a byte count a kernel does not use reads 0.  A call resets its own record when it starts (K20's two calls share one: see there) and touches no other.  PEP_ERR_ARG: a null ctx or out, a `which`
+ * outside [0, PEP_CALL_COUNT).  (The struct goes by its tag: the function has its name.) */
+#define PEP_CALL_ALLELE_DIFF 0        /* pep_allele_diff */
+#define PEP_CALL_GROUP_VERDICTS 1     /* pep_group_verdicts (+ pep_verdict_detail_copy) */
+#define PEP_CALL_GENE_INGROUPS 2      /* pep_gene_ingroups */
+#define PEP_CALL_SYNTENY_PAIRS 3      /* pep_synteny_pairs (+ pep_synteny_pairs_copy) */
+#define PEP_CALL_GENE_STRUCTURE 4     /* pep_gene_structure */
+#define PEP_CALL_PARSER 5             /* pep_rarefaction_curves and pep_profile_pairs */
+#define PEP_CALL_COUNT 6
+struct pep_call_times { double ms[4]; uint64_t bytes_to_device, bytes_to_host; };
+int pep_call_times(const pep_ctx *ctx, int which, struct pep_call_times *out);
 /* K2..K8: seeds, candidates, banded Smith-Waterman, traceback, filters, top-k.  Hits ordered by (q, t). */
 int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out);
 int pep_result_size(const pep_result *r, uint64_t *n_hits, uint64_t *n_cigar);
@@ -347,14 +370,13 @@ int pep_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *nt_off, uint32_
  * past out_cap.  PEP_ERR_LIMIT: the call's output or its bit planes (24 B per 64 columns of a row) exceed PEP_ALLELE_DIFF_MAX_BYTES each;
  * the message says how much was asked for, and the caller splits the batch.  After an error `out` holds nothing usable.
  * (The output limit is reported at the first group that crosses it, with the bytes counted up to that group.)
- * pep_allele_diff_times: of the context's newest pep_allele_diff, in ms: the kernel times - bit planes, pairs - when pep_set_timing is 2
- * (else zeros; at that level the host waits between the two kernels), and the host's wall time from the end of the kernels until the
- * output lies in `out` (always). */
+ * pep_call_times(PEP_CALL_ALLELE_DIFF): of the context's newest pep_allele_diff: ms[0], ms[1] the kernel times - bit planes, pairs - when
+ * pep_set_timing is 2 (else zeros; at that level the host waits between the two kernels), and ms[2] the host's wall time from the end of the
+ * kernels until the output lies in `out` (always).  No byte counts. */
 #define PEP_ALLELE_DIFF_MAX_BYTES (1ull << 31)
 int pep_allele_diff(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows,
                     uint32_t n_groups, const uint64_t *grp_off, const uint32_t *grp_rows, const uint8_t *grp_mode,
                     int32_t *out, const uint64_t *out_off, uint64_t out_cap);
-int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back);
 
 /* K16: divergence verdicts of gene groups - what filt_per_group decides from the pairs of K15 before it looks at any of them on the host
  * (checkDiv over the first and last row, PEPPAN.py:335-344, 346-351; over the first and last row of every genome's sub-group for in-paralog
@@ -379,8 +401,8 @@ int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pair
  * pep_verdict_result_free before the context is destroyed.  pep_verdict_detail_size: pairs of group g's triangle, 0 unless its verdict is 2.
  * pep_verdict_detail_copy: tri (int32 pairs, packed upper triangle as pep_allele_diff's bit 0) and leader (uint32[n]: the row that leads
  * row j, leader[j] == j for a leader); either may be NULL; nothing is written for verdict 0 / 1.
- * pep_group_verdicts_times: of the newest call, the kernel times in ms - bit planes, edge, pairs, leaders - when pep_set_timing is 2 (else
- * zeros), and the bytes that call and the detail copies of its result have sent to the host. */
+ * pep_call_times(PEP_CALL_GROUP_VERDICTS): of the newest call, ms[0..3] the kernel times - bit planes, edge, pairs, leaders - when pep_set_timing is 2
+ * (else zeros), and bytes_to_host what that call and the detail copies of its result have sent to the host. */
 int pep_group_verdicts(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,
                        const uint64_t *grp_off, const uint32_t *grp_rows, const uint32_t *grp_genome, const uint8_t *grp_inparalog, const uint64_t *gd_key,
                        const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, uint8_t *verdict, pep_verdict_result **detail);
@@ -390,7 +412,6 @@ int pep_group_verdicts_check(const uint8_t *packed, const uint64_t *row_off, con
 int pep_verdict_detail_size(const pep_verdict_result *res, uint32_t g, uint64_t *n_pairs);
 int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *tri, uint32_t *leader);
 void pep_verdict_result_free(pep_verdict_result *res);
-int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host);
 
 /* K17: in-group rows and gene scores of `initializing` - determineGroup (PEPPAN.py:1041-1056) as initializing2 calls it for every gene of the
  * .tab store, and the gene's score (:1058-1076).  Gene g is rows [gene_off[g], gene_off[g+1]) of the three row tables, in the order of :1069:
@@ -408,13 +429,139 @@ int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_t
  * not > 0, self_id or thr not finite.  PEP_ERR_LIMIT: n_rows >= 2^32.  Empty batches and empty genes are legal; an empty gene scores 0.  On an
  * error nothing is written and the context stays usable.  The work is quadratic in the rows of a gene in the worst case, as the reference's.
  * pep_gene_ingroups_check runs the checks alone: no context, no device; the message goes to msg (msg_cap bytes, 0-terminated).
- * pep_gene_ingroups_times: of the newest call, the kernel times in ms - pairs, finish - when pep_set_timing is 2 (else zeros), and the bytes
- * the call sent to the host: n_rows + 8 * n_genes. */
+ * pep_call_times(PEP_CALL_GENE_INGROUPS): of the newest call, ms[0], ms[1] the kernel times - pairs, finish - when pep_set_timing is 2 (else zeros),
+ * and bytes_to_host what the call sent to the host: n_rows + 8 * n_genes. */
 int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
                       const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, uint8_t *keep, int64_t *gene_score);
 int pep_gene_ingroups_check(const uint32_t *genome, const int32_t *iden, const int64_t *score, uint64_t n_rows, uint32_t n_genes, const uint64_t *gene_off,
                             const uint64_t *gd_key, const double *gd_val, uint64_t n_gd, const double *gd_default, double self_id, double thr, char *msg, uint64_t msg_cap);
-int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host);
+
+/* ---- K18: neighbourhood paralog splitting (synteny_resolver).
+ * most pairs (sum over the groups of n * (n - 1) / 2) of one pep_synteny_pairs call: a single group may hold 16 384 members */
+#define PEP_SYNTENY_MAX_PAIRS (1ull << 27)
+/* most rank counters of one call: sum over the groups of n * (6 * longest list of the group + 14) */
+#define PEP_SYNTENY_MAX_COUNTERS (1ull << 26)
+/* longest neighbour list of one member */
+#define PEP_SYNTENY_MAX_LIST (1u << 20)
+
+/* K18: the pair loop of ite_synteny_resolver (PEPPAN.py:1097-1151) for a batch of paralogous names.  Group g is members
+ * [member_off[g], member_off[g+1]) of genome[] (compared for equality only) and of the neighbour lists in CSR form: member i owns
+ * nb[nb_off[i] .. nb_off[i+1]), strictly ascending ortholog codes.  Members are numbered 0 .. n-1 inside their group.  For m < k with
+ * c = |N_m & N_k| (:1108-1110):
+ *   s = 3 c + max(6 - min(6, |N_m|), 6 - min(6, |N_k|), 0) + 1,   d = 3 n_neighbor - s,   flag = (genome[m] != genome[k]).
+ * A pair is a conflict iff flag is false and d > 0 (:1112).  dc[g] is the smallest d of a conflict pair (0 and has_conflict[g] = 0 when there
+ * is none).  The call leaves two lists of (m, k) pairs, two uint32 each, in the context:
+ *   conf   the conflict pairs, ascending by (m, k);
+ *   walk   every pair with d < dc, in the order (d, flag, m, k) - the part of the sorted list (:1117) the walk of :1119-1141 reads before it
+ *          stops at the first conflict pair.  Empty for a group without a conflict.
+ * Group g owns conf pairs [conf_off[g], conf_off[g+1]) and walk pairs [walk_off[g], walk_off[g+1]) (G + 1 offsets each, counted in pairs).
+ * The lists are counted first and the context's buffers sized from the count: nothing is truncated.  pep_synteny_pairs_copy downloads the
+ * lists of the newest call: n_conf / n_walk must be conf_off[G] / walk_off[G].
+ * PEP_ERR_ARG: n_neighbor outside [1, 2^20], offsets that do not ascend from 0 to their end, a list that is not strictly ascending.
+ * PEP_ERR_LIMIT: more pairs than PEP_SYNTENY_MAX_PAIRS (the message names the group at which the sum passes it), more counters than
+ * PEP_SYNTENY_MAX_COUNTERS, a list longer than PEP_SYNTENY_MAX_LIST.  All tables are checked on the host before anything is launched.  The
+ * kernels keep a fault word for what those checks exclude - a distance beyond the group's bound, a pair beyond the counted lists: it is read
+ * after each pass, and the call then fails with PEP_ERR_HIP instead of returning a list.  The four outputs are written only when the call
+ * succeeds; on any error nothing is written and the context stays usable.  Integer arithmetic only.
+ * pep_synteny_pairs_check runs the checks alone: no context, no device; the message goes to msg (msg_cap bytes, 0-terminated).
+ * pep_call_times(PEP_CALL_SYNTENY_PAIRS): of the newest call, ms[0..2] the kernel times - count, scans, emit - when pep_set_timing is 2 (else zeros), and
+ * bytes_to_host what the call and its pep_synteny_pairs_copy sent to the host. */
+int pep_synteny_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb,
+                      uint64_t n_nb, int32_t n_neighbor, uint8_t *has_conflict, int32_t *dc, uint64_t *conf_off, uint64_t *walk_off);
+int pep_synteny_pairs_copy(pep_ctx *ctx, uint32_t *conf, uint64_t n_conf, uint32_t *walk, uint64_t n_walk);
+int pep_synteny_pairs_check(uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb,
+                            uint64_t n_nb, int32_t n_neighbor, char *msg, uint64_t msg_cap);
+
+/* The walk of ite_synteny_resolver over the two lists of pep_synteny_pairs (PEPPAN.py:1118-1151), on the host, without a context.  Every
+ * member starts as a component of its own, with list A = [member] when it is an end of a conflict pair and B = [member] otherwise.  For each
+ * walk pair (m, k) whose ends lie in different components ti, tj: the merge is skipped iff a conflict pair joins A[ti] and A[tj]; otherwise
+ * A[ti] += A[tj], B[ti] += B[tj] (:1124-1141).  verdict[g]: 0 no conflict pair (the reference returns [None, None]), 1 a surviving component
+ * has an empty A ([tag, None], :1147-1150), 2 a partition.  For verdict 2, n_comp[g] components in the order of their roots (the dictionary
+ * order of :1148): component c of group g has the root comp_root[member_off[g] + c] - the member whose id is its key in the reference's
+ * dictionary, not always its smallest - and comp_len[member_off[g] + c] members, and members[member_off[g] ..] holds the lists A + B of the
+ * components one after the other (n entries in all).  For the other verdicts n_comp[g] = 0.  The skip test reads per-member conflict
+ * adjacency, and components are joined by union-find over linked lists: the walk stays about linear in the pairs.
+ * PEP_ERR_ARG: offsets that do not ascend from 0, a pair that is not m < k < n. */
+int pep_synteny_walk(uint32_t n_groups, const uint64_t *member_off, const uint64_t *conf_off, const uint32_t *conf, const uint64_t *walk_off, const uint32_t *walk,
+                     uint8_t *verdict, uint32_t *n_comp, uint32_t *comp_root, uint32_t *comp_len, uint32_t *members, char *msg, uint64_t msg_cap);
+
+/* ---- K19: the gene structure of predictions (determineGeneStructure).
+ * a window holds fewer nucleotides than this */
+#define PEP_GENESTRUCT_MAX_WINDOW (1ull << 31)
+/* stop_aa of a frame without a stop codon */
+#define PEP_GENESTRUCT_NO_STOP 0xFFFFFFFFu
+/* kind[]: the outcome of a frame */
+#define PEP_GENESTRUCT_CDS 0
+#define PEP_GENESTRUCT_NOSTART 1
+#define PEP_GENESTRUCT_NOSTOP 2
+#define PEP_GENESTRUCT_PREMATURE 3
+
+/* K19: determineGeneStructure (PEPPAN.py:1193-1229) for a batch of predictions.  The nucleotide set is ASCII bytes, sequence i at
+ * nt[seq_off[i] .. seq_off[i+1]) (n_seq + 1 offsets).  Prediction p reads the window of win_len[p] nucleotides that starts at the 0-based
+ * win_off[p] of sequence seq[p] - forward, or, when bit 0 of flags[p] is set, backward and complemented as the reference's rc() does it
+ * (upper-cased, A<->T, C<->G, everything else N: a '-' read backward is an N).  Bits 1-3 of flags[p] are the tried frames 0, 1, 2.
+ * Frame f of a window of L nucleotides has n = max(0, (L - f) / 3) codons, codon k = window[f + 3k .. f + 3k + 3) (a partial last codon is
+ * dropped, :1197).  A codon with a '-' is neither start nor stop; otherwise a codon with a character outside ACGT (either case) is a stop 'X';
+ * otherwise TAA and TAG are stops, TGA too unless table4, and ATG, GTG, TTG are starts 'M' (modules/configure.py:167-172).
+ * With a = lp / 3, b = (lp + allowed_vary) / 3, and "first / last in [u, v)" clipped to n as str.find / str.rfind clip:
+ *     start = first M in [a, b), else last M in [0, a), else a with the outcome NOSTART
+ *     stop  = first X in [start, n)
+ *     while 0 <= stop < b and there is a first M in [stop, b): start = that M, stop = first X in [start, n)
+ *     no stop: NOSTOP, else (stop - start + 1) * 3 < ref_len - allowed_vary: PREMATURE (both override NOSTART); else NOSTART or CDS.
+ * The tried frames are judged in ascending order:
+ *     frame[p]      the lowest tried frame whose outcome is CDS, or -1
+ *     start_aa[p], stop_aa[p]   start and stop (codon numbers) of that frame; of the FIRST tried frame when frame[p] is -1, with
+ *                   PEP_GENESTRUCT_NO_STOP for a frame without a stop
+ *     kind[p]       the outcome of the first tried frame (PEP_GENESTRUCT_*)
+ * Integer arithmetic only.  The four outputs are written only when the call succeeds; on any error nothing is written and the context
+ * stays usable.  All tables are checked on the host before anything is launched:
+ * PEP_ERR_ARG: seq_off does not ascend from 0, seq[p] >= n_seq, a window that leaves its sequence, no tried frame or flag bits above bit 3,
+ * ref_len[p] == 0.  PEP_ERR_LIMIT: a window of PEP_GENESTRUCT_MAX_WINDOW nucleotides or more; the message names the prediction.
+ * pep_gene_structure_check runs exactly these checks: no context, no device, the nucleotides themselves are not read; the message goes to
+ * msg (msg_cap bytes, 0-terminated).
+ * pep_call_times(PEP_CALL_GENE_STRUCTURE): of the newest call, ms[0] the kernel time when pep_set_timing is 2 (else 0), and the bytes it sent to the
+ * device and to the host. */
+int pep_gene_structure(pep_ctx *ctx, const uint8_t *nt, const uint64_t *seq_off, uint32_t n_seq, uint32_t n_pred, const uint32_t *seq, const uint64_t *win_off,
+                       const uint32_t *win_len, const uint8_t *flags, const uint32_t *lp, const uint32_t *allowed_vary, const uint32_t *ref_len, int table4,
+                       int32_t *frame, uint32_t *start_aa, uint32_t *stop_aa, uint8_t *kind);
+int pep_gene_structure_check(const uint64_t *seq_off, uint32_t n_seq, uint32_t n_pred, const uint32_t *seq, const uint64_t *win_off, const uint32_t *win_len,
+                             const uint8_t *flags, const uint32_t *lp, const uint32_t *allowed_vary, const uint32_t *ref_len, char *msg, uint64_t msg_cap);
+
+/* ---- K20: the two counting loops of PEPPAN_parser.
+ * a presence matrix holds fewer genes than this (the counts travel as int32) */
+#define PEP_PARSER_MAX_GENES (1ull << 31)
+/* n_genomes * n_iter of one pep_rarefaction_curves call stays below this (2 GiB of int32 pairs) */
+#define PEP_PARSER_MAX_CURVE_POINTS (1ull << 28)
+/* profiles of one pep_profile_pairs call (two n x n int32 matrices of 1 GiB each at the limit) */
+#define PEP_PARSER_MAX_PROFILES 16384
+
+/* K20a: the loop of writeCurve (PEPPAN_parser.py:74-80).  bits: the presence matrix as bit rows, uint64[n_genomes][W] with
+ * W = (n_genes + 63) / 64, gene e of genome g at bit e % 64 of bits[g * W + e / 64]; the bits of the last word at and above n_genes (the
+ * padding) are zero.  orders: uint32[n_iter][n_genomes], every row a permutation of 0 .. n_genomes - 1.
+ *     curves[(k * n_iter + t) * 2 + 0]   genes present in at least one of the genomes orders[t][0 .. k]   (np.sum(genes >= 1))
+ *     curves[(k * n_iter + t) * 2 + 1]   genes present in all of them                                     (np.sum(genes >= k + 1))
+ * - the reference's array curves[n_genomes][n_iter][2], as int32.  Integer arithmetic only; no size of n_genomes, n_genes or n_iter below
+ * the limits is special.  curves is written only when the call succeeds; on any error the context stays usable.  Everything is checked on
+ * the host before anything is launched:
+ * PEP_ERR_ARG: a null table, n_genomes, n_genes or n_iter of 0, an order row that is no permutation (the message names the row and the
+ * entry), a padding bit that is set (the message names the genome).  PEP_ERR_LIMIT: n_genes >= PEP_PARSER_MAX_GENES, n_genomes * n_iter >=
+ * PEP_PARSER_MAX_CURVE_POINTS.
+ * pep_rarefaction_curves_check runs exactly these checks: no context, no device; the message goes to msg (msg_cap bytes, 0-terminated). */
+int pep_rarefaction_curves(pep_ctx *ctx, const uint64_t *bits, uint32_t n_genomes, uint64_t n_genes, const uint32_t *orders, uint32_t n_iter, int32_t *curves);
+int pep_rarefaction_curves_check(const uint64_t *bits, uint32_t n_genomes, uint64_t n_genes, const uint32_t *orders, uint32_t n_iter, char *msg, uint64_t msg_cap);
+
+/* K20b: the pair loop of getDistance (PEPPAN_parser.py:172-179).  profiles: int32[n][n_genes], a value > 0 is an allele, anything else
+ * "no allele".  For i < j
+ *     presence[i * n + j]   genes with profiles[i][e] > 0 and profiles[j][e] > 0
+ *     shared[i * n + j]     those of them with profiles[i][e] == profiles[j][e]
+ * Every other entry of the two int32[n][n] matrices is 0.  Written only when the call succeeds.
+ * PEP_ERR_ARG: a null table, n or n_genes of 0.  PEP_ERR_LIMIT: n > PEP_PARSER_MAX_PROFILES, n_genes >= PEP_PARSER_MAX_GENES.
+ * pep_profile_pairs_check runs exactly the checks of the sizes: no context, no device. */
+int pep_profile_pairs(pep_ctx *ctx, const int32_t *profiles, uint32_t n, uint64_t n_genes, int32_t *shared, int32_t *presence);
+int pep_profile_pairs_check(uint32_t n, uint64_t n_genes, char *msg, uint64_t msg_cap);
+
+/* pep_call_times(PEP_CALL_PARSER): ms[0] of the newest pep_rarefaction_curves and ms[1] of the newest pep_profile_pairs of the context: their kernel
+ * times when pep_set_timing is 2 (else 0) - each call resets its own slot only -, and the bytes the newer of the two calls sent to the device and to the host */
 
 /* K14 and its two host passes: the consumer of the all-vs-all table (get_similar_pairs, PEPPAN.py:194-294).
  *

@@ -8,7 +8,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpeppan_hip.so')
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 MAX_SEQ_LEN = (1 << 23) - 256          # PEP_MAX_SEQ_LEN: longest single sequence of a packed set
 ALLELE_DIFF_MAX_BYTES = 1 << 31        # PEP_ALLELE_DIFF_MAX_BYTES: output (and bit planes) of one pep_allele_diff call
 
@@ -44,6 +44,7 @@ SIGNATURES = {
     'pep_set_target_groups': (I, P, P, U32),
     'pep_set_result_mode': (I, P, I),
     'pep_set_timing': (I, P, I),
+    'pep_call_times': (I, P, I, P),
     'pep_search': (I, P, P, P),
     'pep_result_size': (I, P, P, P),
     'pep_result_copy': (I, P, P, P),
@@ -66,16 +67,23 @@ SIGNATURES = {
     'pep_overlaps': (I, P, U64, P, P, P, P, F64, F64, P, U64, P),
     'pep_alleles': (I, P, P, P, U32, U64, P, P, U64, U32, P, P, I, P, P, P, U64),
     'pep_allele_diff': (I, P, P, P, P, U64, U32, P, P, P, P, P, U64),
-    'pep_allele_diff_times': (I, P, P, P, P),
     'pep_group_verdicts': (I, P, P, P, P, U64, U32, P, P, P, P, P, P, U64, P, F64, P, P),
     'pep_group_verdicts_check': (I, P, P, P, U64, U32, P, P, P, P, P, P, U64, P, F64, P, U64),
     'pep_verdict_detail_size': (I, P, U32, P),
     'pep_verdict_detail_copy': (I, P, U32, P, P),
     'pep_verdict_result_free': (None, P),
-    'pep_group_verdicts_times': (I, P, P, P),
     'pep_gene_ingroups': (I, P, P, P, P, U64, U32, P, P, P, U64, P, F64, F64, P, P),
     'pep_gene_ingroups_check': (I, P, P, P, U64, U32, P, P, P, U64, P, F64, F64, P, U64),
-    'pep_gene_ingroups_times': (I, P, P, P),
+    'pep_synteny_pairs': (I, P, U32, P, P, U64, P, P, U64, I32, P, P, P, P),
+    'pep_synteny_pairs_copy': (I, P, P, U64, P, U64),
+    'pep_synteny_pairs_check': (I, U32, P, P, U64, P, P, U64, I32, P, U64),
+    'pep_synteny_walk': (I, U32, P, P, P, P, P, P, P, P, P, P, P, U64),
+    'pep_gene_structure': (I, P, P, P, U32, U32, P, P, P, P, P, P, P, I, P, P, P, P),
+    'pep_gene_structure_check': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64),
+    'pep_rarefaction_curves': (I, P, P, U32, U64, P, U32, P),
+    'pep_rarefaction_curves_check': (I, P, U32, U64, P, U32, P, U64),
+    'pep_profile_pairs': (I, P, P, U32, U64, P, P),
+    'pep_profile_pairs_check': (I, U32, U64, P, U64),
     'pep_similar_classify': (I, U64, P, P, P, P, P, P, P, P, P, P, P, F64, F64, P, P, P),
     'pep_similar_scan': (I, U64, P, P, P, P, P, U64, P, P, P, P, P, P, P, P, P, P),
     'pep_pair_support': (I, P, U64, P, P, U64, U64, P, P, P, P, P),
@@ -106,44 +114,15 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
-# ... and of include/peppan_synteny.h (K18), a header with a version of its own; tests/test_synteny_host.py holds this table to it
-SYNTENY_ABI_VERSION = 1
+# limits and codes of the header's K18, K19 and K20 sections; the host test of each kernel holds them to its #defines
 SYNTENY_MAX_PAIRS = 1 << 27              # PEP_SYNTENY_MAX_PAIRS: pairs of one pep_synteny_pairs call
 SYNTENY_MAX_COUNTERS = 1 << 26           # PEP_SYNTENY_MAX_COUNTERS: rank counters of one call, n * (6 * longest list + 14) per group of two members and more
-SYNTENY_SIGNATURES = {
-    'pep_synteny_version': (I,),
-    'pep_synteny_pairs': (I, P, U32, P, P, U64, P, P, U64, I32, P, P, P, P),
-    'pep_synteny_pairs_copy': (I, P, P, U64, P, U64),
-    'pep_synteny_pairs_check': (I, U32, P, P, U64, P, P, U64, I32, P, U64),
-    'pep_synteny_pairs_times': (I, P, P, P),
-    'pep_synteny_walk': (I, U32, P, P, P, P, P, P, P, P, P, P, P, U64),
-}
-
-# ... and of include/peppan_genestruct.h (K19), likewise a header with a version of its own; tests/test_genestruct_host.py holds this table to it
-GENESTRUCT_ABI_VERSION = 1
 GENESTRUCT_MAX_WINDOW = 1 << 31          # PEP_GENESTRUCT_MAX_WINDOW: a window holds fewer nucleotides than this
 GENESTRUCT_NO_STOP = 0xFFFFFFFF          # PEP_GENESTRUCT_NO_STOP: stop_aa of a frame without a stop codon
 GENESTRUCT_KINDS = ('CDS', 'nostart', 'nostop', 'premature_stop')      # PEP_GENESTRUCT_CDS .. PEP_GENESTRUCT_PREMATURE
-GENESTRUCT_SIGNATURES = {
-    'pep_genestruct_version': (I,),
-    'pep_gene_structure': (I, P, P, P, U32, U32, P, P, P, P, P, P, P, I, P, P, P, P),
-    'pep_gene_structure_check': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64),
-    'pep_gene_structure_times': (I, P, P, P, P),
-}
-
-# ... and of include/peppan_parser.h (K20), likewise a header with a version of its own; tests/test_parser_host.py holds this table to it
-PARSER_ABI_VERSION = 1
 PARSER_MAX_GENES = 1 << 31               # PEP_PARSER_MAX_GENES: a presence matrix or a profile holds fewer genes than this
 PARSER_MAX_CURVE_POINTS = 1 << 28        # PEP_PARSER_MAX_CURVE_POINTS: n_genomes * n_iter of one pep_rarefaction_curves call stays below this
 PARSER_MAX_PROFILES = 16384              # PEP_PARSER_MAX_PROFILES: profiles of one pep_profile_pairs call
-PARSER_SIGNATURES = {
-    'pep_parser_version': (I,),
-    'pep_rarefaction_curves': (I, P, P, U32, U64, P, U32, P),
-    'pep_rarefaction_curves_check': (I, P, U32, U64, P, U32, P, U64),
-    'pep_profile_pairs': (I, P, P, U32, U64, P, P),
-    'pep_profile_pairs_check': (I, U32, U64, P, U64),
-    'pep_parser_times': (I, P, P, P, P, P),
-}
 
 
 class PepError(RuntimeError):
@@ -184,6 +163,14 @@ EVENT_CONFLICT, EVENT_SUPPORT = 0, 1
 
 
 INGROUP_MAX_IDEN = (1 << 31) - 1         # column 4 of a gene's table travels as int32
+
+
+class CallTimes(C.Structure):
+    """struct pep_call_times: what pep_call_times reports of the newest call of one of K15 - K20"""
+    _fields_ = [('ms', C.c_double * 4), ('bytes_to_device', C.c_uint64), ('bytes_to_host', C.c_uint64)]
+
+
+CALL_ALLELE_DIFF, CALL_GROUP_VERDICTS, CALL_GENE_INGROUPS, CALL_SYNTENY_PAIRS, CALL_GENE_STRUCTURE, CALL_PARSER, CALL_COUNT = range(7)      # PEP_CALL_*
 
 
 class SupportLimits(C.Structure):
@@ -233,19 +220,13 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(SYNTENY_SIGNATURES.items()) + list(GENESTRUCT_SIGNATURES.items()) + list(PARSER_SIGNATURES.items()):
+    for name, (restype, *argtypes) in SIGNATURES.items():
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     if lib.pep_version() != ABI_VERSION:
         raise PepError('libpeppan_hip.so ABI version mismatch')
-    if lib.pep_synteny_version() != SYNTENY_ABI_VERSION:
-        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_synteny.h)')
-    if lib.pep_genestruct_version() != GENESTRUCT_ABI_VERSION:
-        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_genestruct.h)')
-    if lib.pep_parser_version() != PARSER_ABI_VERSION:
-        raise PepError('libpeppan_hip.so ABI version mismatch (peppan_parser.h)')
     _lib = lib
     return lib
 
@@ -593,7 +574,7 @@ def gene_structure_check(seq_off, seq, win_off, win_len, flags, lp, allowed_vary
 
 
 def pack_presence(presence):
-    """a presence matrix bool[n_genomes, n_genes] as the bit rows of include/peppan_parser.h: uint64[n_genomes, W], gene e at bit e % 64 of word e // 64, padding zero"""
+    """a presence matrix bool[n_genomes, n_genes] as the bit rows of include/peppan_hip.h (K20): uint64[n_genomes, W], gene e at bit e % 64 of word e // 64, padding zero"""
     presence = np.asarray(presence, dtype=bool)
     if presence.ndim != 2:
         raise ValueError('pack_presence: a matrix [n_genomes, n_genes]')
@@ -1570,12 +1551,16 @@ class Context(object):
             res.append((t, e))
         return res
 
+    def _times(self, which):
+        """pep_call_times: the CallTimes record of the context's newest call `which` (CALL_*)"""
+        t = CallTimes()
+        self._call('pep_call_times', which, C.byref(t))
+        return t
+
     def allele_diff_times(self):
         """of the newest allele_diff library call, in ms: (allele_planes, allele_diff) kernel times when set_timing(2) is on, else zeros, and the
         host's wall time from the end of the kernels until the output lay in the caller's buffer"""
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        self._call('pep_allele_diff_times', C.byref(a), C.byref(b), C.byref(c))
-        return a.value, b.value, c.value
+        return tuple(self._times(CALL_ALLELE_DIFF).ms[:3])
 
     # ---- K16
     def group_verdicts(self, packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail=True, out_budget=1 << 30):
@@ -1622,9 +1607,8 @@ class Context(object):
     def group_verdicts_times(self):
         """of the newest pep_group_verdicts library call: (float64[4] kernel times in ms - bit planes, edge, pairs, leaders - when set_timing(2) is on,
         else zeros; bytes that call and the detail copies of its result sent to the host)"""
-        ms, moved = (C.c_double * 4)(), C.c_uint64()
-        self._call('pep_group_verdicts_times', ms, C.byref(moved))
-        return np.array(list(ms)), int(moved.value)
+        t = self._times(CALL_GROUP_VERDICTS)
+        return np.array(t.ms[:4]), int(t.bytes_to_host)
 
     def group_verdicts_totals(self):
         """the same two figures summed over the library calls of the newest group_verdicts (one per part of a split batch)"""
@@ -1644,16 +1628,15 @@ class Context(object):
 
     def gene_ingroups_times(self):
         """of the newest pep_gene_ingroups: (float64[2] kernel times in ms - pairs, finish - when set_timing(2) is on, else zeros; bytes the call sent to the host)"""
-        ms, moved = (C.c_double * 2)(), C.c_uint64()
-        self._call('pep_gene_ingroups_times', ms, C.byref(moved))
-        return np.array(list(ms)), int(moved.value)
+        t = self._times(CALL_GENE_INGROUPS)
+        return np.array(t.ms[:2]), int(t.bytes_to_host)
 
     # ---- K18
     def synteny_pairs(self, member_off, genome, nb_off, nb, n_neighbor):
         """the pair loop of ite_synteny_resolver (PEPPAN.py:1101-1117) for a batch of paralogous names.  Group g is members member_off[g] ..
         member_off[g+1] of genome and of the neighbour lists nb[nb_off[i] .. nb_off[i+1]] (strictly ascending).
         -> (has_conflict bool[G], dc int32[G], conf_off int64[G+1], conf uint32[., 2], walk_off int64[G+1], walk uint32[., 2]): the conflict pairs
-        (m, k) ascending and the pairs with d < dc in the order (d, flag, m, k), as include/peppan_synteny.h states them"""
+        (m, k) ascending and the pairs with d < dc in the order (d, flag, m, k), as include/peppan_hip.h states them"""
         args, n_groups, keep_alive = _synteny_tables(member_off, genome, nb_off, nb, n_neighbor)
         has, dc = np.zeros(max(n_groups, 1), np.uint8), np.zeros(max(n_groups, 1), np.int32)
         conf_off, walk_off = np.zeros(n_groups + 1, np.uint64), np.zeros(n_groups + 1, np.uint64)
@@ -1665,9 +1648,8 @@ class Context(object):
 
     def synteny_times(self):
         """of the newest pep_synteny_pairs: (float64[3] kernel times in ms - count, scans, emit - when set_timing(2) is on, else zeros; bytes it sent to the host)"""
-        ms, moved = (C.c_double * 3)(), C.c_uint64()
-        self._call('pep_synteny_pairs_times', ms, C.byref(moved))
-        return np.array(list(ms)), int(moved.value)
+        t = self._times(CALL_SYNTENY_PAIRS)
+        return np.array(t.ms[:3]), int(t.bytes_to_host)
 
     # ---- K19
     def gene_structure(self, nt, seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len, table4=False):
@@ -1676,7 +1658,7 @@ class Context(object):
         backward and complemented, bits 1-3 = the tried frames 0, 1, 2.  table4: TGA is no stop.
         -> (frame int32[n]: the lowest tried frame that is a CDS or -1; start_aa, stop_aa uint32[n]: of that frame, of the first tried one when there is
         none, GENESTRUCT_NO_STOP without a stop; kind uint8[n]: the outcome of the first tried frame, an index of GENESTRUCT_KINDS), as
-        include/peppan_genestruct.h states them"""
+        include/peppan_hip.h states them"""
         nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
         args, n, keep_alive = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
         if len(nt) != int(keep_alive[0][-1]):
@@ -1688,16 +1670,15 @@ class Context(object):
 
     def gene_structure_times(self):
         """of the newest pep_gene_structure: (kernel time in ms when set_timing(2) is on, else 0; bytes it sent to the device; bytes it sent to the host)"""
-        ms, up, down = C.c_double(), C.c_uint64(), C.c_uint64()
-        self._call('pep_gene_structure_times', C.byref(ms), C.byref(up), C.byref(down))
-        return float(ms.value), int(up.value), int(down.value)
+        t = self._times(CALL_GENE_STRUCTURE)
+        return float(t.ms[0]), int(t.bytes_to_device), int(t.bytes_to_host)
 
     # ---- K20
     def rarefaction_curves(self, bits, n_genes, orders):
         """the loop of writeCurve (PEPPAN_parser.py:74-80).  bits: the presence matrix as bit rows uint64[n_genomes, W] (pack_presence), n_genes its genes,
         orders: [n_iter, n_genomes], every row a permutation of the genomes.
         -> int64[n_genomes, n_iter, 2]: genes in at least one / in all of the first k + 1 genomes of order t at [k, t], the reference's `curves`, as
-        include/peppan_parser.h states them"""
+        include/peppan_hip.h states them"""
         args, n, n_iter, keep_alive = _curve_tables(bits, n_genes, orders)
         curves = np.zeros((max(n, 1), max(n_iter, 1), 2), np.int32)
         self._call('pep_rarefaction_curves', *args, _ptr(curves))
@@ -1727,9 +1708,8 @@ class Context(object):
     def parser_times(self):
         """of the newest pep_rarefaction_curves and pep_profile_pairs: (their kernel times in ms when set_timing(2) is on, else 0; bytes the newer of the two
         calls sent to the device; bytes it sent to the host)"""
-        ms_curves, ms_pairs, up, down = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()
-        self._call('pep_parser_times', C.byref(ms_curves), C.byref(ms_pairs), C.byref(up), C.byref(down))
-        return float(ms_curves.value), float(ms_pairs.value), int(up.value), int(down.value)
+        t = self._times(CALL_PARSER)
+        return float(t.ms[0]), float(t.ms[1]), int(t.bytes_to_device), int(t.bytes_to_host)
 
     # ---- K13
     def sha1(self, seqs):

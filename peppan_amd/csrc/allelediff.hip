@@ -110,7 +110,8 @@ int pep_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row
     if (n_groups && h_grp_off[n_groups] && !h_grp_rows) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
     if (n_rows && h_row_off[n_rows] && !h_packed) return pep_fail(ctx, PEP_ERR_ARG, "pep_allele_diff: null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->k15_ms[0] = ctx->k15_ms[1] = ctx->k15_ms[2] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_ALLELE_DIFF];
+    times = {};
     if (n_groups == 0) return PEP_OK;
     const GroupTables T{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows};
     const GroupSpec S{"pep_allele_diff: ", "output", "tiles of pairs", 1};
@@ -140,8 +141,8 @@ int pep_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row
         return PEP_OK;
     }
     DevBuf *W = ctx->ws;
-    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 8, 0}}, ctx->k15_ms[0]));
-    pep_timed_stage(ctx, ctx->k15_ms[1], [&] {
+    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 8, 0}}, times.ms[0]));
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(allele_diff, dim3((unsigned)L.tiles.size()), dim3(256), 0, ctx->stream, W[K15_WS_TILES].as<const DiffTile>(), W[K15_WS_GROUPS].as<const GroupRec>(),
                            W[K15_WS_GRP_ROWS].as<const uint32_t>(), W[K15_WS_PLANE_OFF].as<const uint64_t>(), W[K15_WS_PLANES].as<const unsigned long long>(), W[K15_WS_OUT].as<int2>());
     });
@@ -162,16 +163,7 @@ int pep_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row
     }
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    ctx->k15_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - copy_t0).count();
-    return PEP_OK;
-}
-
-int pep_allele_diff_times(const pep_ctx *ctx, double *ms_planes, double *ms_pairs, double *ms_copy_back)
-{
-    if (!ctx || !ms_planes || !ms_pairs || !ms_copy_back) return PEP_ERR_ARG;
-    *ms_planes = ctx->k15_ms[0];
-    *ms_pairs = ctx->k15_ms[1];
-    *ms_copy_back = ctx->k15_ms[2];
+    times.ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - copy_t0).count();
     return PEP_OK;
 }
 

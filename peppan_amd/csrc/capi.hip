@@ -856,6 +856,13 @@ int pep_set_timing(pep_ctx *ctx, int level)
     return PEP_OK;
 }
 
+int pep_call_times(const pep_ctx *ctx, int which, struct pep_call_times *out)
+{
+    if (!ctx || !out || which < 0 || which >= PEP_CALL_COUNT) return PEP_ERR_ARG;
+    *out = ctx->calls[which];
+    return PEP_OK;
+}
+
 int pep_result_labels(const pep_result *r, uint32_t *label, uint32_t n_nodes)
 {
     if (!r || (n_nodes && !label)) return PEP_ERR_ARG;

@@ -10,6 +10,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/peppan_hip.h"
+using CallTimes = struct pep_call_times;     // (the tag alone names the function in C++)
 
 #define PEP_WAVE 64
 // copies of the 1 KiB substitution table in LDS (one per bank group): 32 = conflict-free gather, 16 = half the LDS for at most 2-way conflicts
@@ -251,24 +252,14 @@ struct pep_ctx {
                                             // zero_ok flag still set the next search needs no fill
     DevBuf d_mail_copy;                     // the alignment stage's counter block outside d_zero (trace.hip: emit -> pack_out, K10)
     bool zero_ok[4] = {false, false, false, false};     // which consumer regions of d_zero are still untouched since that fill (PEP_ZC_*)
-    double k15_ms[3] = {0., 0., 0.};         // the newest pep_allele_diff: kernel times (planes, pairs) when pep_set_timing is 2, host time of the output's way back (allelediff.hip)
-    double k16_ms[4] = {0., 0., 0., 0.};     // the newest pep_group_verdicts: kernel times (planes, edge, pairs, leaders) when pep_set_timing is 2 (divergence.hip)
-    uint64_t k16_bytes_to_host = 0;          // ... and what it and the detail copies of its result sent to the host
+    CallTimes calls[PEP_CALL_COUNT] = {};   // pep_call_times: the times and byte counts of the newest call of each of K15 - K20 (the slots: each kernel's section of peppan_hip.h)
     uint64_t k16_serial = 0;                 // counts pep_group_verdicts calls: a pep_verdict_result is live while its serial is the newest
     DevBuf k16_tri, k16_leader;              // grow-only: packed triangles and leaders of the newest pep_group_verdicts (read by pep_verdict_detail_copy)
-    double k17_ms[2] = {0., 0.};             // the newest pep_gene_ingroups: kernel times (pairs, finish) when pep_set_timing is 2 (ingroup.hip)
-    uint64_t k17_bytes_to_host = 0;          // ... and what it sent to the host
-    DevBuf k17[11];                          // grow-only: its tables, work list and outputs (the slots: ingroup.hip)
-    double k18_ms[3] = {0., 0., 0.};         // the newest pep_synteny_pairs: kernel times (count, scans, emit) when pep_set_timing is 2 (synteny.hip)
-    uint64_t k18_bytes_to_host = 0;          // ... and what it and its pep_synteny_pairs_copy sent to the host
-    uint64_t k18_n_conf = 0, k18_n_walk = 0; // the pairs its two lists hold, waiting on the device for pep_synteny_pairs_copy
+    DevBuf k17[11];                          // grow-only, pep_gene_ingroups: its tables, work list and outputs (the slots: ingroup.hip)
+    uint64_t k18_n_conf = 0, k18_n_walk = 0; // the pairs the two lists of the newest pep_synteny_pairs hold, waiting on the device for pep_synteny_pairs_copy
     DevBuf k18[18];                          // grow-only: its tables, counters and the two lists (the slots: synteny.hip)
-    double k19_ms = 0.;                      // the newest pep_gene_structure: kernel time when pep_set_timing is 2 (genestruct.hip)
-    uint64_t k19_bytes_to_device = 0, k19_bytes_to_host = 0;   // ... and what it sent each way
-    DevBuf k19[5];                           // grow-only: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
-    double k20_ms[2] = {0., 0.};             // the newest pep_rarefaction_curves and pep_profile_pairs: their kernel times when pep_set_timing is 2 (parser.hip)
-    uint64_t k20_bytes_to_device = 0, k20_bytes_to_host = 0;   // ... and what the newer of the two sent each way
-    DevBuf k20[6];                           // grow-only: bit rows, orders and curves; profiles and the two pair matrices (the slots: parser.hip)
+    DevBuf k19[5];                           // grow-only, pep_gene_structure: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
+    DevBuf k20[6];                           // grow-only, pep_rarefaction_curves and pep_profile_pairs: bit rows, orders and curves; profiles and the two pair matrices (the slots: parser.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose

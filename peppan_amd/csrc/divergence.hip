@@ -241,8 +241,8 @@ int pep_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_
     if (!detail || (n_groups && !h_verdict)) return pep_fail(ctx, PEP_ERR_ARG, "pep_group_verdicts: null table");
     *detail = nullptr;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    for (double &ms : ctx->k16_ms) ms = 0.;
-    ctx->k16_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_GROUP_VERDICTS];
+    times = {};
     ++ctx->k16_serial;                                              // whatever an earlier result held on the device is about to be overwritten
     const GroupTables T{h_packed, h_row_off, h_row_len, n_rows, n_groups, h_grp_off, h_grp_rows};
     Layout L;
@@ -270,7 +270,7 @@ int pep_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_
                                        {{K16_WS_GENOME, h_grp_genome, n_idx * 4, 4}, {K16_WS_EDGES, L.edges.data(), L.edges.size() * sizeof(EdgePair), sizeof(EdgePair)},
                                         {K16_WS_GD_KEY, gd_key, n_gd * 8, 8}, {K16_WS_GD_VAL, L.gd.data(), L.gd.size() * 8, 0},
                                         {K16_WS_FLAGS, nullptr, (size_t)n_groups * 4, 0}, {K16_WS_VERDICT, nullptr, (size_t)n_groups, 0}, {K16_WS_SPILL, nullptr, (n_idx + 1) * 4, 0}},
-                                       ctx->k16_ms[0]));
+                                       times.ms[0]));
         PEP_HIP(ctx, hipMemsetAsync(W[K16_WS_FLAGS].p, 0, (size_t)n_groups * 4, st));
         const GdTable gd{W[K16_WS_GD_KEY].as<const uint64_t>(), W[K16_WS_GD_VAL].as<const double>(), n_gd, self_id};
         const VGroup *d_groups = W[K15_WS_GROUPS].as<const VGroup>();
@@ -279,21 +279,21 @@ int pep_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_
         const unsigned long long *d_planes = W[K15_WS_PLANES].as<const unsigned long long>();
         uint32_t *d_flags = W[K16_WS_FLAGS].as<uint32_t>();
         if (!L.edges.empty())
-            pep_timed_stage(ctx, ctx->k16_ms[1], [&] {
+            pep_timed_stage(ctx, times.ms[1], [&] {
                 hipLaunchKernelGGL(verdict_edge, dim3((unsigned)ceil_div(L.edges.size(), 4 * K16_EDGE_PER_WAVE)), dim3(256), 0, st, (uint64_t)L.edges.size(),
                                    W[K16_WS_EDGES].as<const EdgePair>(), d_groups, d_grp_rows, d_genome, d_plane_off, d_planes, gd, d_flags);
             });
         if (!L.tiles.empty())
-            pep_timed_stage(ctx, ctx->k16_ms[2], [&] {
+            pep_timed_stage(ctx, times.ms[2], [&] {
                 hipLaunchKernelGGL(verdict_pairs, dim3((unsigned)L.tiles.size()), dim3(256), 0, st, W[K15_WS_TILES].as<const DiffTile>(), d_groups, d_grp_rows, d_genome,
                                    d_plane_off, d_planes, gd, d_flags, ctx->k16_tri.as<int2>());
             });
-        pep_timed_stage(ctx, ctx->k16_ms[3], [&] {
+        pep_timed_stage(ctx, times.ms[3], [&] {
             hipLaunchKernelGGL(verdict_leaders, dim3(n_groups), dim3(256), 0, st, d_groups, (const uint32_t *)d_flags, ctx->k16_tri.as<const int2>(),
                                ctx->k16_leader.as<uint32_t>(), W[K16_WS_SPILL].as<uint32_t>(), W[K16_WS_VERDICT].as<uint8_t>());
         });
         PEP_TRY(pep_d2h_queue(ctx, res->verdict.data(), W[K16_WS_VERDICT].p, n_groups));
-        ctx->k16_bytes_to_host = (uint64_t)n_groups + 4;
+        times.bytes_to_host = (uint64_t)n_groups + 4;
         return group_tables_finish(ctx, K16_SPEC);
     };
     const int rc2 = run();
@@ -327,18 +327,10 @@ int pep_verdict_detail_copy(pep_verdict_result *res, uint32_t g, int32_t *h_tri,
     if (h_leader) PEP_TRY(pep_d2h_queue(ctx, h_leader, ctx->k16_leader.as<const uint32_t>() + res->rows_off[g], n * 4));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    ctx->k16_bytes_to_host += (h_tri ? pairs * 8 : 0) + (h_leader ? n * 4 : 0);
+    ctx->calls[PEP_CALL_GROUP_VERDICTS].bytes_to_host += (h_tri ? pairs * 8 : 0) + (h_leader ? n * 4 : 0);
     return PEP_OK;
 }
 
 void pep_verdict_result_free(pep_verdict_result *res) { delete res; }
-
-int pep_group_verdicts_times(const pep_ctx *ctx, double ms[4], uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
-    for (int k = 0; k < 4; ++k) ms[k] = ctx->k16_ms[k];
-    *bytes_to_host = ctx->k16_bytes_to_host;
-    return PEP_OK;
-}
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // K19: the gene structure of predictions - determineGeneStructure (PEPPAN.py:1193-1229), which write_output runs for every intact prediction (:1468).
 // The reference translates the window in the tried frames with marked starts (transeq, modules/configure.py:160-194: numpy arrays per character, then a
-// string) and searches the strings with find / rfind.  Restated (include/peppan_genestruct.h): per frame the codons are classified M (ATG GTG TTG), X (a stop, or
+// string) and searches the strings with find / rfind.  Restated (include/peppan_hip.h, K19): per frame the codons are classified M (ATG GTG TTG), X (a stop, or
 // any character outside ACGT) or neither; with a = lp / 3, b = (lp + allowed_vary) / 3 the start is the first M in [a, b), else the last M below a, else a; the
 // stop the first X from the start; while the stop lies below b and an M follows it below b, the start moves to that M.
 //   gene_structure   one wavefront per prediction.  A chunk is 64 codons of frame 0 = 192 nucleotides: lane l reads the three of codon 64 c + l (forward, or
@@ -12,7 +12,6 @@
 // Integers only, no LDS, outputs by plain vector stores of lane 0.  What bounds it: byte-granular reads of the window and a short wavefront-serial chain of
 // chunks per prediction.
 #include "common.h"
-#include "../../include/peppan_genestruct.h"
 #include <cstring>
 
 namespace {
@@ -232,8 +231,6 @@ int k19_check(const uint64_t *seq_off, uint32_t n_seq, uint32_t n_pred, const ui
 
 extern "C" {
 
-int pep_genestruct_version(void) { return PEP_GENESTRUCT_ABI_VERSION; }
-
 int pep_gene_structure_check(const uint64_t *seq_off, uint32_t n_seq, uint32_t n_pred, const uint32_t *seq, const uint64_t *win_off, const uint32_t *win_len,
                              const uint8_t *flags, const uint32_t *lp, const uint32_t *allowed_vary, const uint32_t *ref_len, char *msg, uint64_t msg_cap)
 {
@@ -249,8 +246,8 @@ int pep_gene_structure(pep_ctx *ctx, const uint8_t *nt, const uint64_t *seq_off,
     if (!ctx) return PEP_ERR_ARG;
     if (n_pred && (!frame || !start_aa || !stop_aa || !kind)) return pep_fail(ctx, PEP_ERR_ARG, std::string(K19_ME) + "null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->k19_ms = 0.;
-    ctx->k19_bytes_to_device = ctx->k19_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_GENE_STRUCTURE];
+    times = {};
     std::vector<GsItem> items;
     std::string msg;
     const int rc = k19_check(seq_off, n_seq, n_pred, seq, win_off, win_len, flags, lp, allowed_vary, ref_len, &items, msg);
@@ -262,7 +259,7 @@ int pep_gene_structure(pep_ctx *ctx, const uint8_t *nt, const uint64_t *seq_off,
     hipStream_t st = ctx->stream;
     PEP_TRY(pep_tables_to_device(ctx, W, {{K19_NT, nt, n_nt, 16}, {K19_ITEM, items.data(), (size_t)n_pred * sizeof(GsItem), 0}, {K19_START, nullptr, (size_t)n_pred * 4, 0},
                                           {K19_STOP, nullptr, (size_t)n_pred * 4, 0}, {K19_VERDICT, nullptr, n_pred, 0}}));
-    pep_timed_stage(ctx, ctx->k19_ms, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(gene_structure, dim3((unsigned)ceil_div(n_pred, 4)), dim3(256), 0, st, W[K19_NT].as<const uint8_t>(), W[K19_ITEM].as<const GsItem>(), n_pred,
                            table4 ? GS_STOPS_TABLE4 : GS_STOPS, W[K19_START].as<uint32_t>(), W[K19_STOP].as<uint32_t>(), W[K19_VERDICT].as<uint8_t>());
     });
@@ -281,17 +278,8 @@ int pep_gene_structure(pep_ctx *ctx, const uint8_t *nt, const uint64_t *seq_off,
         kind[p] = h_verdict[p] & 3u;
         frame[p] = (int32_t)(h_verdict[p] >> 2) - 1;
     }
-    ctx->k19_bytes_to_device = n_nt + (uint64_t)n_pred * sizeof(GsItem);
-    ctx->k19_bytes_to_host = 9ull * n_pred;
-    return PEP_OK;
-}
-
-int pep_gene_structure_times(const pep_ctx *ctx, double *kernel_ms, uint64_t *bytes_to_device, uint64_t *bytes_to_host)
-{
-    if (!ctx || !kernel_ms || !bytes_to_device || !bytes_to_host) return PEP_ERR_ARG;
-    *kernel_ms = ctx->k19_ms;
-    *bytes_to_device = ctx->k19_bytes_to_device;
-    *bytes_to_host = ctx->k19_bytes_to_host;
+    times.bytes_to_device = n_nt + (uint64_t)n_pred * sizeof(GsItem);
+    times.bytes_to_host = 9ull * n_pred;
     return PEP_OK;
 }
 

@@ -173,8 +173,8 @@ int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden,
     if (!ctx) return PEP_ERR_ARG;
     if ((n_rows && !h_keep) || (n_genes && !h_gene_score)) return pep_fail(ctx, PEP_ERR_ARG, "pep_gene_ingroups: null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->k17_ms[0] = ctx->k17_ms[1] = 0.;
-    ctx->k17_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_GENE_INGROUPS];
+    times = {};
     Layout L;
     std::string msg;
     const int rc = k17_check(genome, iden, score, n_rows, n_genes, gene_off, gd_key, gd_val, n_gd, gd_default, self_id, thr, L, msg);
@@ -182,7 +182,7 @@ int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden,
     if (n_genes == 0) return PEP_OK;
     if (L.work.empty()) {                                               // empty genes only: they score 0
         memset(h_gene_score, 0, (size_t)n_genes * 8);
-        ctx->k17_bytes_to_host = 8ull * n_genes;
+        times.bytes_to_host = 8ull * n_genes;
         return PEP_OK;
     }
     DevBuf *W = ctx->k17;
@@ -198,11 +198,11 @@ int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden,
     const IgWork *d_work = W[K17_WORK].as<const IgWork>();
     const uint64_t *d_gene_off = W[K17_GENE_OFF].as<const uint64_t>();
     const dim3 grid((unsigned)L.work.size());
-    pep_timed_stage(ctx, ctx->k17_ms[0], [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(ingroup_pairs, grid, dim3(K17_CHUNK), 0, st, d_work, d_gene_off, W[K17_GENOME].as<const uint32_t>(), W[K17_IDEN].as<const int32_t>(), gd, thr,
                            W[K17_RAW].as<uint8_t>());
     });
-    pep_timed_stage(ctx, ctx->k17_ms[1], [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(ingroup_finish, grid, dim3(K17_CHUNK), 0, st, d_work, d_gene_off, W[K17_FIRST].as<const uint32_t>(), W[K17_SCORE].as<const long long>(),
                            W[K17_RAW].as<const uint8_t>(), W[K17_KEEP].as<uint8_t>(), W[K17_GENE_SCORE].as<unsigned long long>());
     });
@@ -216,16 +216,7 @@ int pep_gene_ingroups(pep_ctx *ctx, const uint32_t *genome, const int32_t *iden,
     pep_d2h_finish(ctx);
     memcpy(h_keep, keep.data(), n_rows);
     memcpy(h_gene_score, gene_score.data(), (size_t)n_genes * 8);
-    ctx->k17_bytes_to_host = n_rows + 8ull * n_genes;
-    return PEP_OK;
-}
-
-int pep_gene_ingroups_times(const pep_ctx *ctx, double ms[2], uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
-    ms[0] = ctx->k17_ms[0];
-    ms[1] = ctx->k17_ms[1];
-    *bytes_to_host = ctx->k17_bytes_to_host;
+    times.bytes_to_host = n_rows + 8ull * n_genes;
     return PEP_OK;
 }
 

@@ -1,7 +1,7 @@
 // K20: the two counting loops of PEPPAN_parser - writeCurve (PEPPAN_parser.py:63-115, its loop :74-80) and getDistance (:172-179, behind writeCGAV).
 // Both are integer and data-parallel; the floats made of their counts (curve fits, -log) stay on the host (peppan_amd/panparser.py).
 //   rarefaction      the reference adds every genome of a shuffled order to a per-gene counter and sums `genes >= 1` and `genes >= k + 1` over all genes after each,
-//                    n_iter x n_genomes times.  Restated over bit rows (include/peppan_parser.h): pan = popcount of the running OR, core = popcount of the running
+//                    n_iter x n_genomes times.  Restated over bit rows (include/peppan_hip.h, K20): pan = popcount of the running OR, core = popcount of the running
 //                    AND, which starts from the valid-bit mask so that padding never counts.  One workgroup per order.  A slice is 1 024 words (65 536 genes):
 //                    every lane keeps the running OR and AND of its four words in registers across the walk, loads its words of row order[k] (consecutive lanes,
 //                    consecutive words; the next row is on its way while this one is judged) and forms two deltas - newly in pan, newly out of core.  A ballot that
@@ -15,7 +15,6 @@
 // Integers only, plain vector stores.  The walk is bound by the latency of one row load per step (the matrix is cache-resident), the pairs by VALU.
 #include "common.h"
 #include "allelediff_tile.h"
-#include "../../include/peppan_parser.h"
 #include <algorithm>
 
 namespace {
@@ -207,8 +206,6 @@ int k20_pairs_check(uint32_t n, uint64_t n_genes, std::string &msg)
 
 extern "C" {
 
-int pep_parser_version(void) { return PEP_PARSER_ABI_VERSION; }
-
 int pep_rarefaction_curves_check(const uint64_t *bits, uint32_t n_genomes, uint64_t n_genes, const uint32_t *orders, uint32_t n_iter, char *msg, uint64_t msg_cap)
 {
     std::string text;
@@ -221,8 +218,9 @@ int pep_rarefaction_curves(pep_ctx *ctx, const uint64_t *bits, uint32_t n_genome
     if (!ctx) return PEP_ERR_ARG;
     if (!curves) return pep_fail(ctx, PEP_ERR_ARG, std::string(K20_CURVES_ME) + "null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->k20_ms[0] = 0.;
-    ctx->k20_bytes_to_device = ctx->k20_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_PARSER];                  // shared with pep_profile_pairs: slot 0 is this call's, the byte counts the newer call's
+    times.ms[0] = 0.;
+    times.bytes_to_device = times.bytes_to_host = 0;
     std::string msg;
     const int rc = k20_curves_check(bits, n_genomes, n_genes, orders, n_iter, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
@@ -230,7 +228,7 @@ int pep_rarefaction_curves(pep_ctx *ctx, const uint64_t *bits, uint32_t n_genome
     const size_t bits_bytes = (size_t)n_genomes * W * 8, order_bytes = (size_t)n_genomes * n_iter * 4, curve_bytes = (size_t)n_genomes * n_iter * 8;
     DevBuf *B = ctx->k20;
     PEP_TRY(pep_tables_to_device(ctx, B, {{K20_BITS, bits, bits_bytes, 0}, {K20_ORDERS, orders, order_bytes, 0}, {K20_CURVES, nullptr, curve_bytes, 0}}));
-    pep_timed_stage(ctx, ctx->k20_ms[0], [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(rarefaction, dim3(n_iter), dim3(K20_BLOCK), 0, ctx->stream, B[K20_BITS].as<const unsigned long long>(), n_genomes, n_genes, W,
                            B[K20_ORDERS].as<const uint32_t>(), n_iter, B[K20_CURVES].as<int2>());
     });
@@ -238,8 +236,8 @@ int pep_rarefaction_curves(pep_ctx *ctx, const uint64_t *bits, uint32_t n_genome
     PEP_TRY(pep_d2h_queue(ctx, curves, B[K20_CURVES].p, curve_bytes));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    ctx->k20_bytes_to_device = bits_bytes + order_bytes;
-    ctx->k20_bytes_to_host = curve_bytes;
+    times.bytes_to_device = bits_bytes + order_bytes;
+    times.bytes_to_host = curve_bytes;
     return PEP_OK;
 }
 
@@ -255,8 +253,9 @@ int pep_profile_pairs(pep_ctx *ctx, const int32_t *profiles, uint32_t n, uint64_
     if (!ctx) return PEP_ERR_ARG;
     if (!profiles || !shared || !presence) return pep_fail(ctx, PEP_ERR_ARG, std::string(K20_PAIRS_ME) + "null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->k20_ms[1] = 0.;
-    ctx->k20_bytes_to_device = ctx->k20_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_PARSER];                  // shared with pep_rarefaction_curves: slot 1 is this call's, the byte counts the newer call's
+    times.ms[1] = 0.;
+    times.bytes_to_device = times.bytes_to_host = 0;
     std::string msg;
     const int rc = k20_pairs_check(n, n_genes, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
@@ -266,7 +265,7 @@ int pep_profile_pairs(pep_ctx *ctx, const int32_t *profiles, uint32_t n, uint64_
     PEP_HIP(ctx, hipMemsetAsync(B[K20_SHARED].p, 0, out_bytes, ctx->stream));         // the kernel stores the pairs i < j alone
     PEP_HIP(ctx, hipMemsetAsync(B[K20_PRESENCE].p, 0, out_bytes, ctx->stream));
     const unsigned tiles = (unsigned)ceil_div(n, K15_TILE);
-    pep_timed_stage(ctx, ctx->k20_ms[1], [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(profile_pairs, dim3(tiles, tiles), dim3(256), 0, ctx->stream, B[K20_PROFILES].as<const int32_t>(), n, n_genes, B[K20_SHARED].as<int32_t>(),
                            B[K20_PRESENCE].as<int32_t>());
     });
@@ -275,18 +274,8 @@ int pep_profile_pairs(pep_ctx *ctx, const int32_t *profiles, uint32_t n, uint64_
     PEP_TRY(pep_d2h_queue(ctx, presence, B[K20_PRESENCE].p, out_bytes));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    ctx->k20_bytes_to_device = prof_bytes;
-    ctx->k20_bytes_to_host = 2 * out_bytes;
-    return PEP_OK;
-}
-
-int pep_parser_times(const pep_ctx *ctx, double *ms_curves, double *ms_pairs, uint64_t *bytes_to_device, uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms_curves || !ms_pairs || !bytes_to_device || !bytes_to_host) return PEP_ERR_ARG;
-    *ms_curves = ctx->k20_ms[0];
-    *ms_pairs = ctx->k20_ms[1];
-    *bytes_to_device = ctx->k20_bytes_to_device;
-    *bytes_to_host = ctx->k20_bytes_to_host;
+    times.bytes_to_device = prof_bytes;
+    times.bytes_to_host = 2 * out_bytes;
     return PEP_OK;
 }
 

@@ -1,6 +1,6 @@
 // K18: neighbourhood paralog splitting - ite_synteny_resolver (PEPPAN.py:1097-1151) as synteny_resolver (:1153-1191) runs it for every paralogous name.
 // The reference computes, in a Python double loop over the members of a name, a distance for every pair from the intersection of two neighbour
-// sets, sorts all pairs and walks them.  Restated without an order (include/peppan_synteny.h): with dc the smallest distance of a conflict pair
+// sets, sorts all pairs and walks them.  Restated without an order (include/peppan_hip.h, K18): with dc the smallest distance of a conflict pair
 // (same genome, d > 0), the walk reads exactly the pairs with d < dc in the order (d, flag, m, k) and stops.  The device makes the two sparse lists -
 // the conflict pairs and the walked pairs, ranked - and the host walks them (pep_synteny_walk below, no context).
 //   synteny_count    one wavefront per member m (row): lanes take the members k > m, 64 at a time.  The row's list sits in eight uniform registers
@@ -16,7 +16,6 @@
 // Integers only, plain vector stores, no LDS: the lists of a group of 4 000 members are 100 KB and stay in L2.  What bounds it: a row is one
 // wavefront's, so a group's longest row (n - 1 pairs) is serial in chunks of 64, and a tiny group fills one lane per pair.
 #include "common.h"
-#include "../../include/peppan_synteny.h"
 #include <algorithm>
 #include <cstring>
 
@@ -270,8 +269,8 @@ int k18_check(uint32_t n_groups, const uint64_t *member_off, const uint32_t *gen
 int k18_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb,
               uint64_t n_nb, int32_t n_neighbor, uint8_t *has_conflict, int32_t *dc, uint64_t *conf_off, uint64_t *walk_off)
 {
-    ctx->k18_ms[0] = ctx->k18_ms[1] = ctx->k18_ms[2] = 0.;
-    ctx->k18_bytes_to_host = 0;
+    CallTimes &times = ctx->calls[PEP_CALL_SYNTENY_PAIRS];
+    times = {};
     ctx->k18_n_conf = ctx->k18_n_walk = 0;
     Layout L;
     std::string msg;
@@ -302,13 +301,13 @@ int k18_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const
     uint32_t *d_dc = W[K18_DC].as<uint32_t>(), *d_cnt = W[K18_CNT].as<uint32_t>(), *d_pos = W[K18_POS].as<uint32_t>();
     uint32_t *d_conf_cnt = W[K18_CONF_CNT].as<uint32_t>(), *d_conf_pos = W[K18_CONF_POS].as<uint32_t>();
     const dim3 rows((unsigned)ceil_div(n_members, 4));
-    pep_timed_stage(ctx, ctx->k18_ms[0], [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(synteny_count, rows, dim3(256), 0, st, T, d_cnt, d_conf_cnt, d_dc);
         hipLaunchKernelGGL(synteny_mask, dim3(n_groups), dim3(256), 0, st, T, (const uint32_t *)d_dc, d_cnt);
     });
     PEP_HIP(ctx, hipGetLastError());
     int scan_rc = PEP_OK;
-    pep_timed_stage(ctx, ctx->k18_ms[1], [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         scan_rc = pep_scan_u32(ctx, d_cnt, d_pos, n_cnt, W[K18_SCAN_TMP]);
         if (scan_rc == PEP_OK) scan_rc = pep_scan_u32(ctx, d_conf_cnt, d_conf_pos, n_members, W[K18_SCAN_TMP]);
         if (scan_rc == PEP_OK)
@@ -333,7 +332,7 @@ int k18_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const
     PEP_TRY(dev_reserve(ctx, W[K18_CONF_OUT], std::max<uint64_t>(n_conf, 1) * 8));
     PEP_TRY(dev_reserve(ctx, W[K18_WALK_OUT], std::max<uint64_t>(n_walk, 1) * 8));
     if (n_conf) {
-        pep_timed_stage(ctx, ctx->k18_ms[2], [&] {
+        pep_timed_stage(ctx, times.ms[2], [&] {
             hipLaunchKernelGGL(synteny_emit, rows, dim3(256), 0, st, T, (const uint32_t *)d_dc, d_pos, (const uint32_t *)d_conf_pos, W[K18_CONF_OUT].as<uint2>(), n_conf,
                                W[K18_WALK_OUT].as<uint2>(), n_walk);
         });
@@ -350,7 +349,7 @@ int k18_pairs(pep_ctx *ctx, uint32_t n_groups, const uint64_t *member_off, const
     for (uint32_t g = 0; g <= n_groups; ++g) conf_off[g] = h_conf[g], walk_off[g] = h_walk[g];
     ctx->k18_n_conf = n_conf;
     ctx->k18_n_walk = n_walk;
-    ctx->k18_bytes_to_host = 12ull * n_groups + 12 + (n_conf ? 4 : 0);     // dc and two offsets per group, the two totals, the fault word after each pass
+    times.bytes_to_host = 12ull * n_groups + 12 + (n_conf ? 4 : 0);     // dc and two offsets per group, the two totals, the fault word after each pass
     return PEP_OK;
 }
 
@@ -368,8 +367,6 @@ struct Walker {
 }  // namespace
 
 extern "C" {
-
-int pep_synteny_version(void) { return PEP_SYNTENY_ABI_VERSION; }
 
 int pep_synteny_pairs_check(uint32_t n_groups, const uint64_t *member_off, const uint32_t *genome, uint64_t n_members, const uint64_t *nb_off, const uint32_t *nb,
                             uint64_t n_nb, int32_t n_neighbor, char *msg, uint64_t msg_cap)
@@ -405,15 +402,7 @@ int pep_synteny_pairs_copy(pep_ctx *ctx, uint32_t *conf, uint64_t n_conf, uint32
     pep_d2h_finish(ctx);
     if (n_conf) memcpy(conf, h_conf.data(), n_conf * 8);
     if (n_walk) memcpy(walk, h_walk.data(), n_walk * 8);
-    ctx->k18_bytes_to_host += 8 * (n_conf + n_walk);
-    return PEP_OK;
-}
-
-int pep_synteny_pairs_times(const pep_ctx *ctx, double ms[3], uint64_t *bytes_to_host)
-{
-    if (!ctx || !ms || !bytes_to_host) return PEP_ERR_ARG;
-    for (int k = 0; k < 3; ++k) ms[k] = ctx->k18_ms[k];
-    *bytes_to_host = ctx->k18_bytes_to_host;
+    ctx->calls[PEP_CALL_SYNTENY_PAIRS].bytes_to_host += 8 * (n_conf + n_walk);
     return PEP_OK;
 }
 

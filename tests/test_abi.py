@@ -45,8 +45,8 @@ def test_signature_table_is_the_header():
     """peppan_amd._native.SIGNATURES states the return and parameter types of every prototype of include/peppan_hip.h, and load_library() has given them to ctypes"""
     from peppan_amd import _native as N
     protos = _header_prototypes()
-    assert len(protos) == 85 and sum(len(params) for _, _, params in protos) == 531          # (a prototype the pattern misses shows here)
-    assert {name for _, name, _ in protos} == set(N.SIGNATURES) == set(N.EXPORTS) and len(N.EXPORTS) == 85
+    assert len(protos) == 93 and sum(len(params) for _, _, params in protos) == 618          # (a prototype the pattern misses shows here)
+    assert {name for _, name, _ in protos} == set(N.SIGNATURES) == set(N.EXPORTS) and len(N.EXPORTS) == len(protos)
     lib = N.load_library()
     for ret, name, params in protos:
         restype, *argtypes = N.SIGNATURES[name]
@@ -80,12 +80,12 @@ def test_direct_callers_get_the_full_return_width():
 
 
 HANDLE_FIRST = ['pep_rescore_nt', 'pep_rescore_codons', 'pep_components', 'pep_components_of_hits', 'pep_set_grouping', 'pep_linclust', 'pep_overlaps', 'pep_alleles',
-                'pep_sha1', 'pep_dedup', 'pep_allele_diff', 'pep_allele_diff_times', 'pep_group_verdicts', 'pep_verdict_detail_size', 'pep_verdict_detail_copy',
-                'pep_group_verdicts_times', 'pep_gene_ingroups', 'pep_gene_ingroups_times']
+                'pep_sha1', 'pep_dedup', 'pep_allele_diff', 'pep_group_verdicts', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_gene_ingroups',
+                'pep_call_times', 'pep_synteny_pairs', 'pep_synteny_pairs_copy', 'pep_gene_structure', 'pep_rarefaction_curves', 'pep_profile_pairs']
 
 
 def test_null_handle_is_an_argument_error():
-    """every entry point of K7 and K9 - K17 that takes a pep_ctx * or a pep_verdict_result * first answers a null one with PEP_ERR_ARG, whatever else it is given: the
+    """every entry point of K7 and K9 - K20 that takes a pep_ctx * or a pep_verdict_result * first answers a null one with PEP_ERR_ARG, whatever else it is given: the
     check of the handle comes before anything that would need a device"""
     from peppan_amd import _native as N
     lib = N.load_library()
@@ -93,6 +93,19 @@ def test_null_handle_is_an_argument_error():
         restype, *argtypes = N.SIGNATURES[name]
         assert restype is C.c_int and argtypes[0] is C.c_void_p, name
         assert getattr(lib, name)(*[None if t is C.c_void_p else t(0) for t in argtypes]) == -2, name          # PEP_ERR_ARG
+
+
+def test_call_times_refuses_a_bad_selector_and_a_null_record():
+    """pep_call_times answers which = -1, which = PEP_CALL_COUNT and a null out with PEP_ERR_ARG (here without a context, which alone is refused already; on a live
+    context: tests/test_gpu_ctx_resources.py); PEP_CALL_COUNT and the six selectors of the header are _native's"""
+    from peppan_amd import _native as N
+    lib = N.load_library()
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
+    names = ('ALLELE_DIFF', 'GROUP_VERDICTS', 'GENE_INGROUPS', 'SYNTENY_PAIRS', 'GENE_STRUCTURE', 'PARSER', 'COUNT')
+    assert [int(re.search(r'#define PEP_CALL_%s (\d+)\b' % n, hdr).group(1)) for n in names] == [getattr(N, 'CALL_' + n) for n in names] == list(range(7))
+    out = N.CallTimes()
+    for which, record in ((-1, C.byref(out)), (N.CALL_COUNT, C.byref(out)), (0, None), (0, C.byref(out))):
+        assert lib.pep_call_times(None, which, record) == -2          # PEP_ERR_ARG
 
 
 def test_struct_layouts_match_header(tmp_path):
@@ -103,12 +116,14 @@ def test_struct_layouts_match_header(tmp_path):
     probes = [('pep_search_params', 'min_id_pct'), ('pep_search_params', 'dbsize'), ('pep_search_params', 'ka_lambda'), ('pep_search_params', 'hsp_mode'),
               ('pep_search_params', 't_index_base'), ('pep_stats', 'cells_swept_trace'), ('pep_stats', 'candidates_settled'), ('pep_stats', 'cells_settled'), ('pep_stats', 'ms_seed'), ('pep_stats', 'ms_seed_match'),
               ('pep_hit', 'cigar_off'), ('pep_hit', 'cells'), ('pep_nt_hit', 'cigar_off'), ('pep_locus', 'cigar_off'),
-              ('pep_mat_cols', 'iden'), ('pep_mat_cols', 'arena'), ('pep_mat_cols', 'rid'), ('pep_mat_cols', 'score_is_int')]
+              ('pep_mat_cols', 'iden'), ('pep_mat_cols', 'arena'), ('pep_mat_cols', 'rid'), ('pep_mat_cols', 'score_is_int'),
+              ('pep_call_times', 'bytes_to_device'), ('pep_call_times', 'bytes_to_host')]
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "peppan_hip.h"\nint main(void) {\n'
     for st in ('pep_search_params', 'pep_stats', 'pep_hit', 'pep_nt_hit', 'pep_locus', 'pep_query_meta', 'pep_target_meta', 'pep_mat_cols'):
         src += '  printf("%s %%zu\\n", sizeof(%s));\n' % (st, st)
+    src += '  printf("pep_call_times %zu\\n", sizeof(struct pep_call_times));\n'          # (known by its tag: the function has the name)
     for st, f in probes:
-        src += '  printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (st, f, st, f)
+        src += '  printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (st, f, 'struct pep_call_times' if st == 'pep_call_times' else st, f)
     src += '  return 0;\n}\n'
     (tmp_path / 'probe.c').write_text(src)
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), '-o', str(tmp_path / 'probe'), str(tmp_path / 'probe.c')])
@@ -118,8 +133,9 @@ def test_struct_layouts_match_header(tmp_path):
     assert got['pep_hit'] == N.HIT_DTYPE.itemsize == 64 and got['pep_nt_hit'] == N.NT_HIT_DTYPE.itemsize == 40
     assert got['pep_locus'] == N.LOCUS_DTYPE.itemsize == 32 and got['pep_mat_cols'] == C.sizeof(N.MatCols)
     assert got['pep_query_meta'] == N.QUERY_META_DTYPE.itemsize == 16 and got['pep_target_meta'] == N.TARGET_META_DTYPE.itemsize == 16
+    assert got['pep_call_times'] == C.sizeof(N.CallTimes) == 48
     for st, f in probes:
-        mirror = {'pep_search_params': N.SearchParams, 'pep_stats': N.Stats, 'pep_mat_cols': N.MatCols}.get(st)
+        mirror = {'pep_search_params': N.SearchParams, 'pep_stats': N.Stats, 'pep_mat_cols': N.MatCols, 'pep_call_times': N.CallTimes}.get(st)
         if mirror is not None:
             assert got[st + '.' + f] == getattr(mirror, f).offset, (st, f)
         else:

@@ -1,8 +1,7 @@
 """K19 (the gene structure of predictions, PEPPAN.py:1193-1229) without a GPU: the g23 fixture recorded from the reference's own
-determineGeneStructure against the independent restatement in plain loops (tests/genestruct_helpers.py), the header of its own
-(include/peppan_genestruct.h) against the signature table, the table checks of pep_gene_structure, which need no device, and the host half
+determineGeneStructure against the independent restatement in plain loops (tests/genestruct_helpers.py), its section of
+include/peppan_hip.h against _native's limits and codes, the table checks of pep_gene_structure, which need no device, and the host half
 of peppan_amd.genestruct - texts and coordinates from hand-made device outputs."""
-import ctypes as C
 import os
 import re
 import sys
@@ -54,56 +53,15 @@ def test_marks_are_the_marked_start_translation():
     assert rc('acgTn-x') == 'NNNACGT'
 
 
-SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'double': C.c_double}
-
-
-def _prototypes(header):
-    """[(return declaration, name, [parameter declaration])] of every prototype of a header, comments stripped"""
-    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    return [(ret.strip(), name, [] if params.strip() == 'void' else [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-
-
-def _ctypes_of(decl, is_return=False):
-    if decl == 'void':
-        return {None}
-    if '*' in decl or '[' in decl:
-        if re.match(r'(const )?char \*', decl):
-            return {C.c_char_p} if is_return else {C.c_char_p, C.c_void_p}
-        return {C.c_void_p}
-    return {SCALARS[decl.replace('const ', '').split()[0]]}
-
-
-def test_genestruct_signature_table_is_its_header(N):
-    protos = _prototypes('peppan_genestruct.h')
-    assert len(protos) == 4 and sum(len(p) for _, _, p in protos) == 33             # (a prototype the pattern misses shows here)
-    assert {name for _, name, _ in protos} == set(N.GENESTRUCT_SIGNATURES)
-    assert not set(N.GENESTRUCT_SIGNATURES) & (set(N.SIGNATURES) | set(N.SYNTENY_SIGNATURES))
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.GENESTRUCT_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert restype in _ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in _ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-    hdr = open(os.path.join(ROOT, 'include', 'peppan_genestruct.h')).read()
-    assert re.search(r'#define PEP_GENESTRUCT_ABI_VERSION 1\b', hdr) and lib.pep_genestruct_version() == N.GENESTRUCT_ABI_VERSION == 1
+def test_genestruct_section_of_the_header(N):
+    """the K19 section of include/peppan_hip.h cites what it replaces, and its limits and codes are _native's (the prototypes: tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
     assert 'PEPPAN.py:1193-1229' in hdr
     assert int(re.search(r'#define PEP_GENESTRUCT_MAX_WINDOW \(1ull << (\d+)\)', hdr).group(1)) == N.GENESTRUCT_MAX_WINDOW.bit_length() - 1 == 31
     assert int(re.search(r'#define PEP_GENESTRUCT_NO_STOP (0x[0-9A-F]+)u', hdr).group(1), 16) == N.GENESTRUCT_NO_STOP == NO_STOP
     for k, name in enumerate(('CDS', 'NOSTART', 'NOSTOP', 'PREMATURE')):
         assert re.search(r'#define PEP_GENESTRUCT_%s %d\b' % (name, k), hdr)
     assert N.GENESTRUCT_KINDS == KINDS
-
-
-def test_the_other_two_headers_are_untouched(N):
-    protos = _prototypes('peppan_hip.h')
-    assert len(protos) == 85 and sum(len(p) for _, _, p in protos) == 531 and len(N.EXPORTS) == 85
-    assert N.ABI_VERSION == 18 and N.load_library().pep_version() == 18
-    assert not [name for _, name, _ in protos if 'gene_structure' in name or 'genestruct' in name]
-    assert len(_prototypes('peppan_synteny.h')) == 6 and N.load_library().pep_synteny_version() == 1
 
 
 GOOD = dict(seq_off=[0, 100, 100, 350], seq=[0, 2, 2, 1], win_off=[0, 10, 250, 0], win_len=[100, 240, 0, 0], flags=[2, 15, 9, 4], lp=[0, 60, 7, 0],

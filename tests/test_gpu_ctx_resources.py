@@ -115,3 +115,43 @@ def test_a_staged_result_is_copied_out_before_its_context_goes(N):
         assert np.array_equal(hits, want_hits) and np.array_equal(cigar, want_cigar)
     finally:
         lib.pep_result_free(r)
+
+
+def test_the_six_call_records_do_not_share_a_slot(N):
+    """pep_call_times keeps one record per kernel of K15 - K20 in the context.  Each of the six calls runs once, at the smallest shape that launches its
+    kernels, on one context with every phase timed; then all six records are read: the byte counts are those the kernel's own test states for the shape, the
+    slots a kernel fills are >= 0, every slot and byte count it does not use is exactly 0 - a kernel writing into another's record would show in one of
+    them - and a second K19 call leaves the other five records bit for bit as they were.  A bad selector or a null record is refused on a live context too."""
+    from peppan_amd import orthofilter as OF
+    lib = N.load_library()
+    gd = OF.gd_table({(1, 2): (0.01, 0.1)}, 0.002, 3)
+    packed, row_off, row_len, index = verdict_table([pack_codes(np.array([[1, 2, 3], [1, 2, 4]]))], [3])
+    with N.Context(0) as ctx:
+        ctx.set_timing(2)
+        ctx.allele_diff(packed, row_off, row_len, index, 3)
+        (verdict, tri, leader), = ctx.group_verdicts(packed, row_off, row_len, index, [np.array([1, 2])], [False], gd, 0.002, detail=True)
+        ctx.gene_ingroups([1, 2], [9000, 8000], [100, 90], [0, 2], gd, 0.005, 8800.)
+        has_conflict, _, conf_off, _, walk_off, _ = ctx.synteny_pairs([0, 2], [1, 2], [0, 1, 2], [5, 5], 2)
+        assert not has_conflict[0] and conf_off[-1] == walk_off[-1] == 0          # (two genomes: no conflict pair, so the emit pass has nothing to do)
+        ctx.gene_structure(b'ATGAAA', [0, 6], [0], [0], [6], [2], [0], [0], [6])
+        ctx.rarefaction_curves(N.pack_presence([[True], [False]]), 1, [[1, 0]])
+        ctx.profile_pairs([[1], [2]])
+        # (slots in use, bytes to the device, bytes to the host); K16: a byte per group and the word of flags, and the detail of a verdict-2 group: a pair and two leaders
+        want = {N.CALL_ALLELE_DIFF: (3, 0, 0), N.CALL_GROUP_VERDICTS: (4, 0, 1 + 4 + (8 + 2 * 4 if verdict == 2 else 0)), N.CALL_GENE_INGROUPS: (2, 0, 2 + 8 * 1),
+                N.CALL_SYNTENY_PAIRS: (3, 0, 12 * 1 + 12), N.CALL_GENE_STRUCTURE: (1, 6 + 32 * 1, 9 * 1), N.CALL_PARSER: (2, 2 * 1 * 4, 2 * 2 * 2 * 4)}
+        assert sorted(want) == list(range(N.CALL_COUNT))
+        records = {which: ctx._times(which) for which in want}
+        for which, (used, up, down) in want.items():
+            t = records[which]
+            print('call %d: ms %r, bytes to the device %d, to the host %d' % (which, list(t.ms), t.bytes_to_device, t.bytes_to_host))
+            assert all(ms >= 0 for ms in t.ms[:used]) and list(t.ms[used:]) == [0.] * (4 - used), (which, list(t.ms))
+            assert (t.bytes_to_device, t.bytes_to_host) == (up, down), which
+        ctx.gene_structure(b'ATGAAA', [0, 6], [0], [0], [6], [2], [0], [0], [6])
+        for which in want:
+            if which != N.CALL_GENE_STRUCTURE:
+                assert bytes(ctx._times(which)) == bytes(records[which]), which
+        assert ctx.gene_structure_times()[1:] == (38, 9)
+        out = N.CallTimes()
+        for which, record in ((-1, C.byref(out)), (N.CALL_COUNT, C.byref(out)), (0, None)):
+            assert lib.pep_call_times(ctx._h, which, record) == -2          # PEP_ERR_ARG
+        assert lib.pep_call_times(ctx._h, N.CALL_COUNT - 1, C.byref(out)) == 0

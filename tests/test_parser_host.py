@@ -1,6 +1,6 @@
 """K20 (the counting loops of PEPPAN_parser: writeCurve, PEPPAN_parser.py:63-115, and getDistance, :172-179) without a GPU: the g25 fixture recorded from
-the reference's own functions against the independent restatement in plain loops (tests/parser_helpers.py), the header of its own
-(include/peppan_parser.h) against the signature table, the table checks of the two entry points, which need no device, and the host half of
+the reference's own functions against the independent restatement in plain loops (tests/parser_helpers.py), its section of
+include/peppan_hip.h against _native's limits, the table checks of the two entry points, which need no device, and the host half of
 peppan_amd.panparser - GFF reading, genome orders from a seed, bit packing, recoding, and the three text writers fed with the recorded counts."""
 import ctypes as C
 import os
@@ -141,55 +141,13 @@ def test_profiles_outside_int32_are_recoded_injectively(g25):
     assert PP.getDistance(np.zeros((3, 0))).tolist() == [[0., -np.log(0.5), -np.log(0.5)], [-np.log(0.5), 0., -np.log(0.5)], [-np.log(0.5), -np.log(0.5), 0.]]
 
 
-SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'double': C.c_double}
-
-
-def _prototypes(header):
-    """[(return declaration, name, [parameter declaration])] of every prototype of a header, comments stripped"""
-    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    return [(ret.strip(), name, [] if params.strip() == 'void' else [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-
-
-def _ctypes_of(decl, is_return=False):
-    if decl == 'void':
-        return {None}
-    if '*' in decl or '[' in decl:
-        if re.match(r'(const )?char \*', decl):
-            return {C.c_char_p} if is_return else {C.c_char_p, C.c_void_p}
-        return {C.c_void_p}
-    return {SCALARS[decl.replace('const ', '').split()[0]]}
-
-
-def test_parser_signature_table_is_its_header(N):
-    protos = _prototypes('peppan_parser.h')
-    assert len(protos) == 6 and sum(len(p) for _, _, p in protos) == 29              # (a prototype the pattern misses shows here)
-    assert {name for _, name, _ in protos} == set(N.PARSER_SIGNATURES)
-    assert not set(N.PARSER_SIGNATURES) & (set(N.SIGNATURES) | set(N.SYNTENY_SIGNATURES) | set(N.GENESTRUCT_SIGNATURES))
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.PARSER_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert restype in _ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in _ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-    hdr = open(os.path.join(ROOT, 'include', 'peppan_parser.h')).read()
-    assert re.search(r'#define PEP_PARSER_ABI_VERSION 1\b', hdr) and lib.pep_parser_version() == N.PARSER_ABI_VERSION == 1
+def test_parser_section_of_the_header(N):
+    """the K20 section of include/peppan_hip.h cites what it replaces, and its limits are _native's (the prototypes: tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
     assert 'PEPPAN_parser.py:74-80' in hdr and 'PEPPAN_parser.py:172-179' in hdr
     assert int(re.search(r'#define PEP_PARSER_MAX_GENES \(1ull << (\d+)\)', hdr).group(1)) == N.PARSER_MAX_GENES.bit_length() - 1 == 31
     assert int(re.search(r'#define PEP_PARSER_MAX_CURVE_POINTS \(1ull << (\d+)\)', hdr).group(1)) == N.PARSER_MAX_CURVE_POINTS.bit_length() - 1 == 28
     assert int(re.search(r'#define PEP_PARSER_MAX_PROFILES (\d+)\b', hdr).group(1)) == N.PARSER_MAX_PROFILES == 16384
-
-
-def test_the_other_headers_are_untouched(N):
-    protos = _prototypes('peppan_hip.h')
-    assert len(protos) == 85 and sum(len(p) for _, _, p in protos) == 531 and len(N.EXPORTS) == 85
-    assert N.ABI_VERSION == 18 and N.load_library().pep_version() == 18
-    assert not [name for _, name, _ in protos if 'parser' in name or 'rarefaction' in name or 'profile_pairs' in name]
-    assert len(_prototypes('peppan_synteny.h')) == 6 and N.load_library().pep_synteny_version() == 1
-    assert len(_prototypes('peppan_genestruct.h')) == 4 and N.load_library().pep_genestruct_version() == 1
 
 
 def _refused(call, N, code, text):
