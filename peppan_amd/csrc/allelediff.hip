@@ -140,6 +140,7 @@ int pep_allele_diff(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row
             if (h_packed[k] > 124) return group_tables_bad_byte(ctx, S, (uint64_t)(std::upper_bound(h_row_off, h_row_off + n_rows + 1, k) - h_row_off) - 1);
         return PEP_OK;
     }
+    static_assert(K15_WS_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
     DevBuf *W = ctx->ws;
     PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 8, 0}}, times.ms[0]));
     pep_timed_stage(ctx, times.ms[1], [&] {

@@ -119,7 +119,8 @@ __global__ __launch_bounds__(256) void k12_pack(uint32_t n_groups, const uint64_
 }
 
 // the slots of pep_ctx::ws
-enum { K12_NT = 0, K12_NT_OFF, K12_ROWS, K12_CIGAR, K12_ROW_OFF, K12_CODES, K12_FRAME_ORF, K12_GRP_OFF, K12_GRP_QLEN, K12_PACK_OFF, K12_PACKED };
+enum { K12_NT = 0, K12_NT_OFF, K12_ROWS, K12_CIGAR, K12_ROW_OFF, K12_CODES, K12_FRAME_ORF, K12_GRP_OFF, K12_GRP_QLEN, K12_PACK_OFF, K12_PACKED, K12_SLOTS };
+static_assert(K12_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
 
 }  // namespace
 

@@ -139,6 +139,41 @@ struct PackDesc {
 // ... and of a packed nucleotide sequence (pep_use_nt_as_residues: NuclSide::d_desc): the sequence and whether it is its reverse complement
 struct NuclDesc { uint32_t seq, rev; };
 
+// The slots of pep_ctx::ws that the search pipeline addresses (seed stage -> score pass -> selection -> traceback pass -> emit), and the ones other
+// files enter it through.  Per line: what the slot holds, its element type, who writes it, who reads it last.  An alias is a take-over inside one
+// search, with the reason the earlier tenant is dead by then.  The stand-alone calls name their slots in their own files and stay below PEP_WS_HITS_OUT.
+enum PepWsSlot {
+    PEP_WS_BUCKET_CNT = 0,                  // entries per index bucket of the count -> scan -> fill build, u32: seed_count / seed_fill (seeds.hip), read last by seed_fill
+    PEP_WS_UF_PARENT = PEP_WS_BUCKET_CNT,   // K10's parent of every node, u32: pack_out / uf_init, read last by uf_flatten - the bucket counts are dead when the seed stage ends, the parents are written behind emit
+    PEP_WS_IDX_START = 1,                   // first entry of every bucket, per seed shape, u32: idx_finish / the scan, read last by the matchers (seed_match, seed_match_stride)
+    PEP_WS_IDX_ENTRIES = 2,                 // the query index's entries, per seed shape, u64: idx_finish / seed_fill, read last by the matchers
+    // 3: free in the pipeline
+    PEP_WS_CANDS = 4,                       // the sorted candidate keys, u64: set_compact and the sort - or the caller's upload (linclust.hip) -, read last by select_gather (as d_cands of pep_extend)
+    PEP_WS_CANDS_TMP = 5,                   // the sort's second buffer, u64: sort.hip, read last by its final pass
+    // 6: free in the pipeline
+    PEP_WS_SEED_SCAN_TMP = 7,               // scratch of the bucket scan (count -> scan -> fill build): pep_scan_u32
+    PEP_WS_SEED_HITS = 8,                   // raw seed hits, u64: the matchers, read last by seed_runs_extend
+    PEP_WS_TRACE_KNOWN = PEP_WS_SEED_HITS,  // known score + end lane of every selected pair, i32 x 2: select_gather, read last by the traceback sweeps - the raw seed hits are dead once seed_runs_extend has made candidates of them, in the seed stage
+    PEP_WS_SEED_FILTER = 9,                 // occupancy bits in front of the index, per seed shape, u64: idx_finish / filter_fill, read last by the matchers
+    PEP_WS_DPP_SELFTEST = PEP_WS_SEED_FILTER,   // the two shifted lane rows of pep_selftest_dpp, i32: a call of its own at start-up, waited for before it returns
+    PEP_WS_SW_NBLK = 10,                    // 16-step blocks per candidate of the newest pass, u32: sw_prep, read last by emit (trace.hip)
+    PEP_WS_SW_DIR_OFF = 11,                 // first traceback block per candidate, u64[n + 1]: sw_prep, read last by walk (trace.hip)
+    PEP_WS_SW_OUT = 12,                     // score / end cell / a0 per candidate, int4: identical_check, the sweeps and gapless_check, read last by walk
+    PEP_WS_IDX_PART = 13,                   // the partition build's slabs per coarse bucket, u64: idx_slab, read last by idx_finish
+    PEP_WS_SW_SKIP_MODE = PEP_WS_IDX_PART,  // score pass: which candidates identical_check settled, i32, read last by sw_order - the slabs are dead once idx_finish has run, in the seed stage
+    PEP_WS_TRACE_DIRS = PEP_WS_IDX_PART,    // traceback codes, 512 B per 16-step block, u32: sw_trace_kernel, read last by walk - the skip modes are dead once the score pass is over (the traceback pass reads d_trace_mode)
+    PEP_WS_SW_SCAN_IN = 14,                 // blocks per candidate as the look-back scan's input, u64: sw_prep
+    PEP_WS_SW_ORDER = 15,                   // the candidates by decreasing length, u32: sw_order, read last by the sweeps
+    // 16 - 18: free
+    PEP_WS_SEL = 19,                        // the record of every selected pair, SelInfo: select_gather .. topk, read last by emit
+    PEP_WS_SEL_RUNS_KEYS = 20,              // run slot of every selected pair u64[n + 2], then their keys u64[n + 2]: select_gather, read last by emit
+    PEP_WS_RUNS = 21,                       // the CIGAR run arena of the selected pairs, u32: walk, read last by emit
+    PEP_WS_KEEP = 22,                       // keep flag u32, hit position u32, CIGAR position u64 per selected pair: topk, read last by emit
+    PEP_WS_HITS_OUT = 23,                   // the search's hit table, pep_hit[n_hits] + CIGAR runs u32: emit.  The one slot that outlives a call: intact while ctx->dev_result is set
+                                            // (pep_fetch_result and pep_k10_components_dev read it later), so whoever writes it calls pep_drop_dev_result first and every other user of ws stays below it
+    PEP_WS_COUNT
+};
+
 enum PepTimer { TM_SEED = 0, TM_TOTAL, TM_SW, TM_SW_TRACE, TM_TRACE, TM_MATCH0, TM_MATCH1, TM_MATCH2, TM_MATCH3, TM_COUNT };
 
 struct pep_ctx {
@@ -215,8 +250,8 @@ struct pep_ctx {
     DevBuf d_t_class;
     DevBuf d_t_subject;                         // hsp_mode 2: the reference sequence every target is a strand / frame / chunk of (uploaded per search)
     bool t_class_ready = false;
-    // workspaces (grow-only, reused between searches)
-    DevBuf ws[24];
+    // workspaces (grow-only, reused between searches and between calls: PepWsSlot above)
+    DevBuf ws[PEP_WS_COUNT];
     DevBuf sub_lds;                         // replicated substitution table image (32 KiB)
     DevBuf d_params;                        // device copy of seed params
     int8_t d_params_host[1024] = {};        // what d_params holds (uploaded again only when the substitution table changes)
@@ -246,7 +281,7 @@ struct pep_ctx {
     PinBuf pin_nt_match;                     // grow-only: those counts on their way to the result
     uint32_t grp_nodes = 0, grp_q_base = 0;  // pep_set_grouping: the searches of this context end with K10 over their own hit table (0 = off)
     bool device_results = false;            // pep_set_result_mode: searches leave their table on the device; the host copy is fetched on demand
-    pep_result *dev_result = nullptr;       // the result whose hit table is still intact on the device (ws[23]): the newest search's, until the workspace is reused
+    pep_result *dev_result = nullptr;       // the result whose hit table is still intact on the device (PEP_WS_HITS_OUT): the newest search's, until the workspace is reused
     DevBuf d_zero;                          // the small counters of one search, cleared by ONE fill when it starts (layout: PEP_ZERO_* below)
     bool zero_clean = false;                // the seed stage's part of d_zero is zero as of the end of what is queued (pack_out cleared all of d_zero): with every
                                             // zero_ok flag still set the next search needs no fill

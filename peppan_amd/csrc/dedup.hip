@@ -124,6 +124,13 @@ __global__ void k13_table(uint32_t n, const uint32_t *__restrict__ run_excl, con
     atomicAdd(fail, 1u);
 }
 
+// the slots of pep_ctx::ws: pep_sha1's three, then pep_dedup's (a call of its own: K13_REP carries the probe failure count behind the n representatives)
+enum {
+    K13_SHA_BYTES = 0, K13_SHA_OFF, K13_SHA_WORDS,
+    K13_LEN = 0, K13_WORDS, K13_RUN_FLAG, K13_RUN_EXCL, K13_TABLE, K13_REP, K13_SCAN_TMP, K13_SLOTS
+};
+static_assert(K13_SHA_WORDS < K13_SLOTS && K13_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+
 }  // namespace
 
 extern "C" {
@@ -139,15 +146,15 @@ int pep_sha1(pep_ctx *ctx, const uint8_t *h_bytes, const uint64_t *h_off, uint32
     DevBuf *W = ctx->ws;
     hipStream_t st = ctx->stream;
     const uint64_t total = h_off[n];
-    PEP_TRY(dev_reserve(ctx, W[0], total + 64));
-    PEP_TRY(dev_reserve(ctx, W[1], ((size_t)n + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[2], (size_t)n * 20));
-    PEP_HIP(ctx, hipMemcpyAsync(W[0].p, h_bytes, total, hipMemcpyHostToDevice, st));
-    PEP_HIP(ctx, hipMemcpyAsync(W[1].p, h_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k13_sha1, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, n, W[0].as<const uint8_t>(), W[1].as<const uint64_t>(), W[2].as<uint32_t>());
+    PEP_TRY(dev_reserve(ctx, W[K13_SHA_BYTES], total + 64));
+    PEP_TRY(dev_reserve(ctx, W[K13_SHA_OFF], ((size_t)n + 1) * 8));
+    PEP_TRY(dev_reserve(ctx, W[K13_SHA_WORDS], (size_t)n * 20));
+    PEP_HIP(ctx, hipMemcpyAsync(W[K13_SHA_BYTES].p, h_bytes, total, hipMemcpyHostToDevice, st));
+    PEP_HIP(ctx, hipMemcpyAsync(W[K13_SHA_OFF].p, h_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k13_sha1, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, n, W[K13_SHA_BYTES].as<const uint8_t>(), W[K13_SHA_OFF].as<const uint64_t>(), W[K13_SHA_WORDS].as<uint32_t>());
     PEP_HIP(ctx, hipGetLastError());
     std::vector<uint32_t> words((size_t)n * 5);
-    PEP_HIP(ctx, hipMemcpyAsync(words.data(), W[2].p, (size_t)n * 20, hipMemcpyDeviceToHost, st));
+    PEP_HIP(ctx, hipMemcpyAsync(words.data(), W[K13_SHA_WORDS].p, (size_t)n * 20, hipMemcpyDeviceToHost, st));
     PEP_HIP(ctx, hipStreamSynchronize(st));
     for (size_t k = 0; k < words.size(); ++k) {          // big-endian bytes, as hashlib's digest()
         const uint32_t v = words[k];
@@ -170,27 +177,27 @@ int pep_dedup(pep_ctx *ctx, uint32_t n, const uint32_t *h_len, const uint8_t *h_
     uint32_t bits = 4;
     while ((1ull << bits) < 2ull * n) ++bits;
     const uint32_t mask = (uint32_t)((1ull << bits) - 1);
-    PEP_TRY(dev_reserve(ctx, W[0], (size_t)n * 4));
-    PEP_TRY(dev_reserve(ctx, W[1], (size_t)n * 20));
-    PEP_TRY(dev_reserve(ctx, W[2], ((size_t)n + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[3], ((size_t)n + 2) * 4));
-    PEP_TRY(dev_reserve(ctx, W[4], ((size_t)mask + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[5], ((size_t)n + 1) * 4));
-    PEP_HIP(ctx, hipMemcpyAsync(W[0].p, h_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    PEP_HIP(ctx, hipMemcpyAsync(W[1].p, words.data(), (size_t)n * 20, hipMemcpyHostToDevice, st));
-    PEP_HIP(ctx, hipMemsetAsync(W[4].p, 0xFF, ((size_t)mask + 1) * 4, st));
-    PEP_HIP(ctx, hipMemsetAsync(W[5].as<uint32_t>() + n, 0, 4, st));
+    PEP_TRY(dev_reserve(ctx, W[K13_LEN], (size_t)n * 4));
+    PEP_TRY(dev_reserve(ctx, W[K13_WORDS], (size_t)n * 20));
+    PEP_TRY(dev_reserve(ctx, W[K13_RUN_FLAG], ((size_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K13_RUN_EXCL], ((size_t)n + 2) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K13_TABLE], ((size_t)mask + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K13_REP], ((size_t)n + 1) * 4));
+    PEP_HIP(ctx, hipMemcpyAsync(W[K13_LEN].p, h_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PEP_HIP(ctx, hipMemcpyAsync(W[K13_WORDS].p, words.data(), (size_t)n * 20, hipMemcpyHostToDevice, st));
+    PEP_HIP(ctx, hipMemsetAsync(W[K13_TABLE].p, 0xFF, ((size_t)mask + 1) * 4, st));
+    PEP_HIP(ctx, hipMemsetAsync(W[K13_REP].as<uint32_t>() + n, 0, 4, st));
     const unsigned g = (unsigned)ceil_div(n, 256);
-    hipLaunchKernelGGL(k13_run_flags, dim3(g), dim3(256), 0, st, n, W[0].as<const uint32_t>(), W[2].as<uint32_t>());
-    PEP_TRY(pep_scan_u32(ctx, W[2].as<const uint32_t>(), W[3].as<uint32_t>(), n, W[6]));
-    uint32_t *fail = W[5].as<uint32_t>() + n;
-    hipLaunchKernelGGL(k13_table<true>, dim3(g), dim3(256), 0, st, n, W[3].as<const uint32_t>(), W[2].as<const uint32_t>(), W[1].as<const uint32_t>(),
-                       W[4].as<uint32_t>(), mask, (uint32_t *)nullptr, fail);
-    hipLaunchKernelGGL(k13_table<false>, dim3(g), dim3(256), 0, st, n, W[3].as<const uint32_t>(), W[2].as<const uint32_t>(), W[1].as<const uint32_t>(),
-                       W[4].as<uint32_t>(), mask, W[5].as<uint32_t>(), fail);
+    hipLaunchKernelGGL(k13_run_flags, dim3(g), dim3(256), 0, st, n, W[K13_LEN].as<const uint32_t>(), W[K13_RUN_FLAG].as<uint32_t>());
+    PEP_TRY(pep_scan_u32(ctx, W[K13_RUN_FLAG].as<const uint32_t>(), W[K13_RUN_EXCL].as<uint32_t>(), n, W[K13_SCAN_TMP]));
+    uint32_t *fail = W[K13_REP].as<uint32_t>() + n;
+    hipLaunchKernelGGL(k13_table<true>, dim3(g), dim3(256), 0, st, n, W[K13_RUN_EXCL].as<const uint32_t>(), W[K13_RUN_FLAG].as<const uint32_t>(), W[K13_WORDS].as<const uint32_t>(),
+                       W[K13_TABLE].as<uint32_t>(), mask, (uint32_t *)nullptr, fail);
+    hipLaunchKernelGGL(k13_table<false>, dim3(g), dim3(256), 0, st, n, W[K13_RUN_EXCL].as<const uint32_t>(), W[K13_RUN_FLAG].as<const uint32_t>(), W[K13_WORDS].as<const uint32_t>(),
+                       W[K13_TABLE].as<uint32_t>(), mask, W[K13_REP].as<uint32_t>(), fail);
     PEP_HIP(ctx, hipGetLastError());
     uint32_t n_fail = 0;
-    PEP_HIP(ctx, hipMemcpyAsync(h_rep, W[5].p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    PEP_HIP(ctx, hipMemcpyAsync(h_rep, W[K13_REP].p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     PEP_HIP(ctx, hipMemcpyAsync(&n_fail, fail, 4, hipMemcpyDeviceToHost, st));
     PEP_HIP(ctx, hipStreamSynchronize(st));
     if (n_fail) return pep_fail(ctx, PEP_ERR_INTERNAL, "pep_dedup: hash table probe failed");

@@ -260,6 +260,7 @@ int pep_group_verdicts(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_
     if (n_groups == 0) return PEP_OK;
     const auto run = [&]() -> int {
         const uint64_t n_idx = h_grp_off[n_groups];
+        static_assert(K16_WS_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
         DevBuf *W = ctx->ws;
         hipStream_t st = ctx->stream;
         std::vector<VGroup> dev_groups(n_groups);

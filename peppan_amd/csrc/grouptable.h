@@ -37,8 +37,11 @@ enum {
     K15_WS_PACKED = 0, K15_WS_ROW_OFF, K15_WS_ROW_LEN, K15_WS_PLANE_OFF, K15_WS_PLANES, K15_WS_GRP_ROWS, K15_WS_GROUPS, K15_WS_TILES,
     K15_WS_OUT,                     // K15 alone: its output
     K15_WS_BAD_ROW,
-    K16_WS_GENOME, K16_WS_EDGES, K16_WS_GD_KEY, K16_WS_GD_VAL, K16_WS_FLAGS, K16_WS_VERDICT, K16_WS_SPILL
+    K15_WS_SLOTS,                   // K16 goes on where K15 ends
+    K16_WS_GENOME = K15_WS_SLOTS, K16_WS_EDGES, K16_WS_GD_KEY, K16_WS_GD_VAL, K16_WS_FLAGS, K16_WS_VERDICT, K16_WS_SPILL,
+    K16_WS_SLOTS
 };
+static_assert(K16_WS_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
 
 // Every check of the row and group tables, on the host, so that a bad table is an error and not an out-of-bounds access; also lays the device
 // buffers out.  Returns a code and, for an error, msg.

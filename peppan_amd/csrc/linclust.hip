@@ -256,6 +256,14 @@ void k9_params(int base, const pep_search_params &defaults, pep_search_params &P
 
 struct GapCand { uint32_t s, c; int32_t bin; };
 
+// The slots of pep_ctx::ws.  The gapped stage in the middle of pep_linclust (k9_gapped) uploads its keys to PEP_WS_CANDS - where the seed stage leaves a search's
+// candidates, and where K9_SEL_CNT was: read to the host by then - and runs pep_extend over them, which overwrites K9_NACC (PEP_WS_TRACE_KNOWN), K9_REP (PEP_WS_SW_NBLK),
+// K9_FLAGS (PEP_WS_SW_DIR_OFF), K9_GAP_PAIR (PEP_WS_SW_OUT), K9_GAP_BIN (PEP_WS_TRACE_DIRS) and, with pep_set_grouping on, K9_RES (PEP_WS_UF_PARENT).
+enum { K9_RES = 0, K9_OFF, K9_SEL_KEY, K9_SEL_POS, K9_SEL_CNT, K9_MAP_KEY, K9_MAP_VAL, K9_ACC, K9_NACC, K9_STATUS, K9_REP, K9_FLAGS, K9_GAP_PAIR, K9_GAP_BIN, K9_SLOTS };
+static_assert(K9_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");          // (its own calls: pep_extend drops the old table before it writes the new one)
+static_assert(K9_SEL_CNT == PEP_WS_CANDS && K9_NACC == PEP_WS_TRACE_KNOWN && K9_REP == PEP_WS_SW_NBLK && K9_FLAGS == PEP_WS_SW_DIR_OFF && K9_GAP_PAIR == PEP_WS_SW_OUT &&
+              K9_GAP_BIN == PEP_WS_TRACE_DIRS && K9_RES == PEP_WS_UF_PARENT, "the slots pep_extend takes over, as listed above");
+
 // (member, centre) pairs accepted by the gapped alignment of the best band among `cands` (sorted by centre, member, bin; unique)
 int k9_gapped(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, int base, double min_id, double min_cov, const std::vector<GapCand> &cands,
               std::vector<std::pair<uint32_t, uint32_t>> &accepted)
@@ -315,14 +323,14 @@ int k9_gapped(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, int bas
         }
         std::sort(keys.begin(), keys.end());
         keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-        rc = dev_reserve(ctx, ctx->ws[4], (keys.size() + 1) * 8);
+        rc = dev_reserve(ctx, ctx->ws[PEP_WS_CANDS], (keys.size() + 1) * 8);
         if (rc != PEP_OK) break;
-        if (hipMemcpy(ctx->ws[4].p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = pep_fail(ctx, PEP_ERR_HIP, "pep_linclust: key upload failed"); break; }
+        if (hipMemcpy(ctx->ws[PEP_WS_CANDS].p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = pep_fail(ctx, PEP_ERR_HIP, "pep_linclust: key upload failed"); break; }
         std::vector<int32_t> min_score(q_list.size() + 1, 1);
         pep_result res;
         res.ctx = ctx;
         pep_materialise_staged(ctx);
-        rc = pep_extend(ctx, ctx->ws[4].as<const uint64_t>(), keys.size(), min_score.data(), &res);
+        rc = pep_extend(ctx, ctx->ws[PEP_WS_CANDS].as<const uint64_t>(), keys.size(), min_score.data(), &res);
         if (rc != PEP_OK) break;
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = pep_fail(ctx, PEP_ERR_HIP, "pep_linclust: stream sync failed"); break; }
         const pep_hit *hits = res.st_hits ? res.st_hits : res.hits.data();
@@ -359,33 +367,33 @@ extern "C" int pep_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *
     const uint64_t total = h_off[n];
     hipStream_t st = ctx->stream;
     DevBuf *W = ctx->ws;
-    PEP_TRY(dev_reserve(ctx, W[0], total + 64));
-    PEP_TRY(dev_reserve(ctx, W[1], ((uint64_t)n + 1) * 8));
-    PEP_TRY(dev_reserve(ctx, W[2], (uint64_t)n * m * 8 + 8));
-    PEP_TRY(dev_reserve(ctx, W[3], (uint64_t)n * m * 4 + 8));
-    PEP_TRY(dev_reserve(ctx, W[4], ((uint64_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K9_RES], total + 64));
+    PEP_TRY(dev_reserve(ctx, W[K9_OFF], ((uint64_t)n + 1) * 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_SEL_KEY], (uint64_t)n * m * 8 + 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_SEL_POS], (uint64_t)n * m * 4 + 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_SEL_CNT], ((uint64_t)n + 1) * 4));
     int bits = 10;
     while ((1ull << bits) < 2ull * n * m) ++bits;
     if (bits > 31) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_linclust: too many k-mers for the centre map");
     const uint64_t cap = 1ull << bits;
-    PEP_TRY(dev_reserve(ctx, W[5], cap * 8));
-    PEP_TRY(dev_reserve(ctx, W[6], cap * 8));
-    PEP_TRY(dev_reserve(ctx, W[7], (uint64_t)n * m * 4 + 8));
-    PEP_TRY(dev_reserve(ctx, W[8], ((uint64_t)n + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[9], ((uint64_t)n + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[10], ((uint64_t)n + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[11], 64));
-    PEP_TRY(dev_reserve(ctx, W[12], (uint64_t)n * m * 8 + 8));
-    PEP_TRY(dev_reserve(ctx, W[13], (uint64_t)n * m * 4 + 8));
-    uint8_t *res = W[0].as<uint8_t>();
-    uint64_t *off = W[1].as<uint64_t>(), *sel_key = W[2].as<uint64_t>(), *map_key = W[5].as<uint64_t>();
-    uint32_t *sel_pos = W[3].as<uint32_t>(), *sel_cnt = W[4].as<uint32_t>(), *acc = W[7].as<uint32_t>(), *nacc = W[8].as<uint32_t>();
-    uint32_t *status = W[9].as<uint32_t>(), *rep = W[10].as<uint32_t>();
-    unsigned long long *map_val = W[6].as<unsigned long long>();
-    uint32_t *flags = W[11].as<uint32_t>();
+    PEP_TRY(dev_reserve(ctx, W[K9_MAP_KEY], cap * 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_MAP_VAL], cap * 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_ACC], (uint64_t)n * m * 4 + 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_NACC], ((uint64_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K9_STATUS], ((uint64_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K9_REP], ((uint64_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K9_FLAGS], 64));
+    PEP_TRY(dev_reserve(ctx, W[K9_GAP_PAIR], (uint64_t)n * m * 8 + 8));
+    PEP_TRY(dev_reserve(ctx, W[K9_GAP_BIN], (uint64_t)n * m * 4 + 8));
+    uint8_t *res = W[K9_RES].as<uint8_t>();
+    uint64_t *off = W[K9_OFF].as<uint64_t>(), *sel_key = W[K9_SEL_KEY].as<uint64_t>(), *map_key = W[K9_MAP_KEY].as<uint64_t>();
+    uint32_t *sel_pos = W[K9_SEL_POS].as<uint32_t>(), *sel_cnt = W[K9_SEL_CNT].as<uint32_t>(), *acc = W[K9_ACC].as<uint32_t>(), *nacc = W[K9_NACC].as<uint32_t>();
+    uint32_t *status = W[K9_STATUS].as<uint32_t>(), *rep = W[K9_REP].as<uint32_t>();
+    unsigned long long *map_val = W[K9_MAP_VAL].as<unsigned long long>();
+    uint32_t *flags = W[K9_FLAGS].as<uint32_t>();
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(flags + 4);          // [0] verified, [1] accepted without gaps, [2] pairs for the gapped stage
-    unsigned long long *gap_pair = W[12].as<unsigned long long>();
-    int32_t *gap_bin = W[13].as<int32_t>();
+    unsigned long long *gap_pair = W[K9_GAP_PAIR].as<unsigned long long>();
+    int32_t *gap_bin = W[K9_GAP_BIN].as<int32_t>();
     if (total) PEP_HIP(ctx, hipMemcpyAsync(res, h_res, total, hipMemcpyHostToDevice, st));
     PEP_HIP(ctx, hipMemcpyAsync(off, h_off, ((uint64_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     PEP_HIP(ctx, hipMemsetAsync(map_key, 0xFF, cap * 8, st));
@@ -399,7 +407,7 @@ extern "C" int pep_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *
                        (const uint32_t *)sel_cnt, (const uint64_t *)map_key, (const unsigned long long *)map_val, bits, min_id, min_cov, acc, nacc, stats,
                        gap_pair, gap_bin, stats + 2);
     PEP_HIP(ctx, hipGetLastError());
-    // ---- everything the later stages need comes to the host: the gapped stage reuses the workspaces of the alignment engine
+    // ---- everything the later stages need comes to the host: the gapped stage's pep_extend overwrites K9_NACC, K9_REP, K9_FLAGS, K9_GAP_PAIR and K9_GAP_BIN (the enum above)
     std::vector<uint32_t> cnt(n), h_nacc(n), h_acc((size_t)n * m);
     unsigned long long hs[3] = {0, 0, 0};
     uint32_t h_flags[2] = {0, 0};
@@ -429,12 +437,12 @@ extern "C" int pep_linclust(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *
             if (!have && h_nacc[sc.first] < (uint32_t)m) { list[h_nacc[sc.first]++] = sc.second; ++n_accepted; }
         }
         PEP_HIP(ctx, hipMemcpyAsync(off, h_off, ((uint64_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-        PEP_TRY(dev_reserve(ctx, W[7], (uint64_t)n * m * 4 + 8));
-        PEP_TRY(dev_reserve(ctx, W[8], ((uint64_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[9], ((uint64_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[10], ((uint64_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[11], 64));
-        acc = W[7].as<uint32_t>(); nacc = W[8].as<uint32_t>(); status = W[9].as<uint32_t>(); rep = W[10].as<uint32_t>(); flags = W[11].as<uint32_t>();
+        PEP_TRY(dev_reserve(ctx, W[K9_ACC], (uint64_t)n * m * 4 + 8));
+        PEP_TRY(dev_reserve(ctx, W[K9_NACC], ((uint64_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K9_STATUS], ((uint64_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K9_REP], ((uint64_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K9_FLAGS], 64));
+        acc = W[K9_ACC].as<uint32_t>(); nacc = W[K9_NACC].as<uint32_t>(); status = W[K9_STATUS].as<uint32_t>(); rep = W[K9_REP].as<uint32_t>(); flags = W[K9_FLAGS].as<uint32_t>();
         PEP_HIP(ctx, hipMemcpyAsync(acc, h_acc.data(), (uint64_t)n * m * 4, hipMemcpyHostToDevice, st));
         PEP_HIP(ctx, hipMemcpyAsync(nacc, h_nacc.data(), (uint64_t)n * 4, hipMemcpyHostToDevice, st));
         PEP_HIP(ctx, hipMemsetAsync(flags, 0, 64, st));

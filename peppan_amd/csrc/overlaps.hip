@@ -39,7 +39,8 @@ __global__ __launch_bounds__(256) void ovl_sweep(OvlArgs a, uint64_t *__restrict
 }
 
 // the slots of pep_ctx::ws
-enum { K11_CONTIG = 0, K11_START, K11_END, K11_RID, K11_CNT, K11_OFF, K11_OUT, K11_SCAN_TMP };
+enum { K11_CONTIG = 0, K11_START, K11_END, K11_RID, K11_CNT, K11_OFF, K11_OUT, K11_SCAN_TMP, K11_SLOTS };
+static_assert(K11_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
 
 }  // namespace
 

@@ -283,6 +283,10 @@ static int k7_codons_check(uint64_t n, const pep_nt_hit *h_hits, const uint32_t 
     return k7_check("pep_rescore_codons", n, h_hits, h_cigar, n_cigar, q_off, n_q, r_off, n_r, msg);
 }
 
+// the slots of pep_ctx::ws (uploaded tables only: pep_k7_hits_queue reads a search's own hits where they are)
+enum { K7_HITS = 0, K7_CIGAR, K7_OUT, K7_TABLES, K7_SLOTS };
+static_assert(K7_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+
 // pep_rescore_nt (mode 1, no tables, width 5) and pep_rescore_codons (its mode and tables, width 7): checks, upload, k7_table<mode>, h_out[n, width]; `who` leads the messages.
 // width 5: mode is 1 and no table is read.  width 7: the mode and the tables are the caller's and are judged first, also for n == 0 and before the state.
 static int k7_rescore(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hit *h_hits, const uint32_t *h_cigar, uint64_t n_cigar, int32_t mode,
@@ -295,22 +299,22 @@ static int k7_rescore(pep_ctx *ctx, const char *who, uint64_t n, const pep_nt_hi
     if (!ctx->q_nt.nt.p || !ctx->r_nt.nt.p) return pep_fail(ctx, PEP_ERR_STATE, std::string(who) + " needs pep_set_query_nt and pep_set_ref_nt first");
     rc = k7_check(who, n, h_hits, h_cigar, n_cigar, ctx->q_nt.h_off.data(), ctx->q_nt.n, ctx->r_nt.h_off.data(), ctx->r_nt.n, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], n * sizeof(pep_nt_hit)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[1], (n_cigar + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[2], n * width * 8));
-    PEP_TRY(pep_h2d(ctx, ctx->ws[0].p, h_hits, n * sizeof(pep_nt_hit)));
-    PEP_TRY(pep_h2d(ctx, ctx->ws[1].p, h_cigar, n_cigar * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K7_HITS], n * sizeof(pep_nt_hit)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K7_CIGAR], (n_cigar + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K7_OUT], n * width * 8));
+    PEP_TRY(pep_h2d(ctx, ctx->ws[K7_HITS].p, h_hits, n * sizeof(pep_nt_hit)));
+    PEP_TRY(pep_h2d(ctx, ctx->ws[K7_CIGAR].p, h_cigar, n_cigar * 4));
     uint8_t tables[128 + 1024] = {0};            // aa_of_word at 0, sub at 128; alive until the stream has been waited for
     if (mode == 2) {
         memcpy(tables, aa_of_word, 125);
         memcpy(tables + 128, sub, 1024);
-        PEP_TRY(dev_reserve(ctx, ctx->ws[3], sizeof(tables)));
-        PEP_TRY(pep_h2d(ctx, ctx->ws[3].p, tables, sizeof(tables)));
+        PEP_TRY(dev_reserve(ctx, ctx->ws[K7_TABLES], sizeof(tables)));
+        PEP_TRY(pep_h2d(ctx, ctx->ws[K7_TABLES].p, tables, sizeof(tables)));
     }
     hipLaunchKernelGGL(mode == 1 ? k7_table<1> : mode == 2 ? k7_table<2> : k7_table<3>, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, ctx->stream, n,
-                       ctx->ws[0].as<const pep_nt_hit>(), ctx->ws[1].as<const uint32_t>(), k7_seqs(ctx), ctx->ws[3].as<const uint8_t>(), ctx->ws[2].as<long long>());
+                       ctx->ws[K7_HITS].as<const pep_nt_hit>(), ctx->ws[K7_CIGAR].as<const uint32_t>(), k7_seqs(ctx), ctx->ws[K7_TABLES].as<const uint8_t>(), ctx->ws[K7_OUT].as<long long>());
     PEP_HIP(ctx, hipGetLastError());
-    PEP_TRY(pep_d2h_queue(ctx, h_out, ctx->ws[2].p, n * width * 8));
+    PEP_TRY(pep_d2h_queue(ctx, h_out, ctx->ws[K7_OUT].p, n * width * 8));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
     return PEP_OK;

@@ -1053,8 +1053,7 @@ int pep_upload_sub_table(pep_ctx *ctx)
     return PEP_OK;
 }
 
-// workspace slots used here: ws[0] cnt, ws[1] start, ws[2] entries, ws[3] table, ws[4] list, ws[5] list tmp (sort),
-// ws[6] counters+stats, ws[7] scan scratch, ws[8] raw seed hits, ws[10..12] runs of hits (the sort histogram reuses ws[0])
+// workspace slots used here: PepWsSlot (common.h); the candidate set is ctx->d_set, the counters and histograms are in ctx->d_zero
 // need_targets (optional): the target set may still be on its way (pep_search queues K1 for both sides and waits for the query side only);
 // the hook is called once, right before the first use of anything about the targets - after the first shape's index build has been queued,
 // so that the GPU goes from K1 into the index kernels while the host picks up the target side's summary.
@@ -1086,14 +1085,14 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
     for (int s = 1; s < P.n_shapes && s < 4; ++s) same_weight = same_weight && P.weight[s] == P.weight[0];
     const int n_idx = same_weight ? std::max(1, std::min<int>(P.n_shapes, 4)) : 1;
     const uint64_t start_stride = (n_buckets + 2 + 15) & ~15ull, entries_stride = (Q.total + 4 + 7) & ~7ull, filter_stride = ((n_buckets >> FILTER_SHIFT) + 2 + 7) & ~7ull;
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], (n_buckets + 1) * sizeof(uint32_t)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[1], n_idx * start_stride * sizeof(uint32_t)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[2], n_idx * entries_stride * sizeof(uint64_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_BUCKET_CNT], (n_buckets + 1) * sizeof(uint32_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_IDX_START], n_idx * start_stride * sizeof(uint32_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_IDX_ENTRIES], n_idx * entries_stride * sizeof(uint64_t)));
     PEP_TRY(dev_reserve(ctx, ctx->d_zero, PEP_ZERO_TOTAL));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[9], n_idx * filter_stride * 8));
-    unsigned long long *filter0 = ctx->ws[9].as<unsigned long long>();
-    uint32_t *cnt = ctx->ws[0].as<uint32_t>(), *start0 = ctx->ws[1].as<uint32_t>();
-    uint64_t *entries0 = ctx->ws[2].as<uint64_t>();
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SEED_FILTER], n_idx * filter_stride * 8));
+    unsigned long long *filter0 = ctx->ws[PEP_WS_SEED_FILTER].as<unsigned long long>();
+    uint32_t *cnt = ctx->ws[PEP_WS_BUCKET_CNT].as<uint32_t>(), *start0 = ctx->ws[PEP_WS_IDX_START].as<uint32_t>();
+    uint64_t *entries0 = ctx->ws[PEP_WS_IDX_ENTRIES].as<uint64_t>();
     char *zero = ctx->d_zero.as<char>();
     uint32_t *counters = reinterpret_cast<uint32_t *>(zero + PEP_ZERO_SEED);
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(counters + 4);
@@ -1120,8 +1119,8 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
         PEP_TRY(dev_reserve(ctx, ctx->d_set, cap * sizeof(uint64_t)));
         if (ctx->set_clean_slots < cap) PEP_HIP(ctx, hipMemsetAsync(ctx->d_set.p, 0xFF, cap * sizeof(uint64_t), ctx->stream));
         ctx->set_clean_slots = 0;                               // in use until set_compact below has been queued
-        PEP_TRY(dev_reserve(ctx, ctx->ws[4], (uint64_t)list_cap * sizeof(uint64_t)));
-        PEP_TRY(dev_reserve(ctx, ctx->ws[5], (uint64_t)list_cap * sizeof(uint64_t)));
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_CANDS], (uint64_t)list_cap * sizeof(uint64_t)));
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_CANDS_TMP], (uint64_t)list_cap * sizeof(uint64_t)));
         // ONE fill for every small counter block of the search (seed stage, candidate sort, both Smith-Waterman passes, selection)
         // (not even that when the previous search's last kernel has left all of them cleared and nothing has touched them since)
         bool all_ok = ctx->zero_clean;
@@ -1179,8 +1178,8 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
                 const uint32_t n_coarse = 1u << (bucket_bits - fine_bits);
                 const size_t lds = (size_t)n_coarse * 4 + TILE + TILE_HALO;
                 const uint64_t part_stride = (uint64_t)n_coarse * PART_CAP;
-                PEP_TRY(dev_reserve(ctx, ctx->ws[13], (fused_build ? n_idx : 1) * part_stride * sizeof(uint64_t)));
-                uint64_t *part = ctx->ws[13].as<uint64_t>();
+                PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_IDX_PART], (fused_build ? n_idx : 1) * part_stride * sizeof(uint64_t)));
+                uint64_t *part = ctx->ws[PEP_WS_IDX_PART].as<uint64_t>();
                 uint32_t *coarse = reinterpret_cast<uint32_t *>(zero + PEP_ZERO_COARSE) + (size_t)s * 8192;       // (cleared by the search's one fill)
                 if (!fused_build || s == 0) {
                     SeedShapeSet shs;
@@ -1193,7 +1192,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
             } else {
                 PEP_HIP(ctx, hipMemsetAsync(cnt, 0, (n_buckets + 1) * sizeof(uint32_t), ctx->stream));
                 PEP_SEED_DISPATCH(seed_count, dim3(qb), sh, Q.res.as<const uint8_t>(), Q.total, cnt, bucket_bits);
-                PEP_TRY(pep_scan_u32(ctx, cnt, start, n_buckets, ctx->ws[7]));
+                PEP_TRY(pep_scan_u32(ctx, cnt, start, n_buckets, ctx->ws[PEP_WS_SEED_SCAN_TMP]));
                 PEP_HIP(ctx, hipMemsetAsync(cnt, 0, (n_buckets + 1) * sizeof(uint32_t), ctx->stream));
                 PEP_SEED_DISPATCH(seed_fill, dim3(qb), sh, Q.res.as<const uint8_t>(), Q.total, (const uint32_t *)start, cnt, entries, bucket_bits);
                 PEP_HIP(ctx, hipMemsetAsync(filter, 0, (n_buckets >> FILTER_SHIFT) * 8, ctx->stream));
@@ -1209,7 +1208,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
                     return PEP_OK;
                 }
                 if (hit_cap == 0) hit_cap = std::max<uint64_t>(1ull << 22, 2 * T.total);
-                PEP_TRY(dev_reserve(ctx, ctx->ws[8], hit_cap * sizeof(uint64_t)));
+                PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SEED_HITS], hit_cap * sizeof(uint64_t)));
             }
             const unsigned tb = (unsigned)ceil_div(T.total, 256);
             JoinArgs a;
@@ -1223,7 +1222,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
             if (s == 0 && P.ungapped_min > 0 && P.reserved[0] == 0) PEP_TRY(pep_self_map(ctx, &self_on));     // (reserved[0] = 10 / 8: the plain stream, for comparison)
             if (self_on) a.self_delta = ctx->d_self_delta.as<const int32_t>();
             unsigned long long *hit_count = reinterpret_cast<unsigned long long *>(zero + PEP_ZERO_SHAPE) + 2 * s;      // per shape, cleared by the one fill
-            a.hits = ctx->ws[8].as<uint64_t>(); a.hit_count = hit_count; a.hit_cap = hit_cap;
+            a.hits = ctx->ws[PEP_WS_SEED_HITS].as<uint64_t>(); a.hit_count = hit_count; a.hit_cap = hit_cap;
             if (self_on && s == 0) {
                 // which targets repeat a query, the blocks whose diagonal-0 self hits the matchers drop, and those genes' own candidates: one launch, all shapes
                 SeedShapeSet shs;
@@ -1256,7 +1255,7 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
         const int key_bits = qb + tb + bb, top_shift = key_bits > PEP_SORT_TOP_BITS && key_bits <= 54 && P.reserved[2] == 0 ? key_bits - PEP_SORT_TOP_BITS : -1;
         uint32_t *top_hist = reinterpret_cast<uint32_t *>(zero + PEP_ZERO_TOP);
         hipLaunchKernelGGL(set_compact, dim3((unsigned)ceil_div(cap, 256 * COMPACT_ROUNDS)), dim3(256), 0, ctx->stream, ctx->d_set.as<uint64_t>(), cap,
-                           ctx->ws[4].as<uint64_t>(), list_cap, counters, tb, bb, bin_min, top_hist, top_shift);
+                           ctx->ws[PEP_WS_CANDS].as<uint64_t>(), list_cap, counters, tb, bb, bin_min, top_hist, top_shift);
         ctx->set_clean_slots = cap;
         struct { uint32_t counters[4]; unsigned long long stats[3]; uint32_t n_entries[4]; uint32_t pad[2]; uint32_t top[1 << PEP_SORT_TOP_BITS]; } h_all;
         // counters[0..3], the three statistics words, the index sizes per shape and the top-digit histogram of the candidate keys: one copy
@@ -1285,15 +1284,15 @@ int pep_find_candidates(pep_ctx *ctx, uint64_t **d_cands, uint64_t *n_cands, int
             for (uint32_t v : h_all.top) top_max = std::max(top_max, v);
             if (top_shift >= 0 && top_max <= PEP_SORT_TOP_CAP) {
                 // every bucket of the top digit fits LDS: partition + per-bucket sort, two launches
-                PEP_TRY(pep_sort_u64_two_level(ctx, ctx->ws[4].as<uint64_t>(), ctx->ws[5].as<uint64_t>(), n, key_bits, top_hist, &up));
-                *d_cands = ctx->ws[4].as<uint64_t>();
+                PEP_TRY(pep_sort_u64_two_level(ctx, ctx->ws[PEP_WS_CANDS].as<uint64_t>(), ctx->ws[PEP_WS_CANDS_TMP].as<uint64_t>(), n, key_bits, top_hist, &up));
+                *d_cands = ctx->ws[PEP_WS_CANDS].as<uint64_t>();
                 *n_cands = n;
                 return PEP_OK;
             }
             PEP_TRY(pep_zero_block(ctx, PEP_ZC_SORT, PEP_ZERO_SORT, 8 * 2048 * 4, &sort_hist));
-            PEP_TRY(pep_sort_u64(ctx, ctx->ws[4].as<uint64_t>(), ctx->ws[5].as<uint64_t>(), nullptr, n, qb + tb + bb, reinterpret_cast<uint32_t *>(sort_hist), &up));
+            PEP_TRY(pep_sort_u64(ctx, ctx->ws[PEP_WS_CANDS].as<uint64_t>(), ctx->ws[PEP_WS_CANDS_TMP].as<uint64_t>(), nullptr, n, qb + tb + bb, reinterpret_cast<uint32_t *>(sort_hist), &up));
         }
-        *d_cands = ctx->ws[4].as<uint64_t>();
+        *d_cands = ctx->ws[PEP_WS_CANDS].as<uint64_t>();
         *n_cands = n;
         return PEP_OK;
     }

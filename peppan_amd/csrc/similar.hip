@@ -207,6 +207,10 @@ __global__ __launch_bounds__(64) void k14_pair_support(SupportArgs a)
     if (lane == 0) a.value[g] = result;
 }
 
+// the slots of pep_ctx::ws (pep_pair_support)
+enum { K14_ROWS = 0, K14_CIGAR, K14_GROUPS, K14_SCR_ROWS, K14_SCR_SEQ, K14_SLOTS };
+static_assert(K14_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+
 }  // namespace
 
 static int pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *h_rows, const uint32_t *h_cigar, uint64_t n_cigar, uint64_t n_groups,
@@ -239,27 +243,27 @@ static int pair_support(pep_ctx *ctx, uint64_t n_rows, const pep_support_row *h_
     }
     batch_end.push_back(n_groups);
     const uint64_t total = cap;
-    // ws[0] rows, ws[1] cigar, ws[2] groups (off u64, scr u64, qlen u32, rlen u32, value i32), ws[3] scratch bytes x2, ws[4] scratch u32
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], (n_rows + 1) * sizeof(pep_support_row)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[1], (n_cigar + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[2], (n_groups + 1) * (8 + 8 + 4 + 4 + 4) + 64));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[3], 2 * total + 64));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[4], total * 4 + 64));
-    char *gb = ctx->ws[2].as<char>();
+    // (the slots: K14_* above; K14_GROUPS holds off u64, scr u64, qlen u32, rlen u32, value i32 per group, K14_SCR_ROWS two byte rows, K14_SCR_SEQ one of u32)
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K14_ROWS], (n_rows + 1) * sizeof(pep_support_row)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K14_CIGAR], (n_cigar + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K14_GROUPS], (n_groups + 1) * (8 + 8 + 4 + 4 + 4) + 64));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K14_SCR_ROWS], 2 * total + 64));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K14_SCR_SEQ], total * 4 + 64));
+    char *gb = ctx->ws[K14_GROUPS].as<char>();
     uint64_t *d_off = reinterpret_cast<uint64_t *>(gb), *d_scr = d_off + n_groups + 1;
     uint32_t *d_ql = reinterpret_cast<uint32_t *>(d_scr + n_groups + 1), *d_rl = d_ql + n_groups + 1;
     int32_t *d_val = reinterpret_cast<int32_t *>(d_rl + n_groups + 1);
     hipStream_t st = ctx->stream;
-    if (n_rows) PEP_TRY(pep_h2d(ctx, ctx->ws[0].p, h_rows, n_rows * sizeof(pep_support_row)));
-    if (n_cigar) PEP_TRY(pep_h2d(ctx, ctx->ws[1].p, h_cigar, n_cigar * 4));
+    if (n_rows) PEP_TRY(pep_h2d(ctx, ctx->ws[K14_ROWS].p, h_rows, n_rows * sizeof(pep_support_row)));
+    if (n_cigar) PEP_TRY(pep_h2d(ctx, ctx->ws[K14_CIGAR].p, h_cigar, n_cigar * 4));
     PEP_TRY(pep_h2d(ctx, d_off, h_grp_off, (n_groups + 1) * 8));
     PEP_TRY(pep_h2d(ctx, d_scr, scr.data(), (n_groups + 1) * 8));
     PEP_TRY(pep_h2d(ctx, d_ql, h_qlen, n_groups * 4));
     PEP_TRY(pep_h2d(ctx, d_rl, h_rlen, n_groups * 4));
     SupportArgs a;
-    a.rows = ctx->ws[0].as<const pep_support_row>(); a.cigar = ctx->ws[1].as<const uint32_t>();
+    a.rows = ctx->ws[K14_ROWS].as<const pep_support_row>(); a.cigar = ctx->ws[K14_CIGAR].as<const uint32_t>();
     a.grp_off = d_off; a.grp_qlen = d_ql; a.grp_rlen = d_rl; a.scr_off = d_scr;
-    a.last_row = ctx->ws[3].as<uint8_t>(); a.val_row = a.last_row + total; a.seq = ctx->ws[4].as<uint32_t>();
+    a.last_row = ctx->ws[K14_SCR_ROWS].as<uint8_t>(); a.val_row = a.last_row + total; a.seq = ctx->ws[K14_SCR_SEQ].as<uint32_t>();
     a.value = d_val; a.n_groups = n_groups; a.lim = *lim;
     for (uint64_t b = 0, g0 = 0; b < batch_end.size(); g0 = batch_end[b++]) {             // (one launch unless the scratch budget splits the groups)
         a.g_base = g0;

@@ -930,10 +930,10 @@ __global__ void dpp_selftest(int *out)
 
 int pep_selftest_dpp(pep_ctx *ctx)
 {
-    PEP_TRY(dev_reserve(ctx, ctx->ws[9], 128 * sizeof(int)));
-    hipLaunchKernelGGL(dpp_selftest, dim3(1), dim3(64), 0, ctx->stream, ctx->ws[9].as<int>());
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_DPP_SELFTEST], 128 * sizeof(int)));
+    hipLaunchKernelGGL(dpp_selftest, dim3(1), dim3(64), 0, ctx->stream, ctx->ws[PEP_WS_DPP_SELFTEST].as<int>());
     int h[128];
-    PEP_HIP(ctx, hipMemcpyAsync(h, ctx->ws[9].p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    PEP_HIP(ctx, hipMemcpyAsync(h, ctx->ws[PEP_WS_DPP_SELFTEST].p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     PEP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int l = 0; l < 64; ++l) {
         const int e_shr = l == 0 ? -1 : l - 1, e_shl = l == 63 ? -2 : l + 1;
@@ -942,8 +942,8 @@ int pep_selftest_dpp(pep_ctx *ctx)
     return PEP_OK;
 }
 
-// Runs K5 over `n` candidate keys.  trace = false: score pass (ws[12] <- score / end cell / a0 per candidate).
-// trace = true: same DP plus traceback codes (ws[11] dir_off u64[n+1], ws[13] dirs).  ws[10] nblk, ws[14] scan input.
+// Runs K5 over `n` candidate keys.  trace = false: score pass (score / end cell / a0 per candidate).
+// trace = true: same DP plus traceback codes.  The workspace slots: PepWsSlot, PEP_WS_SW_* and PEP_WS_TRACE_DIRS (common.h).
 // d_n (traceback pass, optional): the number of candidates lives on the device and `n` is an upper bound of it (grids and buffers are
 // sized from the bound).  dir_blocks_bound (traceback pass, optional): an upper bound of the pass's 16-step blocks - with it the traceback
 // area is sized without the host ever seeing the totals (no synchronisation in here; the caller reads the counter block *d_hdr -
@@ -954,10 +954,10 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
     const pep_search_params &P = ctx->params;
     if (d_hdr) *d_hdr = nullptr;
     if (n == 0) return PEP_OK;
-    PEP_TRY(dev_reserve(ctx, ctx->ws[10], (n + 1) * sizeof(uint32_t)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[11], (n + 2) * sizeof(uint64_t)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[14], (n + 2) * sizeof(uint64_t)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[12], (n + 1) * sizeof(int4)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_NBLK], (n + 1) * sizeof(uint32_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_DIR_OFF], (n + 2) * sizeof(uint64_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_SCAN_IN], (n + 2) * sizeof(uint64_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_OUT], (n + 1) * sizeof(int4)));
     if (n >= (1ull << 32)) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_sw_run: more than 2^32 candidates in one launch");
     // per-wave staging area (u16 per residue; score pass: query + target windows of two candidates, traceback pass: of four candidates'
     // sub-bands), sized for the longest possible pair, capped at 8 KiB: two blocks of eight wavefronts per CU next to their table images
@@ -981,14 +981,14 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
         nb_limit = std::min<uint32_t>(nb_limit, LEN_BUCKETS - 2);
     }
     // counter block of this pass (d_zero): [0..63] totals (cells, 16-step blocks, work-queue counters, candidates above nb_limit, candidates in
-    // the order), [64..) length histogram, then the scatter cursors; ws[15]: the order itself
+    // the order), [64..) length histogram, then the scatter cursors; PEP_WS_SW_ORDER: the order itself
     static_assert(PEP_ZERO_SW_BYTES == 64 + 2 * LEN_BUCKETS * sizeof(uint32_t), "counter block of a Smith-Waterman pass");
     void *zb = nullptr;
     PEP_TRY(pep_zero_block(ctx, trace ? PEP_ZC_SW_TRACE : PEP_ZC_SW_SCORE, trace ? PEP_ZERO_SW_TRACE : PEP_ZERO_SW_SCORE, PEP_ZERO_SW_BYTES, &zb));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[15], (n + 1) * sizeof(uint32_t)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_ORDER], (n + 1) * sizeof(uint32_t)));
     unsigned long long *cells = reinterpret_cast<unsigned long long *>(zb);
     if (d_hdr) *d_hdr = cells;
-    uint32_t *len_hist = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(zb) + 64), *cursor = len_hist + LEN_BUCKETS, *order = ctx->ws[15].as<uint32_t>();
+    uint32_t *len_hist = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(zb) + 64), *cursor = len_hist + LEN_BUCKETS, *order = ctx->ws[PEP_WS_SW_ORDER].as<uint32_t>();
     uint64_t *lb_state = nullptr, lb_epoch = 0;
     uint32_t lb_ticket = 0;
     const uint64_t prep_tiles = ceil_div(n + (trace ? 1 : 0), 256);        // (the traceback pass writes one entry more: the total)
@@ -998,7 +998,7 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
     // and the check is a launch and a chain of loads of its own (8x1 cell of the benchmark, 6 163 candidates: 0.965 -> 1.0 ms with it)
     const int32_t *skip = trace ? d_skip_mode : nullptr;
     if (!trace && (P.reserved2 & 2) == 0 && (n >= 16384 || (P.reserved2 & 4)) && P.gap_ext >= 0 && P.gap_open + P.gap_ext > 0) {       // (the argument needs gaps that cost something)
-        PEP_TRY(dev_reserve(ctx, ctx->ws[13], (n + 1) * sizeof(int32_t)));          // (the traceback codes' buffer: not in use before the traceback pass)
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SW_SKIP_MODE], (n + 1) * sizeof(int32_t)));
         IdentArgs ia;
         ia.dominant = ia.harmless = 0;
         for (int r = 0; r < 32; ++r) {
@@ -1013,13 +1013,13 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
         }
         hipLaunchKernelGGL(identical_check, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, ctx->stream, d_cands, n, ctx->q.res.as<const uint8_t>(), ctx->q.off.as<const uint32_t>(),
                            ctx->q.len.as<const uint32_t>(), ctx->t.res.as<const uint8_t>(), ctx->t.off.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), ia,
-                           ctx->ws[12].as<int4>(), ctx->ws[13].as<int32_t>());
-        skip = ctx->ws[13].as<const int32_t>();
+                           ctx->ws[PEP_WS_SW_OUT].as<int4>(), ctx->ws[PEP_WS_SW_SKIP_MODE].as<int32_t>());
+        skip = ctx->ws[PEP_WS_SW_SKIP_MODE].as<const int32_t>();
     }
     hipLaunchKernelGGL(sw_prep, dim3((unsigned)prep_tiles), dim3(256), 0, ctx->stream, d_cands, n, trace ? d_n : nullptr, ctx->q.len.as<const uint32_t>(),
-                       ctx->t.len.as<const uint32_t>(), ctx->ws[10].as<uint32_t>(), ctx->ws[14].as<uint64_t>(), cells, len_hist, nb_limit, skip, trace ? 0 : 1,
-                       ctx->ws[11].as<uint64_t>(), lb_state, lb_ticket, lb_epoch);
-    hipLaunchKernelGGL(sw_order, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, ctx->ws[10].as<const uint32_t>(), n, trace ? d_n : nullptr,
+                       ctx->t.len.as<const uint32_t>(), ctx->ws[PEP_WS_SW_NBLK].as<uint32_t>(), ctx->ws[PEP_WS_SW_SCAN_IN].as<uint64_t>(), cells, len_hist, nb_limit, skip, trace ? 0 : 1,
+                       ctx->ws[PEP_WS_SW_DIR_OFF].as<uint64_t>(), lb_state, lb_ticket, lb_epoch);
+    hipLaunchKernelGGL(sw_order, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>(), n, trace ? d_n : nullptr,
                        (const uint32_t *)len_hist, cursor, order, skip);
     if (trace) {
         uint64_t total_blk = dir_blocks_bound;
@@ -1034,7 +1034,7 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
             ctx->stats.cells_swept_trace += total_blk * 16 * 64;
             ctx->stats.dir_bytes += total_blk * 512;
         }
-        PEP_TRY(dev_reserve(ctx, ctx->ws[13], total_blk * 512 + 512));
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_TRACE_DIRS], total_blk * 512 + 512));
         PEP_TRY(dev_reserve(ctx, ctx->d_trace_mode, (n + 1) * sizeof(int32_t)));
         PEP_TRY(dev_reserve(ctx, ctx->d_trace_defer, (n + 1) * sizeof(uint32_t)));
     }
@@ -1045,8 +1045,8 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
     a.q_off = ctx->q.off.as<const uint32_t>(); a.q_len = ctx->q.len.as<const uint32_t>();
     a.t_off = ctx->t.off.as<const uint32_t>(); a.t_len = ctx->t.len.as<const uint32_t>();
     a.sub_image = ctx->sub_lds.as<const uint32_t>();
-    a.dir_off = ctx->ws[11].as<const uint64_t>(); a.nblk = ctx->ws[10].as<const uint32_t>();
-    a.dirs = trace ? ctx->ws[13].as<uint32_t>() : nullptr; a.out = ctx->ws[12].as<int4>();
+    a.dir_off = ctx->ws[PEP_WS_SW_DIR_OFF].as<const uint64_t>(); a.nblk = ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>();
+    a.dirs = trace ? ctx->ws[PEP_WS_TRACE_DIRS].as<uint32_t>() : nullptr; a.out = ctx->ws[PEP_WS_SW_OUT].as<int4>();
     a.oe = P.gap_open + P.gap_ext; a.ext = P.gap_ext;
     a.pk16 = pk16;
     a.known = trace ? d_known : nullptr;

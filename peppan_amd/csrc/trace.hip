@@ -579,8 +579,7 @@ __global__ __launch_bounds__(256) void pack_out(const unsigned long long *__rest
 
 }  // namespace
 
-// workspace slots: ws[16] flag, ws[17] pos, ws[18] best_idx, ws[19] sel, ws[20] run_cap/run_off (u64 x2) + selected keys,
-//                  ws[21] runs, ws[22] keep arrays, ws[23] output hits + cigar, ws[9] small counters
+// Workspace slots: PepWsSlot (common.h); the small counters come from pep_zero_block.
 //
 // Host round trips.  Between the seed stage's count of candidates and the sizes of the result (hits, CIGAR runs) the host does not need
 // to see anything: the number of selected pairs stays on the device (every kernel behind the selection reads it there and is launched on
@@ -642,7 +641,7 @@ int pep_extend_finish(pep_ctx *ctx)
 int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t *h_min_score, pep_result *res, bool defer)
 {
     const pep_search_params &P = ctx->params;
-    pep_drop_dev_result(ctx);                     // ws[23] is about to be rewritten
+    pep_drop_dev_result(ctx);                     // PEP_WS_HITS_OUT is about to be rewritten
     res->hits.clear();
     res->cigar.clear();
     ctx->stats.candidates = n;
@@ -666,7 +665,7 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
 
     pep_timer_begin(ctx, TM_TRACE);
 
-    const int4 *sw = ctx->ws[12].as<const int4>();
+    const int4 *sw = ctx->ws[PEP_WS_SW_OUT].as<const int4>();
     // the block the host reads: u32 [0] (q, t) pairs, [1] selected pairs, [2] hits; u64 [2] CIGAR runs of the hits, [3] run capacity of the selected
     // pairs, [4] [5] cells / 16-step blocks of the score pass, [6] [7] [8] cells / blocks / swept pairs of the traceback pass
     void *zb = nullptr;
@@ -680,12 +679,12 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
     const unsigned gb = (unsigned)ceil_div(n, 256);
     // selection, compaction and the run slots of the selected pairs in one launch (select_gather); the arrays of the selected pairs are laid
     // out for n entries (every candidate selected) whatever the count turns out to be
-    PEP_TRY(dev_reserve(ctx, ctx->ws[19], (size_t)n * sizeof(SelInfo)));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[20], ((size_t)n + 2) * 8 * 2));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[8], ((size_t)n + 2) * 4 * 2));      // ws[8]: raw seed hits of K4, free again
-    int32_t *known = ctx->ws[8].as<int32_t>(), *end_lane = known + n + 2;
-    SelInfo *sel = ctx->ws[19].as<SelInfo>();
-    uint64_t *run_off = ctx->ws[20].as<uint64_t>(), *sel_keys = run_off + n + 2;
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SEL], (size_t)n * sizeof(SelInfo)));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_SEL_RUNS_KEYS], ((size_t)n + 2) * 8 * 2));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_TRACE_KNOWN], ((size_t)n + 2) * 4 * 2));
+    int32_t *known = ctx->ws[PEP_WS_TRACE_KNOWN].as<int32_t>(), *end_lane = known + n + 2;
+    SelInfo *sel = ctx->ws[PEP_WS_SEL].as<SelInfo>();
+    uint64_t *run_off = ctx->ws[PEP_WS_SEL_RUNS_KEYS].as<uint64_t>(), *sel_keys = run_off + n + 2;
     {
         SelectState ss;
         uint64_t ep = 0;
@@ -714,22 +713,22 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
     if (n_b) {
         uint64_t total_runs = run_bound;
         if (!fast) PEP_TRY(pep_read_back(ctx, &total_runs, mail + 3, 8));         // arrives with the synchronisation inside pep_sw_run (block total)
-        // ---- rule 5a: pairs whose alignment is one ungapped run are settled without a sweep (the score-pass results in ws[12] have been
+        // ---- rule 5a: pairs whose alignment is one ungapped run are settled without a sweep (the score-pass results in PEP_WS_SW_OUT have been
         // consumed by gather_sel: the slots of the selected pairs are written from here on)
         PEP_TRY(dev_reserve(ctx, ctx->d_trace_mode, ((size_t)n_b + 1) * sizeof(int32_t)));
         PEP_TRY(pep_upload_sub_table(ctx));                                 // (K9 drives this stage without the seed stage in front)
         hipLaunchKernelGGL(gapless_check, dim3((unsigned)ceil_div(n_b, 4)), dim3(256), 0, st, d_n_sel, (const uint64_t *)sel_keys, (const int32_t *)known,
                            (const int32_t *)end_lane, ctx->q.res.as<const uint8_t>(), ctx->q.off.as<const uint32_t>(), ctx->q.len.as<const uint32_t>(),
                            ctx->t.res.as<const uint8_t>(), ctx->t.off.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), ctx->d_params.as<const int8_t>(),
-                           ctx->ws[12].as<int4>(), ctx->d_trace_mode.as<int32_t>());
+                           ctx->ws[PEP_WS_SW_OUT].as<int4>(), ctx->d_trace_mode.as<int32_t>());
         // ---- pass 2: the same DP with traceback codes, the remaining selected pairs only
         PEP_TRY(pep_sw_run(ctx, sel_keys, n_b, true, known, end_lane, ctx->d_trace_mode.as<const int32_t>(), d_n_sel, fast ? dir_blocks_bound : 0, &trace_hdr));
-        const int4 *sw2 = ctx->ws[12].as<const int4>();
-        PEP_TRY(dev_reserve(ctx, ctx->ws[21], (total_runs + 1) * 4));
-        runs = ctx->ws[21].as<uint32_t>();
+        const int4 *sw2 = ctx->ws[PEP_WS_SW_OUT].as<const int4>();
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_RUNS], (total_runs + 1) * 4));
+        runs = ctx->ws[PEP_WS_RUNS].as<uint32_t>();
         const unsigned gfin = (unsigned)ceil_div(n_b, 256 / FIN_LANES);
-        hipLaunchKernelGGL(walk, dim3((unsigned)ceil_div(n_b, WALK_LANES)), dim3(WALK_LANES), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, sw2, ctx->ws[11].as<const uint64_t>(),
-                           ctx->ws[13].as<const uint32_t>(), ctx->d_trace_mode.as<const int32_t>(), (const uint64_t *)run_off, runs);
+        hipLaunchKernelGGL(walk, dim3((unsigned)ceil_div(n_b, WALK_LANES)), dim3(WALK_LANES), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, sw2, ctx->ws[PEP_WS_SW_DIR_OFF].as<const uint64_t>(),
+                           ctx->ws[PEP_WS_TRACE_DIRS].as<const uint32_t>(), ctx->d_trace_mode.as<const int32_t>(), (const uint64_t *)run_off, runs);
         hipLaunchKernelGGL(finalize, dim3(gfin), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, ctx->q.res.as<const uint8_t>(),
                            ctx->q.off.as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.res.as<const uint8_t>(),
                            ctx->t.off.as<const uint32_t>(), (const uint64_t *)run_off, (const uint32_t *)runs, P.min_id_pct, P.min_qcov_pct);
@@ -752,8 +751,8 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
                                ctx->t_class_ready ? ctx->d_t_class.as<const uint32_t>() : (const uint32_t *)nullptr, t_subject);
         }
         // top-k, then compaction of hits and CIGAR runs
-        PEP_TRY(dev_reserve(ctx, ctx->ws[22], ((size_t)n_b + 2) * (4 + 4 + 8)));
-        keep_flag = ctx->ws[22].as<uint32_t>(); hit_pos = keep_flag + n_b + 2;
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_KEEP], ((size_t)n_b + 2) * (4 + 4 + 8)));
+        keep_flag = ctx->ws[PEP_WS_KEEP].as<uint32_t>(); hit_pos = keep_flag + n_b + 2;
         cig_pos = reinterpret_cast<uint64_t *>(hit_pos + n_b + 2);
         {
             SelectState ts;
@@ -770,16 +769,16 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
         if (fast && !ctx->device_results && pin_reserve(ctx, ctx->pin_stage, PACK_HEADER) == PEP_OK) {
             // the result leaves through pack_out: output buffers from the same upper bounds, no look at the sizes, no synchronisation here
             const size_t hb_bound = (size_t)n_b * sizeof(pep_hit);
-            PEP_TRY(dev_reserve(ctx, ctx->ws[23], hb_bound + (run_bound + 1) * 4));
-            pep_hit *d_hits = ctx->ws[23].as<pep_hit>();
-            uint32_t *d_cig = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->ws[23].p) + hb_bound);
+            PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_HITS_OUT], hb_bound + (run_bound + 1) * 4));
+            pep_hit *d_hits = ctx->ws[PEP_WS_HITS_OUT].as<pep_hit>();
+            uint32_t *d_cig = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->ws[PEP_WS_HITS_OUT].p) + hb_bound);
             PEP_TRY(dev_reserve(ctx, ctx->d_mail_copy, 128));
             unsigned long long *mail_copy = ctx->d_mail_copy.as<unsigned long long>();
             uint32_t *parent = nullptr;
-            if (ctx->grp_nodes) { PEP_TRY(dev_reserve(ctx, ctx->ws[0], (size_t)ctx->grp_nodes * 4)); parent = ctx->ws[0].as<uint32_t>(); }      // (K10 follows: pep_k10_queue)
+            if (ctx->grp_nodes) { PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)ctx->grp_nodes * 4)); parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>(); }      // (K10 follows: pep_k10_queue)
             hipLaunchKernelGGL(emit, dim3((unsigned)ceil_div(n_b, 4)), dim3(256), 0, st, d_n_sel, (const SelInfo *)sel, (const uint64_t *)sel_keys, (const uint32_t *)keep_flag,
                                (const uint32_t *)hit_pos, (const uint64_t *)cig_pos, (const uint64_t *)run_off, (const uint32_t *)runs,
-                               ctx->ws[10].as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig,
+                               ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig,
                                (const unsigned long long *)mail, mail_copy);
             hipLaunchKernelGGL(pack_out, dim3(1024), dim3(256), 0, st, (const unsigned long long *)mail_copy, (const pep_hit *)d_hits, (const uint32_t *)d_cig,
                                ctx->pin_stage.p, (unsigned long long)ctx->pin_stage.cap, ctx->d_zero.as<uint32_t>(), (uint32_t)(PEP_ZERO_TOTAL / 4), parent, ctx->grp_nodes);
@@ -823,19 +822,19 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
     if (n_hits) {
         const uint32_t n_sel = h_mail.n_sel;
         const size_t hb = (size_t)n_hits * sizeof(pep_hit);
-        PEP_TRY(dev_reserve(ctx, ctx->ws[23], hb + (n_cig + 1) * 4));
-        pep_hit *d_hits = ctx->ws[23].as<pep_hit>();
-        uint32_t *d_cig = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->ws[23].p) + hb);
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_HITS_OUT], hb + (n_cig + 1) * 4));
+        pep_hit *d_hits = ctx->ws[PEP_WS_HITS_OUT].as<pep_hit>();
+        uint32_t *d_cig = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->ws[PEP_WS_HITS_OUT].p) + hb);
         hipLaunchKernelGGL(emit, dim3((unsigned)ceil_div(n_sel, 4)), dim3(256), 0, st, d_n_sel, (const SelInfo *)sel, (const uint64_t *)sel_keys, (const uint32_t *)keep_flag,
                            (const uint32_t *)hit_pos, (const uint64_t *)cig_pos, (const uint64_t *)run_off, (const uint32_t *)runs,
-                           ctx->ws[10].as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig);
+                           ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig);
         PEP_HIP(ctx, hipGetLastError());
         // the table goes to the context's pinned staging area (DMA speed, no page faults); pep_result_copy reads it from there.
         // If the host refuses that much pinned memory the result owns ordinary vectors instead.  In device-result mode
         // (pep_set_result_mode) nothing is copied here: whoever wants the host copy fetches it later (pep_fetch_result).
         if (ctx->device_results) {
         } else if (pin_reserve(ctx, ctx->pin_stage, hb + (n_cig + 1) * 4) == PEP_OK) {
-            PEP_HIP(ctx, hipMemcpyAsync(ctx->pin_stage.p, d_hits, hb + n_cig * 4, hipMemcpyDeviceToHost, st));       // hits and arena are adjacent in ws[23]
+            PEP_HIP(ctx, hipMemcpyAsync(ctx->pin_stage.p, d_hits, hb + n_cig * 4, hipMemcpyDeviceToHost, st));       // hits and arena are adjacent in PEP_WS_HITS_OUT
             res->st_hits = reinterpret_cast<const pep_hit *>(ctx->pin_stage.p);
             res->st_cigar = reinterpret_cast<const uint32_t *>(ctx->pin_stage.p + hb);
         } else {

@@ -708,6 +708,23 @@ int k1_ref_finish(pep_ctx *ctx)
     return PEP_OK;
 }
 
+// The slots of pep_ctx::ws: the query side's, then the reference side's.  The two sides share slots with each other and with the seed stage (PepWsSlot), whose
+// kernels pep_search queues right behind them without a wait: stream order is what makes that safe - a side's kernels have read their slots before anything
+// queued later writes them - and what has to outlive the call (descriptors, summaries) has buffers of its own.
+enum {
+    K1Q_SPARE_A = 0, K1Q_SPARE_B = 1,       // reserved for n + 1 words each, used by no kernel
+    K1Q_PADDED = 3,                         // padded length per query, u32: k1_query_frames, read last by k1_offsets
+    K1Q_PACK_SCAN = 4,                      // handed to layout_and_pack, which touches neither of its two workspace arguments (with K1Q_PACK_TMP)
+    K1Q_COUNT = 5,                          // number of queries, u32: k1_query_frames, read last by k1_pack
+    K1Q_PACK_TMP = 6,
+    K1R_CHUNK_CNT = 1, K1R_CHUNK_OFF, K1R_CHUNK_LEN,    // chunks per frame u32; first residue and length per chunk slot u32: k1_ref_chunks(_mask), read last by k1_ref_desc(_fill)
+    K1R_FIRST = 5,                          // first packed sequence per frame, the number of targets behind them, u32: k1_ref_desc, read last by k1_pack
+    K1R_PADDED,                             // padded length per target, u32: k1_ref_desc(_fill), read last by k1_offsets
+    K1R_PACK_SCAN, K1R_PACK_TMP,            // handed to layout_and_pack (as K1Q_PACK_SCAN)
+    K1_SLOTS
+};
+static_assert(K1Q_PACK_TMP < K1_SLOTS && K1_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+
 }  // namespace
 
 // phase 1 = queue the device work and the download of the descriptors, 2 = wait for it and build the host-side tables, 0 = both.
@@ -721,23 +738,23 @@ int pep_k1_query(pep_ctx *ctx, int gtable, int phase)
         PEP_TRY(upload_codon_table(ctx));
         if (n > PEP_MAX_QUERIES) return pep_fail(ctx, PEP_ERR_LIMIT, "too many queries");
         DevBuf *W = ctx->ws;
-        PEP_TRY(dev_reserve(ctx, W[0], ((size_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[1], ((size_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K1Q_SPARE_A], ((size_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K1Q_SPARE_B], ((size_t)n + 1) * 4));
         DevBuf &D = ctx->d_k1_desc_q;              // the descriptors stay on the device (a buffer of their own): fetched when somebody asks for the host tables
         PEP_TRY(dev_reserve(ctx, D, (2 * (size_t)n + 4) * sizeof(PackDesc)));      // + the summary and the source records behind the descriptors
         PEP_TRY(pin_reserve(ctx, ctx->pin_k1q, sizeof(K1Summary) + ((size_t)n + 1) * 4));
         K1Summary *pin_sum = reinterpret_cast<K1Summary *>(ctx->pin_k1q.p);
         uint32_t *pin_len = reinterpret_cast<uint32_t *>(ctx->pin_k1q.p + sizeof(K1Summary));
-        PEP_TRY(dev_reserve(ctx, W[3], ((size_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[5], 16));
+        PEP_TRY(dev_reserve(ctx, W[K1Q_PADDED], ((size_t)n + 1) * 4));
+        PEP_TRY(dev_reserve(ctx, W[K1Q_COUNT], 16));
         const uint64_t upper = 2 * PEP_END_PAD + (nt.total + 2 * (uint64_t)n) / 3 + (uint64_t)n * (16 + PEP_SEQ_GAP);
         PEP_TRY(reserve_packed(ctx, ctx->q, n, upper));
         if (n) hipLaunchKernelGGL(k1_query_frames, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, tab,
-                                  D.as<PackDesc>(), W[3].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[5].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len,
+                                  D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len,
                                   k1_src_of(D.as<const PackDesc>(), n));
         else hipLaunchKernelGGL(k1_query_desc, dim3(1), dim3(64), 0, ctx->stream, 0u, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                                D.as<PackDesc>(), W[3].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[5].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len);
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[3].as<const uint32_t>(), n, W[5].as<const uint32_t>(), upper, ctx->q, W[4], W[6], pin_sum));
+                                D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len);
+        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1Q_PADDED].as<const uint32_t>(), n, W[K1Q_COUNT].as<const uint32_t>(), upper, ctx->q, W[K1Q_PACK_SCAN], W[K1Q_PACK_TMP], pin_sum));
         // an event of its own: whoever waits for the query side must not wait for what was queued behind it (pep_search queues the reference side next)
         ctx->k1q_event_set = false;
         if (ctx->k1q_event.ensure(pep_wait_event_flags()))
@@ -854,22 +871,22 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
     const uint64_t slots = ctx->k1_base[nw], upper = ctx->k1_upper;
     if (slots > PEP_MAX_TARGETS) return pep_fail(ctx, PEP_ERR_LIMIT, "too many targets");
     DevBuf *W = ctx->ws;
-    PEP_TRY(dev_reserve(ctx, W[1], (nw + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[2], (slots + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, W[3], (slots + 1) * 4));
-    DevBuf &D = ctx->d_k1_desc_t;                  // the descriptors stay on the device (a buffer of their own: ws[] is the seed stage's next)
+    PEP_TRY(dev_reserve(ctx, W[K1R_CHUNK_CNT], (nw + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K1R_CHUNK_OFF], (slots + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K1R_CHUNK_LEN], (slots + 1) * 4));
+    DevBuf &D = ctx->d_k1_desc_t;                  // the descriptors stay on the device (a buffer of their own: the workspace slots are the seed stage's next)
     PEP_TRY(dev_reserve(ctx, D, (2 * slots + 4) * sizeof(PackDesc)));             // + the summary and the source records behind the descriptors
     PEP_TRY(pin_reserve(ctx, ctx->pin_k1, sizeof(K1Summary)));
     K1Summary *pin_sum = reinterpret_cast<K1Summary *>(ctx->pin_k1.p);
-    PEP_TRY(dev_reserve(ctx, W[5], (nw + 2) * 4));
-    PEP_TRY(dev_reserve(ctx, W[6], (slots + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K1R_FIRST], (nw + 2) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K1R_PADDED], (slots + 1) * 4));
     PEP_TRY(reserve_packed(ctx, ctx->t, (uint32_t)slots, upper));
     PEP_TRY(dev_reserve(ctx, ctx->d_self_t, ((size_t)n + 1) * 4));
     ctx->self_first_n = n;
     const uint64_t *d_base = ctx->d_k1_base.as<const uint64_t>();
     if (nw) {
         hipLaunchKernelGGL(k1_ref_chunks, dim3((unsigned)ceil_div(nw, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, nf, tab,
-                           d_base, W[1].as<uint32_t>(), W[2].as<uint32_t>(), W[3].as<uint32_t>(), ctx->k1_n_long ? K1_LONG : INT64_MAX);
+                           d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>(), ctx->k1_n_long ? K1_LONG : INT64_MAX);
         if (ctx->k1_n_long) {
             // the frames of contigs: their stops as a bit mask (all frames side by side), then the chunk chain of every frame out of register windows of that mask
             const K1Long *d_longs = ctx->d_k1_long.as<const K1Long>();
@@ -877,29 +894,29 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
             hipLaunchKernelGGL(k1_stop_mask, dim3((unsigned)ceil_div(ctx->k1_n_seg, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), nf, tab,
                                ctx->d_k1_seg.as<const K1Seg>(), ctx->k1_n_seg, d_longs, d_long_of_w, ctx->d_k1_spec.as<unsigned long long>());
             hipLaunchKernelGGL(k1_ref_chunks_mask, dim3((unsigned)ceil_div(ctx->k1_n_long, 4)), dim3(256), 0, ctx->stream, nt.off.as<const uint64_t>(), nf, d_longs, ctx->k1_n_long,
-                               ctx->d_k1_spec.as<const unsigned long long>(), d_base, W[1].as<uint32_t>(), W[2].as<uint32_t>(), W[3].as<uint32_t>());
+                               ctx->d_k1_spec.as<const unsigned long long>(), d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>());
         }
         {
             K1Scan sc;
             const uint64_t tiles = ceil_div(nw, 256);
             PEP_TRY(pep_lookback_begin(ctx, ctx->scan_state[0], tiles, (1u << 30) - 1, &sc.state, &sc.ticket_base, &sc.epoch));
-            hipLaunchKernelGGL(k1_ref_desc, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nw, nf, d_base, W[1].as<const uint32_t>(),
-                               W[2].as<const uint32_t>(), W[3].as<const uint32_t>(), D.as<PackDesc>(), W[6].as<uint32_t>(),
-                               ctx->t.len.as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + slots), W[5].as<uint32_t>() + nw, sc,
-                               nt.off.as<const uint64_t>(), k1_src_of(D.as<const PackDesc>(), (uint32_t)slots), ctx->d_self_t.as<uint32_t>(), W[5].as<uint32_t>(),
-                               ctx->k1_n_tiles ? K1_FILL_FROM : 0xFFFFFFFFu);         // W[5][nw] = number of targets, W[5][w] = the first packed sequence of frame w
+            hipLaunchKernelGGL(k1_ref_desc, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nw, nf, d_base, W[K1R_CHUNK_CNT].as<const uint32_t>(),
+                               W[K1R_CHUNK_OFF].as<const uint32_t>(), W[K1R_CHUNK_LEN].as<const uint32_t>(), D.as<PackDesc>(), W[K1R_PADDED].as<uint32_t>(),
+                               ctx->t.len.as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + slots), W[K1R_FIRST].as<uint32_t>() + nw, sc,
+                               nt.off.as<const uint64_t>(), k1_src_of(D.as<const PackDesc>(), (uint32_t)slots), ctx->d_self_t.as<uint32_t>(), W[K1R_FIRST].as<uint32_t>(),
+                               ctx->k1_n_tiles ? K1_FILL_FROM : 0xFFFFFFFFu);         // W[K1R_FIRST][nw] = number of targets, W[K1R_FIRST][w] = the first packed sequence of frame w
             if (ctx->k1_n_tiles)
-                hipLaunchKernelGGL(k1_ref_desc_fill, dim3(ctx->k1_n_tiles), dim3(256), 0, ctx->stream, ctx->d_k1_tiles.as<const K1Seg>(), nf, d_base, W[1].as<const uint32_t>(),
-                                   W[2].as<const uint32_t>(), W[3].as<const uint32_t>(), W[5].as<const uint32_t>(), K1_FILL_FROM, D.as<PackDesc>(), W[6].as<uint32_t>(),
+                hipLaunchKernelGGL(k1_ref_desc_fill, dim3(ctx->k1_n_tiles), dim3(256), 0, ctx->stream, ctx->d_k1_tiles.as<const K1Seg>(), nf, d_base, W[K1R_CHUNK_CNT].as<const uint32_t>(),
+                                   W[K1R_CHUNK_OFF].as<const uint32_t>(), W[K1R_CHUNK_LEN].as<const uint32_t>(), W[K1R_FIRST].as<const uint32_t>(), K1_FILL_FROM, D.as<PackDesc>(), W[K1R_PADDED].as<uint32_t>(),
                                    ctx->t.len.as<uint32_t>(), nt.off.as<const uint64_t>(), k1_src_of(D.as<const PackDesc>(), (uint32_t)slots));
         }
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[6].as<const uint32_t>(), (uint32_t)slots, W[5].as<const uint32_t>() + nw, upper, ctx->t,
-                                W[7], W[8], pin_sum));
+        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), (uint32_t)slots, W[K1R_FIRST].as<const uint32_t>() + nw, upper, ctx->t,
+                                W[K1R_PACK_SCAN], W[K1R_PACK_TMP], pin_sum));
     } else {
-        PEP_HIP(ctx, hipMemsetAsync(W[5].p, 0, 8, ctx->stream));
-        PEP_HIP(ctx, hipMemsetAsync(W[6].p, 0, 4, ctx->stream));
+        PEP_HIP(ctx, hipMemsetAsync(W[K1R_FIRST].p, 0, 8, ctx->stream));
+        PEP_HIP(ctx, hipMemsetAsync(W[K1R_PADDED].p, 0, 4, ctx->stream));
         PEP_HIP(ctx, hipMemsetAsync(D.p, 0, 3 * sizeof(PackDesc), ctx->stream));               // (the summary's accumulators)
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[6].as<const uint32_t>(), 0, W[5].as<const uint32_t>(), upper, ctx->t, W[7], W[8], pin_sum));
+        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), 0, W[K1R_FIRST].as<const uint32_t>(), upper, ctx->t, W[K1R_PACK_SCAN], W[K1R_PACK_TMP], pin_sum));
     }
     // the summary has been written into pinned memory by k1_pack; an event marks the point of the stream where it is there
     ctx->k1_desc_cap = (uint32_t)slots;

@@ -60,6 +60,10 @@ __global__ __launch_bounds__(256) void uf_flatten(uint32_t *parent, uint32_t *__
     if (i < n) label[i] = uf_root(parent, i);
 }
 
+// the slots of pep_ctx::ws (the parents: PEP_WS_UF_PARENT of common.h, which the search's emit stage prepares for pep_k10_queue)
+enum { K10_LABEL = PEP_WS_UF_PARENT + 1, K10_EDGE_A, K10_EDGE_B, K10_SLOTS };
+static_assert(K10_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+
 }  // namespace
 
 // the body of pep_components and pep_components_of_hits: the edge columns are on the host
@@ -68,17 +72,17 @@ static int k10_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, cons
     if (n_nodes == 0) return PEP_OK;
     for (uint64_t e = 0; e < n_edges; ++e)
         if (h_a[e] >= n_nodes || h_b[e] >= n_nodes) return pep_fail(ctx, PEP_ERR_ARG, "pep_components: edge endpoint out of range");
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], (size_t)n_nodes * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[1], (size_t)n_nodes * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[2], (n_edges + 1) * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[3], (n_edges + 1) * 4));
-    uint32_t *parent = ctx->ws[0].as<uint32_t>(), *label = ctx->ws[1].as<uint32_t>();
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)n_nodes * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K10_LABEL], (size_t)n_nodes * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K10_EDGE_A], (n_edges + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K10_EDGE_B], (n_edges + 1) * 4));
+    uint32_t *parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>(), *label = ctx->ws[K10_LABEL].as<uint32_t>();
     hipLaunchKernelGGL(uf_init, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, n_nodes);
     if (n_edges) {
-        PEP_HIP(ctx, hipMemcpyAsync(ctx->ws[2].p, h_a, n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
-        PEP_HIP(ctx, hipMemcpyAsync(ctx->ws[3].p, h_b, n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(uf_union, dim3((unsigned)ceil_div(n_edges, 256)), dim3(256), 0, ctx->stream, parent, ctx->ws[2].as<const uint32_t>(),
-                           ctx->ws[3].as<const uint32_t>(), n_edges);
+        PEP_HIP(ctx, hipMemcpyAsync(ctx->ws[K10_EDGE_A].p, h_a, n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
+        PEP_HIP(ctx, hipMemcpyAsync(ctx->ws[K10_EDGE_B].p, h_b, n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(uf_union, dim3((unsigned)ceil_div(n_edges, 256)), dim3(256), 0, ctx->stream, parent, ctx->ws[K10_EDGE_A].as<const uint32_t>(),
+                           ctx->ws[K10_EDGE_B].as<const uint32_t>(), n_edges);
     }
     hipLaunchKernelGGL(uf_flatten, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, label, n_nodes);
     PEP_HIP(ctx, hipGetLastError());
@@ -94,7 +98,7 @@ static int k10_components(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_edges, cons
     return PEP_OK;
 }
 
-// K10 straight from the device copy of the newest search's hit table (d_hits: ws[23], still intact) - no edge columns built or uploaded.
+// K10 straight from the device copy of the newest search's hit table (d_hits: PEP_WS_HITS_OUT, still intact) - no edge columns built or uploaded.
 // The node map is uploaded only when it differs from the one the context already holds.
 int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, const pep_hit *d_hits, uint32_t q_base, const uint32_t *h_node_of_target,
                            uint64_t n_targets, uint32_t *h_label)
@@ -107,9 +111,9 @@ int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, cons
         PEP_TRY(dev_reserve(ctx, ctx->uf_nodes, (n_targets + 1) * 4));
         if (n_targets) PEP_HIP(ctx, hipMemcpyAsync(ctx->uf_nodes.p, ctx->uf_nodes_host.data(), n_targets * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], (size_t)n_nodes * 4));
-    PEP_TRY(dev_reserve(ctx, ctx->ws[1], (size_t)n_nodes * 4));
-    uint32_t *parent = ctx->ws[0].as<uint32_t>(), *label = ctx->ws[1].as<uint32_t>();
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)n_nodes * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[K10_LABEL], (size_t)n_nodes * 4));
+    uint32_t *parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>(), *label = ctx->ws[K10_LABEL].as<uint32_t>();
     hipLaunchKernelGGL(uf_init, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, n_nodes);
     if (n_hits) hipLaunchKernelGGL(uf_union_hits, dim3((unsigned)ceil_div(n_hits, 256)), dim3(256), 0, ctx->stream, parent, d_hits, n_hits, q_base, ctx->uf_nodes.as<const uint32_t>());
     hipLaunchKernelGGL(uf_flatten, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, label, n_nodes);
@@ -135,9 +139,9 @@ int pep_k10_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const ui
     if (n_nodes == 0) return PEP_OK;
     if (ctx->uf_nodes_host.size() < ctx->t.n) return pep_fail(ctx, PEP_ERR_STATE, "pep_set_grouping: fewer node entries than the search has targets");
     if ((uint64_t)ctx->q.n + ctx->grp_q_base > n_nodes) return pep_fail(ctx, PEP_ERR_STATE, "pep_set_grouping: query nodes beyond n_nodes");
-    PEP_TRY(dev_reserve(ctx, ctx->ws[0], (size_t)n_nodes * 4));
+    PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)n_nodes * 4));
     PEP_TRY(pin_reserve(ctx, ctx->pin_labels, (size_t)n_nodes * 4));
-    uint32_t *parent = ctx->ws[0].as<uint32_t>();
+    uint32_t *parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>();
     if (!(ctx->ext.pending && ctx->ext.parent_ready))          // (pack_out has initialised the parents on its way)
         hipLaunchKernelGGL(uf_init, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, n_nodes);
     if (n_hits) hipLaunchKernelGGL(uf_union_hits, dim3((unsigned)ceil_div(n_hits, 256)), dim3(256), 0, ctx->stream, parent, d_hits, n_hits, ctx->grp_q_base, ctx->uf_nodes.as<const uint32_t>(), d_n_hits);
