@@ -174,6 +174,25 @@ enum PepWsSlot {
     PEP_WS_COUNT
 };
 
+// The state areas of the kernels that look back (lookback.h): who begins a launch on the slot (pep_lookback_begin), the kernels that read it, the
+// value bits of its status words.  A slot serves one launch at a time; two users may share one only if their words have the same layout
+// and they begin one after the other on the context's stream.
+enum PepLookback {
+    PEP_LB_SCAN_U32 = 0,                    // scan_onepass<uint32_t> (pep_scan_u32): scan_lookback<uint32_t>; K1's layout_and_pack and reference side (translate.hip): k1_offsets,
+                                            // k1_ref_desc.  32 value bits.  Co-tenants: all three write 32-bit words and are begun one after another on the context's stream
+    PEP_LB_SCAN_U64,                        // scan_onepass<uint64_t> (pep_scan_u64): scan_lookback<uint64_t>; the traceback pass of pep_sw_run (sw.hip): sw_prep.  48 value bits.
+                                            // Co-tenants for the same reason
+    PEP_LB_SELECT_COUNT,                    // the alignment stage (trace.hip): select_gather, selected pairs in front of a tile.  32 value bits.  Its ticket numbers the tiles of both select slots
+    PEP_LB_SELECT_RUNS,                     // ... begun with it: select_gather, run capacity in front of a tile.  48 value bits
+    PEP_LB_TOPK_HITS,                       // the alignment stage: topk, kept hits in front of a tile.  32 value bits.  Its ticket numbers the tiles of both top-k slots
+    PEP_LB_TOPK_RUNS,                       // ... begun with it: topk, CIGAR runs of the kept in front of a tile.  48 value bits
+    PEP_LB_SORT,                            // sort_passes (once per pass) and pep_sort_u64_two_level (sort.hip): sort_onesweep, one word per (tile, digit).  32 value bits
+    PEP_LB_COUNT
+};
+
+// dirty: a failure may have left host and device ticket counts apart - the next launch on the slot starts from a cleared area (pep_fail)
+struct LookbackState { DevBuf buf; uint32_t epoch = 0, ticket_base = 0; bool dirty = false; };
+
 enum PepTimer { TM_SEED = 0, TM_TOTAL, TM_SW, TM_SW_TRACE, TM_TRACE, TM_MATCH0, TM_MATCH1, TM_MATCH2, TM_MATCH3, TM_COUNT };
 
 struct pep_ctx {
@@ -263,12 +282,8 @@ struct pep_ctx {
     int timing_level = 0;                    // pep_set_timing: 0 no phase timers, 1 the score pass only, 2 all of them
     PinBuf pin_labels;                       // grow-only: K10's labels on their way to the caller
     uint64_t trace_swept = 0;               // pairs the last traceback pass swept (the rest were settled by the gapless shortcut)
-    struct ScanState { DevBuf buf; uint32_t epoch = 0, ticket_base = 0; bool dirty = false; };     // dirty: a failure may have left host and device ticket counts apart - next use starts from a cleared area (pep_fail)
-    ScanState fused_state[4];               // kernels that scan while they compute (lookback.h): select (count, run capacity), top-k (hits, CIGAR runs)
-    ScanState scan_state[2];                // single-launch scans (u32, u64): ticket counter + one status word per tile (scan.hip)
-    DevBuf sort_state, sort_hist;           // one-launch-per-pass radix sort (sort.hip): ticket + status words per (tile, digit); its own histograms
-    uint32_t sort_epoch = 0, sort_ticket_base = 0;
-    bool sort_dirty = false;
+    LookbackState lookback[PEP_LB_COUNT];   // the state of every kernel that looks back (lookback.h; the slots: PepLookback above)
+    DevBuf sort_hist;                       // the radix sort's own digit histograms, for callers that bring none (sort.hip)
     DevBuf d_set;                           // candidate hash set of the seed stage (seeds.hip); set_compact leaves every slot it read EMPTY again
     uint64_t set_clean_slots = 0;           // leading slots of d_set known to be EMPTY (0 while a search is using it)
     DevBuf uf_nodes;                        // K10 over a device-resident hit table: node of every target (uploaded when it changes)

@@ -9,6 +9,7 @@
 // copy) with digits of at most 11 bits - the candidate keys of a search are 35-40 bits wide: four passes of 9-10 bits.
 // Optionally the last pass rewrites the keys on their way out (KeyUnpack: the dense candidate form -> q:21 | t:25 | bin:18).
 #include "common.h"
+#include "lookback.h"
 
 namespace {
 
@@ -18,9 +19,19 @@ constexpr int STILE = ST * SI;
 constexpr int MAX_DIGIT_BITS = 11;
 constexpr int MAX_PASSES = 8;
 
-// status word: epoch << 34 | flag << 32 | value (flag 1 = the tile's own count, 2 = count of this digit up to and including the tile).
-// The epoch is a per-pass number: words left by earlier passes never match, so nothing is cleared between them.
-constexpr uint64_t F_SUM = 1, F_PREFIX = 2;
+// status words (lookback.h): 32 value bits - the tile's own count of a digit, then the count of that digit up to and including the tile.
+// Every pass is a launch with an epoch of its own: words left by earlier passes never match, so nothing is cleared between them.
+constexpr int SORT_VB = 32;
+
+constexpr pep_key_unpack NO_UNPACK = {};          // keys leave the sort as they came
+
+// the dense candidate form -> q:21 | t:25 | bin:18 (KeyUnpack), on a key's way out of the sort
+__device__ __forceinline__ uint64_t unpack_key(uint64_t v, const pep_key_unpack &u)
+{
+    if (!u.on) return v;
+    const uint64_t q = v >> (u.tb + u.bb), t = (v >> u.bb) & ((1ull << u.tb) - 1), bin = (v & ((1ull << u.bb) - 1)) + u.bin_min;
+    return (q << 43) | (t << 18) | bin;
+}
 
 struct HistArgs { int shift[MAX_PASSES]; int passes; };
 
@@ -78,20 +89,12 @@ __global__ __launch_bounds__(256) void sort_buckets(const uint64_t *__restrict__
             }
             __syncthreads();
         }
-    for (uint32_t x = threadIdx.x; x < cnt; x += 256) {
-        uint64_t v = k[x];
-        if (unpack.on) {
-            const uint64_t q = v >> (unpack.tb + unpack.bb), t = (v >> unpack.bb) & ((1ull << unpack.tb) - 1), bin = (v & ((1ull << unpack.bb) - 1)) + unpack.bin_min;
-            v = (q << 43) | (t << 18) | bin;
-        }
-        out[start + x] = v;
-    }
+    for (uint32_t x = threadIdx.x; x < cnt; x += 256) out[start + x] = unpack_key(k[x], unpack);
 }
 
 template <int DB>
 __global__ __launch_bounds__(ST) void sort_onesweep(const uint64_t *__restrict__ keys, uint64_t *__restrict__ out, const uint32_t *__restrict__ n_ptr, uint64_t n_host,
-                                                    int shift, const uint32_t *__restrict__ hist /* [R] of this pass */, uint64_t *__restrict__ state,
-                                                    uint32_t ticket_base, uint64_t epoch, pep_key_unpack unpack)
+                                                    int shift, const uint32_t *__restrict__ hist /* [R] of this pass */, LbLaunch lb, pep_key_unpack unpack)
 {
     constexpr uint32_t R = 1u << DB;
     __shared__ __attribute__((aligned(16))) uint8_t wave_cnt[ST / 64][R];       // keys of one digit in one wavefront's row: at most 64
@@ -101,12 +104,10 @@ __global__ __launch_bounds__(ST) void sort_onesweep(const uint64_t *__restrict__
     const uint64_t n = n_ptr ? (uint64_t)*n_ptr : n_host;
     const uint32_t nb = (uint32_t)((n + STILE - 1) / STILE);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_tile = atomicAdd(reinterpret_cast<uint32_t *>(state), 1u) - ticket_base;
-    for (uint32_t d = threadIdx.x; d < R; d += ST) local[d] = 0;
-    __syncthreads();
-    const uint32_t tile = s_tile;
+    for (uint32_t d = threadIdx.x; d < R; d += ST) local[d] = 0;           // (in front of the ticket: its barrier covers this too)
+    const uint32_t tile = lb_take_tile(lb.state, lb.ticket_base, &s_tile);
     if (tile >= nb) return;                              // surplus blocks of a grid sized from an upper bound (block-uniform)
-    uint64_t *status = state + 1;
+    uint64_t *status = lb.status();                      // [tile][digit]
     const uint64_t base = (uint64_t)tile * STILE;
     uint64_t key[SI];
 #pragma unroll
@@ -134,20 +135,19 @@ __global__ __launch_bounds__(ST) void sort_onesweep(const uint64_t *__restrict__
         for (int k = 0; k < PER; ++k) { const uint32_t d = threadIdx.x * PER + k; if (d < R) digit_base[d] = run; run += own[k]; }
         __syncthreads();
     }
-    // look-back per digit: thread t follows digits t, t + 256, ... (coalesced status rows)
+    // look-back per digit: thread t follows digits t, t + 1024, ... (coalesced status rows), tile by tile - a walk of its own over the words of lookback.h
     for (uint32_t d = threadIdx.x; d < R; d += ST) {
         const uint32_t mine = local[d];
         uint32_t before = 0;
         if (tile > 0) {
-            __hip_atomic_store(&status[(uint64_t)tile * R + d], (epoch << 34) | (F_SUM << 32) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            lb_publish(&status[(uint64_t)tile * R + d], lb_word<SORT_VB, LB_SUM>(lb.epoch, mine));
             for (int64_t t = (int64_t)tile - 1; t >= 0; --t) {
-                uint64_t w;
-                do { w = __hip_atomic_load(&status[(uint64_t)t * R + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((w >> 34) != epoch);
-                before += (uint32_t)w;
-                if (((w >> 32) & 3u) == F_PREFIX) break;
+                const uint64_t w = lb_wait<SORT_VB>(&status[(uint64_t)t * R + d], lb.epoch);
+                before += (uint32_t)lb_value<SORT_VB>(w);
+                if (lb_is_prefix<SORT_VB>(w)) break;
             }
         }
-        __hip_atomic_store(&status[(uint64_t)tile * R + d], (epoch << 34) | (F_PREFIX << 32) | (before + mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lb_publish(&status[(uint64_t)tile * R + d], lb_word<SORT_VB, LB_PREFIX>(lb.epoch, before + mine));
         digit_base[d] += before;
     }
     __syncthreads();
@@ -173,12 +173,7 @@ __global__ __launch_bounds__(ST) void sort_onesweep(const uint64_t *__restrict__
         if (valid) {
             uint32_t o = digit_base[d] + rank;
             for (int w = 0; w < wave; ++w) o += wave_cnt[w][d];
-            uint64_t v = k;
-            if (unpack.on) {
-                const uint64_t q = v >> (unpack.tb + unpack.bb), t = (v >> unpack.bb) & ((1ull << unpack.tb) - 1), bin = (v & ((1ull << unpack.bb) - 1)) + unpack.bin_min;
-                v = (q << 43) | (t << 18) | bin;
-            }
-            out[o] = v;
+            out[o] = unpack_key(k, unpack);
         }
         __syncthreads();
         for (uint32_t dd = threadIdx.x; dd < R; dd += ST) {
@@ -197,10 +192,6 @@ int sort_passes(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, const uint32_t 
 {
     constexpr uint32_t R = 1u << DB;
     const uint32_t nb = (uint32_t)ceil_div(n_bound, STILE);
-    DevBuf &S = ctx->sort_state;
-    const size_t need = ((size_t)nb * R + 2) * sizeof(uint64_t);
-    bool clear = false;
-    if (need > S.cap) { PEP_TRY(dev_reserve(ctx, S, need)); clear = true; }
     DevBuf &H = ctx->sort_hist;
     uint32_t *hist = d_hist_zeroed;
     if (!hist) {
@@ -213,22 +204,12 @@ int sort_passes(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, const uint32_t 
     for (int p = 0; p < passes; ++p) ha.shift[ha.passes++] = p * DB;        // (a pass beyond the key width sees digit 0 everywhere: a stable copy)
     hipLaunchKernelGGL(sort_hist_all<DB>, dim3(std::min<uint32_t>(nb, 1024u)), dim3(ST), (size_t)ha.passes * R * 4, ctx->stream, (const uint64_t *)d_keys, d_n, n_bound, hist, ha);
     uint64_t *src = d_keys, *dst = d_tmp;
-    int real = 0;
-    pep_key_unpack none;
-    none.on = 0; none.tb = none.bb = 0; none.bin_min = 0;
     for (int p = 0; p < passes; ++p) {
-        const int shift = p * DB;
         const bool last = p == passes - 1;
-        {
-            if (ctx->sort_dirty) { clear = true; ctx->sort_dirty = false; }
-            ctx->sort_epoch = (ctx->sort_epoch + 1) & ((1u << 29) - 1);
-            if (ctx->sort_epoch == 0) { clear = true; ctx->sort_epoch = 1; }          // wrapped: forget every old word
-            if (clear) { PEP_HIP(ctx, hipMemsetAsync(S.p, 0, S.cap, ctx->stream)); ctx->sort_ticket_base = 0; clear = false; }
-            hipLaunchKernelGGL(sort_onesweep<DB>, dim3(nb), dim3(ST), 0, ctx->stream, (const uint64_t *)src, dst, d_n, n_bound, shift, (const uint32_t *)(hist + (size_t)real * R),
-                               S.as<uint64_t>(), ctx->sort_ticket_base, (uint64_t)ctx->sort_epoch, (last && unpack) ? *unpack : none);
-            ctx->sort_ticket_base += nb;
-            ++real;
-        }
+        LbLaunch lb;
+        PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SORT, nb, R, SORT_VB, &lb));
+        hipLaunchKernelGGL(sort_onesweep<DB>, dim3(nb), dim3(ST), 0, ctx->stream, (const uint64_t *)src, dst, d_n, n_bound, p * DB, (const uint32_t *)(hist + (size_t)p * R), lb,
+                           (last && unpack) ? *unpack : NO_UNPACK);
         uint64_t *t = src; src = dst; dst = t;
     }
     PEP_HIP(ctx, hipGetLastError());
@@ -268,20 +249,10 @@ int pep_sort_u64_two_level(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint
     constexpr int DB = PEP_SORT_TOP_BITS;
     constexpr uint32_t R = 1u << DB;
     const uint32_t nb = (uint32_t)ceil_div(n, STILE);
-    DevBuf &S = ctx->sort_state;
-    const size_t need = ((size_t)nb * R + 2) * sizeof(uint64_t);
-    bool clear = false;
-    if (need > S.cap) { PEP_TRY(dev_reserve(ctx, S, need)); clear = true; }
-    if (ctx->sort_dirty) { clear = true; ctx->sort_dirty = false; }
-    ctx->sort_epoch = (ctx->sort_epoch + 1) & ((1u << 29) - 1);
-    if (ctx->sort_epoch == 0) { clear = true; ctx->sort_epoch = 1; }
-    if (clear) { PEP_HIP(ctx, hipMemsetAsync(S.p, 0, S.cap, ctx->stream)); ctx->sort_ticket_base = 0; }
-    pep_key_unpack none;
-    none.on = 0; none.tb = none.bb = 0; none.bin_min = 0;
-    hipLaunchKernelGGL(sort_onesweep<DB>, dim3(nb), dim3(ST), 0, ctx->stream, (const uint64_t *)d_keys, d_tmp, (const uint32_t *)nullptr, n, bits - DB, d_top_hist,
-                       S.as<uint64_t>(), ctx->sort_ticket_base, (uint64_t)ctx->sort_epoch, none);
-    ctx->sort_ticket_base += nb;
-    hipLaunchKernelGGL(sort_buckets, dim3(R), dim3(256), 0, ctx->stream, (const uint64_t *)d_tmp, d_keys, d_top_hist, unpack ? *unpack : none);
+    LbLaunch lb;
+    PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SORT, nb, R, SORT_VB, &lb));
+    hipLaunchKernelGGL(sort_onesweep<DB>, dim3(nb), dim3(ST), 0, ctx->stream, (const uint64_t *)d_keys, d_tmp, (const uint32_t *)nullptr, n, bits - DB, d_top_hist, lb, NO_UNPACK);
+    hipLaunchKernelGGL(sort_buckets, dim3(R), dim3(256), 0, ctx->stream, (const uint64_t *)d_tmp, d_keys, d_top_hist, unpack ? *unpack : NO_UNPACK);
     PEP_HIP(ctx, hipGetLastError());
     return PEP_OK;
 }

@@ -806,14 +806,14 @@ __global__ __launch_bounds__(256) void sw_prep(const uint64_t *__restrict__ cand
                                                const int32_t *__restrict__ skip_mode,                  // candidates settled without a sweep (mode -2: gapless_check, identical_check) take no part
                                                int count_skipped,                                      // score pass: their cells still count in [0] (and, with their number, in [6] [7])
                                                uint64_t *__restrict__ dir_off,                         // traceback pass: start of every candidate's traceback codes (in 16-step blocks) = exclusive
-                                               uint64_t *__restrict__ lb_state, uint32_t lb_ticket_base, uint64_t lb_epoch)      //   scan of the block counts, taken in here (lookback.h)
+                                               LbLaunch lb)                                            //   scan of the block counts, taken in here (lookback.h); lb.state null: no scan
 {
     __shared__ uint32_t lh[LEN_BUCKETS];
     __shared__ uint32_t s_tile;
     for (int x = threadIdx.x; x < LEN_BUCKETS; x += 256) lh[x] = 0;
     __syncthreads();
     const uint64_t n = d_n ? (uint64_t)*d_n : n_host;          // (the grid is sized from n_host, an upper bound, when the count lives on the device)
-    const uint32_t tile = lb_state ? lb_take_tile(lb_state, lb_ticket_base, &s_tile) : blockIdx.x;
+    const uint32_t tile = lb.state ? lb_take_tile(lb.state, lb.ticket_base, &s_tile) : blockIdx.x;
     const uint64_t c = (uint64_t)tile * 256 + threadIdx.x;
     unsigned long long cells = 0, blocks = 0, cells_skipped = 0, n_skipped = 0;
     bool is_long = false;
@@ -853,12 +853,12 @@ __global__ __launch_bounds__(256) void sw_prep(const uint64_t *__restrict__ cand
             atomicAdd(&lh[len_bucket(nb)], 1u);
         }
     }
-    if (lb_state) {
+    if (lb.state) {
         __shared__ uint64_t lds64[4], s_pre;
         uint64_t tot;
         const uint64_t ex = block_excl_scan_256<uint64_t>(blocks, &tot, lds64);
         if (threadIdx.x < 64) {
-            const uint64_t p = lb_tile_prefix<48>(lb_state + 1, tile, tot, lb_epoch, (int)threadIdx.x);
+            const uint64_t p = lb_tile_prefix<48>(lb.status(), tile, tot, lb.epoch, (int)threadIdx.x);
             if (threadIdx.x == 0) s_pre = p;
         }
         __syncthreads();
@@ -989,10 +989,9 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
     unsigned long long *cells = reinterpret_cast<unsigned long long *>(zb);
     if (d_hdr) *d_hdr = cells;
     uint32_t *len_hist = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(zb) + 64), *cursor = len_hist + LEN_BUCKETS, *order = ctx->ws[PEP_WS_SW_ORDER].as<uint32_t>();
-    uint64_t *lb_state = nullptr, lb_epoch = 0;
-    uint32_t lb_ticket = 0;
+    LbLaunch lb = {nullptr, 0, 0};
     const uint64_t prep_tiles = ceil_div(n + (trace ? 1 : 0), 256);        // (the traceback pass writes one entry more: the total)
-    if (trace) PEP_TRY(pep_lookback_begin(ctx, ctx->scan_state[1], prep_tiles, (1u << 14) - 1, &lb_state, &lb_ticket, &lb_epoch));
+    if (trace) PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SCAN_U64, prep_tiles, 1, 48, &lb));
     // score pass: identical pairs are settled without a sweep (identical_check; params.reserved2 bit 1 switches it off, bit 2 on whatever the
     // size - tests).  Not below 16 k candidates: a pass that small is one or two rounds of wavefronts, a fifth fewer of them does not shorten it,
     // and the check is a launch and a chain of loads of its own (8x1 cell of the benchmark, 6 163 candidates: 0.965 -> 1.0 ms with it)
@@ -1018,7 +1017,7 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
     }
     hipLaunchKernelGGL(sw_prep, dim3((unsigned)prep_tiles), dim3(256), 0, ctx->stream, d_cands, n, trace ? d_n : nullptr, ctx->q.len.as<const uint32_t>(),
                        ctx->t.len.as<const uint32_t>(), ctx->ws[PEP_WS_SW_NBLK].as<uint32_t>(), ctx->ws[PEP_WS_SW_SCAN_IN].as<uint64_t>(), cells, len_hist, nb_limit, skip, trace ? 0 : 1,
-                       ctx->ws[PEP_WS_SW_DIR_OFF].as<uint64_t>(), lb_state, lb_ticket, lb_epoch);
+                       ctx->ws[PEP_WS_SW_DIR_OFF].as<uint64_t>(), lb);
     hipLaunchKernelGGL(sw_order, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream, ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>(), n, trace ? d_n : nullptr,
                        (const uint32_t *)len_hist, cursor, order, skip);
     if (trace) {

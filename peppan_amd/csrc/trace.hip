@@ -26,7 +26,15 @@ __device__ __forceinline__ int key_dlo(uint64_t k) { return (int)(k & ((1u << 18
 // values at once - selected pairs (their slot in the arrays of the selected) and their run capacity (the slot of their CIGAR runs) - finds
 // the totals of the tiles in front of it by look-back and writes the selected pairs' records straight to their slots.  Four launches of a
 // dependent chain before (about 5 us each for 50 k candidates).
-struct SelectState { uint64_t *count_state, *run_state; uint32_t ticket_base; uint64_t epoch_count, epoch_run; };
+// The two look-backs of such a kernel.  The tile number comes from the ticket of `count` alone and indexes the status words of both areas:
+// the two are always begun together, for the same number of tiles (begin_select), so tile t of this launch owns word t of either, and the
+// ticket counter of `runs` (and with it runs.ticket_base) is never read by anyone.
+struct SelectState { LbLaunch count, runs; };
+int begin_select(pep_ctx *ctx, PepLookback count_slot, PepLookback runs_slot, uint64_t tiles, SelectState *s)
+{
+    PEP_TRY(pep_lookback_begin(ctx, count_slot, tiles, 1, 32, &s->count));
+    return pep_lookback_begin(ctx, runs_slot, tiles, 1, 48, &s->runs);
+}
 __global__ __launch_bounds__(256) void select_gather(const uint64_t *__restrict__ cands, uint64_t n, const int4 *__restrict__ sw, const int32_t *__restrict__ min_score,
                                                      int hsp_mode, const uint32_t *__restrict__ q_len, const uint32_t *__restrict__ t_len, SelInfo *__restrict__ sel,
                                                      uint64_t *__restrict__ run_off, uint64_t *__restrict__ sel_keys, int32_t *__restrict__ known, int32_t *__restrict__ end_lane,
@@ -35,7 +43,7 @@ __global__ __launch_bounds__(256) void select_gather(const uint64_t *__restrict_
 {
     __shared__ uint32_t s_tile, lds32[4];
     __shared__ uint64_t lds64[4], s_pre[2];
-    const uint32_t tile = lb_take_tile(st.count_state, st.ticket_base, &s_tile);
+    const uint32_t tile = lb_take_tile(st.count.state, st.count.ticket_base, &s_tile);
     const uint64_t c = (uint64_t)tile * 256 + threadIdx.x;
     const bool live = c < n;
     const uint64_t g = live ? cands[c] >> 18 : 0;
@@ -63,8 +71,8 @@ __global__ __launch_bounds__(256) void select_gather(const uint64_t *__restrict_
     const uint32_t ex_f = block_excl_scan_256<uint32_t>(f, &tot_f, lds32);
     const uint64_t ex_cap = block_excl_scan_256<uint64_t>(cap, &tot_cap, lds64);
     if (threadIdx.x < 64) {
-        const uint64_t p0 = lb_tile_prefix<32>(st.count_state + 1, tile, tot_f, st.epoch_count, (int)threadIdx.x);
-        const uint64_t p1 = lb_tile_prefix<48>(st.run_state + 1, tile, tot_cap, st.epoch_run, (int)threadIdx.x);
+        const uint64_t p0 = lb_tile_prefix<32>(st.count.status(), tile, tot_f, st.count.epoch, (int)threadIdx.x);
+        const uint64_t p1 = lb_tile_prefix<48>(st.runs.status(), tile, tot_cap, st.runs.epoch, (int)threadIdx.x);
         if (threadIdx.x == 0) { s_pre[0] = p0; s_pre[1] = p1; }
     }
     __syncthreads();
@@ -432,7 +440,7 @@ __global__ __launch_bounds__(256) void topk(const uint32_t *__restrict__ d_n_sel
     // the tile scans (kept, runs of the kept) and finds the totals in front of it by look-back (lookback.h)
     __shared__ uint32_t s_tile, lds32[4];
     __shared__ uint64_t lds64[4], s_pre[2];
-    const uint32_t tile = lb_take_tile(st.count_state, st.ticket_base, &s_tile);
+    const uint32_t tile = lb_take_tile(st.count.state, st.count.ticket_base, &s_tile);
     const uint64_t n_sel = *d_n_sel;
     const uint64_t s = (uint64_t)tile * 256 + threadIdx.x;
     if (s == 0) {
@@ -495,8 +503,8 @@ __global__ __launch_bounds__(256) void topk(const uint32_t *__restrict__ d_n_sel
     const uint32_t ex_k = block_excl_scan_256<uint32_t>(keep, &tot_k, lds32);
     const uint64_t ex_r = block_excl_scan_256<uint64_t>(n_runs, &tot_r, lds64);
     if (threadIdx.x < 64) {
-        const uint64_t p0 = lb_tile_prefix<32>(st.count_state + 1, tile, tot_k, st.epoch_count, (int)threadIdx.x);
-        const uint64_t p1 = lb_tile_prefix<48>(st.run_state + 1, tile, tot_r, st.epoch_run, (int)threadIdx.x);
+        const uint64_t p0 = lb_tile_prefix<32>(st.count.status(), tile, tot_k, st.count.epoch, (int)threadIdx.x);
+        const uint64_t p1 = lb_tile_prefix<48>(st.runs.status(), tile, tot_r, st.runs.epoch, (int)threadIdx.x);
         if (threadIdx.x == 0) { s_pre[0] = p0; s_pre[1] = p1; }
     }
     __syncthreads();
@@ -687,11 +695,7 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
     uint64_t *run_off = ctx->ws[PEP_WS_SEL_RUNS_KEYS].as<uint64_t>(), *sel_keys = run_off + n + 2;
     {
         SelectState ss;
-        uint64_t ep = 0;
-        uint32_t tb2 = 0;
-        PEP_TRY(pep_lookback_begin(ctx, ctx->fused_state[0], gb, (1u << 30) - 1, &ss.count_state, &ss.ticket_base, &ss.epoch_count));
-        PEP_TRY(pep_lookback_begin(ctx, ctx->fused_state[1], gb, (1u << 14) - 1, &ss.run_state, &tb2, &ep));
-        ss.epoch_run = ep;
+        PEP_TRY(begin_select(ctx, PEP_LB_SELECT_COUNT, PEP_LB_SELECT_RUNS, gb, &ss));
         hipLaunchKernelGGL(select_gather, dim3(gb), dim3(256), 0, st, d_cands, n, sw, dms.as<const int32_t>(), P.hsp_mode, ctx->q.len.as<const uint32_t>(),
                            ctx->t.len.as<const uint32_t>(), sel, run_off, sel_keys, known, end_lane, counters, mail + 3, ss);
     }
@@ -756,12 +760,8 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
         cig_pos = reinterpret_cast<uint64_t *>(hit_pos + n_b + 2);
         {
             SelectState ts;
-            uint64_t ep = 0;
-            uint32_t tb2 = 0;
             const uint64_t tiles = ceil_div(n_b, 256);
-            PEP_TRY(pep_lookback_begin(ctx, ctx->fused_state[2], tiles, (1u << 30) - 1, &ts.count_state, &ts.ticket_base, &ts.epoch_count));
-            PEP_TRY(pep_lookback_begin(ctx, ctx->fused_state[3], tiles, (1u << 14) - 1, &ts.run_state, &tb2, &ep));
-            ts.epoch_run = ep;
+            PEP_TRY(begin_select(ctx, PEP_LB_TOPK_HITS, PEP_LB_TOPK_RUNS, tiles, &ts));
             hipLaunchKernelGGL(topk, dim3((unsigned)tiles), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, P.top_k, P.n_splits,
                                (uint32_t)(P.t_index_base % P.n_splits), ctx->t_class_ready ? ctx->d_t_class.as<const uint32_t>() : (const uint32_t *)nullptr, keep_flag, hit_pos, cig_pos,
                                (const unsigned long long *)score_hdr, (const unsigned long long *)trace_hdr, mail, ts, t_subject);

@@ -552,16 +552,12 @@ __global__ void k1_query_desc(uint32_t n, const uint32_t *__restrict__ frame, co
     pin_len[i] = len[i];                     // the host's copy (pinned memory): the search derives its score thresholds from the lengths
 }
 
-// reference side: the chunks of (sequence, frame) w become packed sequences first[w] .. first[w] + cnt[w] - 1
-// look-back state of a K1 kernel that scans while it works (lookback.h)
-struct K1Scan { uint64_t *state; uint32_t ticket_base; uint64_t epoch; };
-
-// the chunks of (sequence, frame) w become packed sequences first[w] .. first[w] + cnt[w] - 1, first = exclusive scan of the chunk counts -
+// reference side: the chunks of (sequence, frame) w become packed sequences first[w] .. first[w] + cnt[w] - 1, first = exclusive scan of the chunk counts -
 // taken inside this kernel (tile totals by look-back) instead of by a scan launch in front of it; *n_targets = their number
 __global__ __launch_bounds__(256) void k1_ref_desc(uint64_t nw, int n_frames, const uint64_t *__restrict__ chunk_base, const uint32_t *__restrict__ chunk_cnt,
                                                    const uint32_t *__restrict__ chunk_off, const uint32_t *__restrict__ chunk_len,
                                                    PackDesc *__restrict__ desc, uint32_t *__restrict__ padded, uint32_t *__restrict__ len_out, K1Summary *__restrict__ sum,
-                                                   uint32_t *__restrict__ n_targets, K1Scan sc, const uint64_t *__restrict__ nt_off, K1Src *__restrict__ src_of,
+                                                   uint32_t *__restrict__ n_targets, LbLaunch sc, const uint64_t *__restrict__ nt_off, K1Src *__restrict__ src_of,
                                                    uint32_t *__restrict__ first_t, uint32_t *__restrict__ first_w, uint32_t fill_from)
 {
     __shared__ uint32_t s_tile, lds[4];
@@ -573,7 +569,7 @@ __global__ __launch_bounds__(256) void k1_ref_desc(uint64_t nw, int n_frames, co
     uint32_t tot;
     const uint32_t ex = block_excl_scan_256<uint32_t>(cnt, &tot, lds);
     if (threadIdx.x < 64) {
-        const uint64_t p = lb_tile_prefix<32>(sc.state + 1, tile, tot, sc.epoch, (int)threadIdx.x);
+        const uint64_t p = lb_tile_prefix<32>(sc.status(), tile, tot, sc.epoch, (int)threadIdx.x);
         if (threadIdx.x == 0) s_pre = p;
     }
     __syncthreads();
@@ -617,7 +613,7 @@ __global__ __launch_bounds__(256) void k1_ref_desc_fill(const K1Seg *__restrict_
 // the last sequence count as empty); entries n .. cap hold the layout's total size (sentinel of the owner search).
 // Also the set's summary: number of sequences, layout size, residues, longest sequence.
 __global__ __launch_bounds__(256) void k1_offsets(const uint32_t *__restrict__ n_ptr, const uint32_t *__restrict__ padded, uint32_t cap, uint32_t *__restrict__ pk_off,
-                                                  const uint32_t *__restrict__ len, K1Summary *__restrict__ sum, K1Scan sc)
+                                                  const uint32_t *__restrict__ len, K1Summary *__restrict__ sum, LbLaunch sc)
 {
     __shared__ uint32_t s_tile, lds[4];
     __shared__ uint64_t s_pre;
@@ -630,7 +626,7 @@ __global__ __launch_bounds__(256) void k1_offsets(const uint32_t *__restrict__ n
     uint32_t tot;
     const uint32_t ex = block_excl_scan_256<uint32_t>(pad, &tot, lds);
     if (threadIdx.x < 64) {
-        const uint64_t p = lb_tile_prefix<32>(sc.state + 1, tile, tot, sc.epoch, (int)threadIdx.x);
+        const uint64_t p = lb_tile_prefix<32>(sc.status(), tile, tot, sc.epoch, (int)threadIdx.x);
         if (threadIdx.x == 0) s_pre = p;
     }
     __syncthreads();
@@ -666,9 +662,9 @@ int layout_and_pack(pep_ctx *ctx, const NtSet &nt, int tab, const PackDesc *d_de
 {
     (void)d_scan; (void)tmp;
     K1Summary *d_sum = reinterpret_cast<K1Summary *>(const_cast<PackDesc *>(d_desc) + cap);        // behind the descriptors
-    K1Scan sc;
+    LbLaunch sc;
     const uint64_t tiles = ceil_div((uint64_t)cap + 1, 256);
-    PEP_TRY(pep_lookback_begin(ctx, ctx->scan_state[0], tiles, (1u << 30) - 1, &sc.state, &sc.ticket_base, &sc.epoch));
+    PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SCAN_U32, tiles, 1, 32, &sc));
     hipLaunchKernelGGL(k1_offsets, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, d_n, d_padded, cap, out.off.as<uint32_t>(), out.len.as<const uint32_t>(), d_sum, sc);
     hipLaunchKernelGGL(k1_pack, dim3((unsigned)ceil_div((uint64_t)cap + 1, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), (const K1Src *)k1_src_of(d_desc, cap), tab,
                        d_desc, out.off.as<const uint32_t>(), d_n, cap, out.res.as<uint8_t>(), out.blk2seq.as<uint2>(), (const K1Summary *)d_sum, pin_sum);
@@ -897,9 +893,9 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
                                ctx->d_k1_spec.as<const unsigned long long>(), d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>());
         }
         {
-            K1Scan sc;
+            LbLaunch sc;
             const uint64_t tiles = ceil_div(nw, 256);
-            PEP_TRY(pep_lookback_begin(ctx, ctx->scan_state[0], tiles, (1u << 30) - 1, &sc.state, &sc.ticket_base, &sc.epoch));
+            PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SCAN_U32, tiles, 1, 32, &sc));
             hipLaunchKernelGGL(k1_ref_desc, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nw, nf, d_base, W[K1R_CHUNK_CNT].as<const uint32_t>(),
                                W[K1R_CHUNK_OFF].as<const uint32_t>(), W[K1R_CHUNK_LEN].as<const uint32_t>(), D.as<PackDesc>(), W[K1R_PADDED].as<uint32_t>(),
                                ctx->t.len.as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + slots), W[K1R_FIRST].as<uint32_t>() + nw, sc,

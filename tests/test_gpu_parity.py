@@ -1522,6 +1522,45 @@ def test_many_searches_on_one_context(ctx):
     assert h.tobytes() == h0.tobytes() and c.tobytes() == c0.tobytes()
 
 
+def test_failed_call_leaves_nothing_behind_in_any_lookback_slot(ctx):
+    """a call that fails marks the state area of every kernel that looks back - the scans, the selection and top-k kernels, the sort - to be
+    cleared before its next use (pep_fail).  A search refused for its parameters (n_shapes = 0: an argument error, nothing is queued) does
+    that to all of them at once; what runs next - a search through either sort path, linclust, the u64 scan of overlaps - gives what it
+    gave before, byte for byte"""
+    from peppan_amd import _native as N, synth
+    prots = synth.make_proteins(48, length=(60, 200), seed=21, family=4, sub=0.2)
+    p = N.default_params(0., 0., 10, 5)
+    refused = N.default_params(0., 0., 10, 5)
+    refused.n_shapes = 0
+
+    def refuse():
+        with pytest.raises(N.PepError):
+            ctx.search(refused)
+    ctx.set_query_aa(prots); ctx.set_ref_aa(prots)
+    h0, c0, st0 = ctx.search(p)
+    assert len(h0) > 40
+    refuse()
+    for forced in (0, 1):
+        p.reserved[2] = forced
+        h, c, st = ctx.search(p)
+        assert h.tobytes() == h0.tobytes() and c.tobytes() == c0.tobytes(), forced
+    letters = np.full(26, 20, dtype=np.uint8)                       # residue codes (letter - 'A') -> linclust's alphabet
+    letters[np.frombuffer(b'ACDEFGHIKLMNPQRSTVWY', dtype=np.uint8) - 65] = np.arange(20, dtype=np.uint8)
+    seqs = [letters[x] for x in prots]
+    rep0, lst0 = ctx.linclust(seqs, 0.5, 0.5, base=20, k=5, m=20)
+    assert len(set(rep0.tolist())) < len(seqs)
+    refuse()
+    rep1, lst1 = ctx.linclust(seqs, 0.5, 0.5, base=20, k=5, m=20)
+    assert rep1.tobytes() == rep0.tobytes() and lst1 == lst0
+    n = 300                                                         # every row overlaps the two behind it
+    contig, start, rid = np.zeros(n, dtype=np.int32), 10 * np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64)[::-1].copy()
+    o0 = ctx.overlaps(contig, start, start + 25, rid, 300., 0.)
+    assert len(o0) == 2 * n - 3
+    refuse()
+    o1 = ctx.overlaps(contig, start, start + 25, rid, 300., 0.)
+    assert o1.tobytes() == o0.tobytes()
+
+
 def test_searches_in_flight_together_on_contexts_of_their_own(ctx):
     """two host threads, a context (stream, work space, counters) each, searching different sets at the same time: every result equals the one the
     context produces alone - nothing of a search lives outside its context (what bench.py's `two_searches_in_flight` and a caller with
@@ -1669,6 +1708,38 @@ def test_candidate_sort_two_level_and_fallback(ctx):
         _cmp_hits(np.frombuffer(out[0][0], dtype=N.HIT_DTYPE), np.frombuffer(out[0][1], dtype=np.uint32), oh, oc)
         assert out[0][2] == ost['candidates']
     assert ost['candidates'] < 4096
+
+
+def test_candidate_sort_both_paths_over_two_tiles(ctx):
+    """both sort paths with a look-back chain: a tile of the sort's passes is 8 192 keys, so only a search with more candidates than that
+    has a tile that waits for the digit counts of the tile in front of it.  350 mutants of each of 24 proteins: 8 424 candidates (one
+    band per pair; the oracle's count, taken on the CPU when the case was sized), the second tile 232 keys long, and no bucket of the top
+    ten key bits (a query and 512 neighbouring targets) above 4 096, so that the two-level sort runs unless params.reserved[2] forces the
+    four LSD passes.  Both tables equal each other and the oracle's"""
+    from peppan_amd import _native as N, synth
+    from oracle import oracle as O
+    rng = np.random.default_rng(12)
+    base = synth.make_proteins(24, length=(150, 260), seed=31, family=1, sub=0.)
+    crowd = []
+    for b in base:
+        for k in range(350):
+            p = b.copy()
+            idx = rng.integers(0, len(p), 6)
+            p[idx] = rng.integers(0, 20, 6).astype(np.uint8)
+            crowd.append(p)
+    qs, ts = base, crowd + base
+    ctx.set_query_aa(qs); ctx.set_ref_aa(ts)
+    out = []
+    for forced in (0, 1):
+        p = N.default_params(30., 10., 50, 5)
+        p.reserved[2] = forced
+        h, c, st = ctx.search(p)
+        assert st['candidates'] > 8192
+        out.append((h.tobytes(), c.tobytes(), st['candidates'], st['pairs'], st['tracebacks']))
+    assert out[0] == out[1]
+    oh, oc, ost = O.search(qs, ts, O.default_params(30., 10., 50, 5))
+    _cmp_hits(np.frombuffer(out[0][0], dtype=N.HIT_DTYPE), np.frombuffer(out[0][1], dtype=np.uint32), oh, oc)
+    assert out[0][2] == ost['candidates']
 
 
 def test_identical_pairs_settled_without_a_sweep(ctx):
