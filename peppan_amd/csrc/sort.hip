@@ -223,7 +223,7 @@ int sort_passes(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, const uint32_t 
 // d_hist_zeroed: MAX_PASSES x 2^11 zeroed u32 words the caller provides (nullptr: the sort clears its own).
 int pep_sort_u64(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, const uint32_t *d_n, uint64_t n_bound, int bits, uint32_t *d_hist_zeroed, const pep_key_unpack *unpack)
 {
-    if (n_bound < 2 && !d_n) return PEP_OK;
+    if (n_bound < 2 && !d_n && !(unpack && unpack->on)) return PEP_OK;      // (a single key is sorted, but it still has to leave in the unpacked form)
     if (n_bound == 0) return PEP_OK;
     if (n_bound >= (1ull << 30)) return pep_fail(ctx, PEP_ERR_LIMIT, "pep_sort_u64: more than 2^30 keys");
     bits = std::max(1, std::min(64, bits));
