@@ -1,5 +1,6 @@
 // C ABI of libpeppan_hip.so (declared in include/peppan_hip.h): context, inputs, search, results, pep_merge_hits.  The entry points of a kernel are in the kernel's file.
 #include "common.h"
+#include "setstate.h"
 #include <chrono>
 #include <time.h>
 #include <algorithm>
@@ -361,12 +362,12 @@ int upload_nt(pep_ctx *ctx, NtSet &s, const uint8_t *nt, const uint64_t *off, ui
     return PEP_OK;
 }
 
-int upload_aa(pep_ctx *ctx, SeqSet &s, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n)
+int upload_aa(pep_ctx *ctx, PepSide side, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n)
 {
     if (n && (!codes || !off)) return pep_fail(ctx, PEP_ERR_ARG, "null sequence buffer");
     if (n > max_n) return pep_fail(ctx, PEP_ERR_LIMIT, "too many sequences");
-    if (&s == &ctx->t) ctx->t_tables_lazy = false;          // the host tables are built right here
-    if (&s == &ctx->q) ctx->q_tables_lazy = false;
+    SeqSet &s = pep_set_of(ctx, side);
+    side_tables_built(ctx, side);                            // the host tables are built right here
     s.n = n;
     s.h_off.assign(n + 1, 0);
     s.h_len.assign(n, 0);
@@ -401,10 +402,20 @@ int upload_aa(pep_ctx *ctx, SeqSet &s, const uint8_t *codes, const uint64_t *off
     return pep_upload_blk2seq(ctx, s);
 }
 
-int download_aa(pep_ctx *ctx, const SeqSet &s, uint8_t *codes, uint64_t cap, uint64_t *off)
+// PEP_ERR_STATE unless a side's packed set is complete on the device
+int readable(pep_ctx *ctx, PepSide s)
 {
+    if (ctx && (ctx->side[s].packed == Packed::Yes || ctx->holds == SetsHold::BaseCodes)) return PEP_OK;
+    return pep_fail(ctx, PEP_ERR_STATE, s == PEP_SIDE_Q ? "queries not set / not translated" : "targets not set / not translated");
+}
+
+int download_aa(pep_ctx *ctx, PepSide side, uint8_t *codes, uint64_t cap, uint64_t *off)
+{
+    PEP_TRY(readable(ctx, side));
+    PEP_HIP(ctx, hipSetDevice(ctx->device));
+    const SeqSet &s = pep_set_of(ctx, side);
     if (s.residues > cap) return pep_fail(ctx, PEP_ERR_ARG, "output buffer too small");
-    PEP_TRY(pep_k1_host_tables(ctx));
+    PEP_TRY(pep_k1_host_tables(ctx, side));
     std::vector<uint8_t> img(s.total);
     if (s.total) PEP_HIP(ctx, hipMemcpy(img.data(), s.res.p, s.total, hipMemcpyDeviceToHost));
     uint64_t pos = 0;
@@ -417,10 +428,28 @@ int download_aa(pep_ctx *ctx, const SeqSet &s, uint8_t *codes, uint64_t cap, uin
     return PEP_OK;
 }
 
+int set_count(pep_ctx *ctx, PepSide s, uint32_t *n, uint64_t *residues)
+{
+    PEP_TRY(readable(ctx, s));
+    if (n) *n = pep_set_of(ctx, s).n;
+    if (residues) *residues = pep_set_of(ctx, s).residues;
+    return PEP_OK;
+}
+
+template <class Meta> int meta_out(pep_ctx *ctx, PepSide s, std::vector<Meta> pep_ctx::*table, Meta *out, uint32_t cap)
+{
+    PEP_TRY(readable(ctx, s));
+    PEP_TRY(pep_k1_host_tables(ctx, s));
+    const std::vector<Meta> &meta = ctx->*table;
+    if (cap < meta.size()) return pep_fail(ctx, PEP_ERR_ARG, "output buffer too small");
+    if (!meta.empty()) memcpy(out, meta.data(), meta.size() * sizeof(Meta));
+    return PEP_OK;
+}
+
 }  // namespace
 
 // entry points for other translation units (K9's gapped verification drives the alignment engine on its own sequence sets)
-int pep_upload_codes(pep_ctx *ctx, SeqSet &s, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n) { return upload_aa(ctx, s, codes, off, n, max_n); }
+int pep_upload_codes(pep_ctx *ctx, PepSide side, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n) { return upload_aa(ctx, side, codes, off, n, max_n); }
 int pep_upload_sub(pep_ctx *ctx) { return upload_sub_image(ctx); }
 
 extern "C" {
@@ -535,8 +564,7 @@ int pep_set_query_nt(pep_ctx *ctx, const uint8_t *nt, const uint64_t *off, uint3
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     if (n > PEP_MAX_QUERIES) return pep_fail(ctx, PEP_ERR_LIMIT, "too many queries");
     PEP_TRY(upload_nt(ctx, ctx->q_nt, nt, off, n));
-    ctx->nucl_valid = false;
-    ctx->q_from_nt = true; ctx->q_gtable = gtable; ctx->q_ready = false; ctx->resid_from_nucl = false;
+    sets_given_nt(ctx, PEP_SIDE_Q, gtable);
     return PEP_OK;
 }
 
@@ -546,9 +574,7 @@ int pep_set_ref_nt(pep_ctx *ctx, const uint8_t *nt, const uint64_t *off, uint32_
     if (frames != 3 && frames != 6) return pep_fail(ctx, PEP_ERR_ARG, "frames must be 3 or 6");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     PEP_TRY(upload_nt(ctx, ctx->r_nt, nt, off, n));
-    ctx->nucl_valid = false;
-    ctx->t_from_nt = true; ctx->t_gtable = gtable; ctx->t_frames = frames; ctx->t_ready = false; ctx->k1_base_frames = 0; ctx->resid_from_nucl = false;
-    ctx->group_of_seq.clear(); ctx->t_class_ready = false;
+    sets_given_nt(ctx, PEP_SIDE_T, gtable, frames);
     return PEP_OK;
 }
 
@@ -556,10 +582,10 @@ int pep_set_query_aa(pep_ctx *ctx, const uint8_t *codes, const uint64_t *off, ui
 {
     if (!ctx) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    PEP_TRY(upload_aa(ctx, ctx->q, codes, off, n, PEP_MAX_QUERIES));
+    PEP_TRY(upload_aa(ctx, PEP_SIDE_Q, codes, off, n, PEP_MAX_QUERIES));
     ctx->q_meta.resize(n);
     for (uint32_t i = 0; i < n; ++i) ctx->q_meta[i] = pep_query_meta{i, 0u, ctx->q.h_len[i], 0u};
-    ctx->q_from_nt = false; ctx->q_ready = true; ctx->resid_from_nucl = false;
+    sets_given_residues(ctx, PEP_SIDE_Q);
     return PEP_OK;
 }
 
@@ -567,104 +593,71 @@ int pep_set_ref_aa(pep_ctx *ctx, const uint8_t *codes, const uint64_t *off, uint
 {
     if (!ctx) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    PEP_TRY(upload_aa(ctx, ctx->t, codes, off, n, PEP_MAX_TARGETS));
+    PEP_TRY(upload_aa(ctx, PEP_SIDE_T, codes, off, n, PEP_MAX_TARGETS));
     ctx->t_meta.resize(n);
     for (uint32_t i = 0; i < n; ++i) ctx->t_meta[i] = pep_target_meta{i, 0u, 0u, ctx->t.h_len[i]};
-    ctx->t_from_nt = false; ctx->t_ready = true; ctx->resid_from_nucl = false;
-    ctx->group_of_seq.clear(); ctx->t_class_ready = false;
+    sets_given_residues(ctx, PEP_SIDE_T);
     return PEP_OK;
 }
+
+// K1 of the sides named: both are queued first, in the order asked for, so that the GPU runs one side's kernels while the host takes the other's summary; the
+// query side is taken here, the reference side here as well (in front of the queries) or left queued for the caller.  A side is marked packed = queued
+// as it goes on the stream: a caller that can fail before everything is taken holds a DropQueuedOnExit
+static int run_k1(pep_ctx *ctx, bool do_q, bool do_t, bool ref_first, bool take_ref)
+{
+    const bool wanted[2] = {do_q, do_t};
+    sets_hold(ctx, SetsHold::Inputs);          // (K1 writes the sets: whoever had taken them over, they are K1's again)
+    for (PepSide s : {ref_first ? PEP_SIDE_T : PEP_SIDE_Q, ref_first ? PEP_SIDE_Q : PEP_SIDE_T}) {
+        if (!wanted[s]) continue;
+        PEP_TRY(s == PEP_SIDE_Q ? pep_k1_query_queue(ctx, ctx->side[s].gtable) : pep_k1_ref_queue(ctx, ctx->side[s].frames, ctx->side[s].gtable));
+        side_queued(ctx, s);
+    }
+    if (do_t && take_ref) { PEP_TRY(pep_k1_ref_take(ctx)); side_taken(ctx, PEP_SIDE_T); }
+    if (do_q) { PEP_TRY(pep_k1_query_take(ctx)); side_taken(ctx, PEP_SIDE_Q); }
+    return PEP_OK;
+}
+
+// does K1 have to run for a side: a nucleotide one that is not packed (force: or is)
+static bool k1_wanted(const pep_ctx *ctx, PepSide s, int force) { return ctx->side[s].from_nt() && (force || ctx->side[s].packed != Packed::Yes); }
 
 int pep_translate(pep_ctx *ctx, int force)
 {
     if (!ctx) return PEP_ERR_ARG;
     PEP_HIP(ctx, hipSetDevice(ctx->device));
-    // both sides are queued first (reference, then queries); the reference's summary is taken while the query kernels run
-    ctx->resid_from_nucl = false;           // (pep_use_nt_as_residues left q_ready / t_ready false: K1 runs again)
-    const bool do_q = ctx->q_from_nt && (force || !ctx->q_ready), do_t = ctx->t_from_nt && (force || !ctx->t_ready);
+    sets_hold(ctx, SetsHold::Inputs);
+    const bool do_q = k1_wanted(ctx, PEP_SIDE_Q, force), do_t = k1_wanted(ctx, PEP_SIDE_T, force);
     if (!do_q && !do_t) return PEP_OK;       // nothing to translate (pep_search calls this every time): no events, no waiting
     const bool timed = ctx->timing_level >= 2 && ctx->k1_t0.ensure() && ctx->k1_t1.ensure();      // (the two timing events: made when a timed translation first needs them, kept as long as the context)
     if (timed) (void)hipEventRecord(ctx->k1_t0, ctx->stream);
-    if (do_t) PEP_TRY(pep_k1_ref(ctx, ctx->t_frames, ctx->t_gtable, 1));
-    if (do_q) PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 1));
-    if (do_t) { PEP_TRY(pep_k1_ref(ctx, ctx->t_frames, ctx->t_gtable, 2)); ctx->t_ready = true; }
-    if (do_q) { PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 2)); ctx->q_ready = true; }
+    DropQueuedOnExit guard{ctx};
+    PEP_TRY(run_k1(ctx, do_q, do_t, true, true));          // reference, then queries; the reference's summary is taken while the query kernels run
     float ms = 0.f;
     if (timed && hipEventRecord(ctx->k1_t1, ctx->stream) == hipSuccess && pep_event_wait(ctx->k1_t1) == hipSuccess) (void)hipEventElapsedTime(&ms, ctx->k1_t0, ctx->k1_t1);
     ctx->stats.ms_k1 = ms;
     return PEP_OK;
 }
 
-int pep_invalidate_translation(pep_ctx *ctx)
-{
-    if (!ctx) return PEP_ERR_ARG;
-    if (ctx->q_from_nt) ctx->q_ready = false;
-    if (ctx->t_from_nt) ctx->t_ready = false;
-    return PEP_OK;
-}
+int pep_invalidate_translation(pep_ctx *ctx) { return ctx ? (sets_invalidate_translation(ctx), PEP_OK) : PEP_ERR_ARG; }
 
 int pep_use_nt_as_residues(pep_ctx *ctx, int strands)
 {
     if (!ctx) return PEP_ERR_ARG;
     if (strands != 1 && strands != 2) return pep_fail(ctx, PEP_ERR_ARG, "strands must be 1 or 2");
-    if (!ctx->q_from_nt || !ctx->t_from_nt) return pep_fail(ctx, PEP_ERR_STATE, "pep_use_nt_as_residues needs pep_set_query_nt and pep_set_ref_nt first");
+    if (!ctx->side[PEP_SIDE_Q].from_nt() || !ctx->side[PEP_SIDE_T].from_nt()) return pep_fail(ctx, PEP_ERR_STATE, "pep_use_nt_as_residues needs pep_set_query_nt and pep_set_ref_nt first");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     pep_materialise_staged(ctx);
-    ctx->q_ready = ctx->t_ready = false;      // the packed protein sets are gone: a later pep_translate runs K1 again
-    ctx->resid_from_nucl = false;
-    ctx->t_class_ready = false;
+    sets_hold(ctx, SetsHold::TakenOver);      // the packed protein sets are gone: a later pep_translate runs K1 again
     PEP_TRY(pep_nucl_sets(ctx, strands));
-    ctx->resid_from_nucl = true;
+    sets_hold(ctx, SetsHold::BaseCodes);
     return PEP_OK;
 }
 
-int pep_query_count(pep_ctx *ctx, uint32_t *n, uint64_t *residues)
-{
-    if (!ctx || !(ctx->q_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "queries not set / not translated");
-    if (n) *n = ctx->q.n;
-    if (residues) *residues = ctx->q.residues;
-    return PEP_OK;
-}
-
-int pep_target_count(pep_ctx *ctx, uint32_t *n, uint64_t *residues)
-{
-    if (!ctx || !(ctx->t_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "targets not set / not translated");
-    if (n) *n = ctx->t.n;
-    if (residues) *residues = ctx->t.residues;
-    return PEP_OK;
-}
-
-int pep_get_query_meta(pep_ctx *ctx, pep_query_meta *out, uint32_t cap)
-{
-    if (!ctx || !(ctx->q_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "queries not set / not translated");
-    PEP_TRY(pep_k1_host_tables_q(ctx));
-    if (cap < ctx->q_meta.size()) return pep_fail(ctx, PEP_ERR_ARG, "output buffer too small");
-    if (!ctx->q_meta.empty()) memcpy(out, ctx->q_meta.data(), ctx->q_meta.size() * sizeof(pep_query_meta));
-    return PEP_OK;
-}
-
-int pep_get_target_meta(pep_ctx *ctx, pep_target_meta *out, uint32_t cap)
-{
-    if (!ctx || !(ctx->t_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "targets not set / not translated");
-    PEP_TRY(pep_k1_host_tables(ctx));
-    if (cap < ctx->t_meta.size()) return pep_fail(ctx, PEP_ERR_ARG, "output buffer too small");
-    if (!ctx->t_meta.empty()) memcpy(out, ctx->t_meta.data(), ctx->t_meta.size() * sizeof(pep_target_meta));
-    return PEP_OK;
-}
-
-int pep_get_query_aa(pep_ctx *ctx, uint8_t *codes, uint64_t cap, uint64_t *off)
-{
-    if (!ctx || !(ctx->q_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "queries not set / not translated");
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return download_aa(ctx, ctx->q, codes, cap, off);
-}
-
-int pep_get_target_aa(pep_ctx *ctx, uint8_t *codes, uint64_t cap, uint64_t *off)
-{
-    if (!ctx || !(ctx->t_ready || ctx->resid_from_nucl)) return pep_fail(ctx, PEP_ERR_STATE, "targets not set / not translated");
-    PEP_HIP(ctx, hipSetDevice(ctx->device));
-    return download_aa(ctx, ctx->t, codes, cap, off);
-}
+int pep_query_count(pep_ctx *ctx, uint32_t *n, uint64_t *residues) { return set_count(ctx, PEP_SIDE_Q, n, residues); }
+int pep_target_count(pep_ctx *ctx, uint32_t *n, uint64_t *residues) { return set_count(ctx, PEP_SIDE_T, n, residues); }
+int pep_get_query_meta(pep_ctx *ctx, pep_query_meta *out, uint32_t cap) { return meta_out(ctx, PEP_SIDE_Q, &pep_ctx::q_meta, out, cap); }
+int pep_get_target_meta(pep_ctx *ctx, pep_target_meta *out, uint32_t cap) { return meta_out(ctx, PEP_SIDE_T, &pep_ctx::t_meta, out, cap); }
+int pep_get_query_aa(pep_ctx *ctx, uint8_t *codes, uint64_t cap, uint64_t *off) { return download_aa(ctx, PEP_SIDE_Q, codes, cap, off); }
+int pep_get_target_aa(pep_ctx *ctx, uint8_t *codes, uint64_t cap, uint64_t *off) { return download_aa(ctx, PEP_SIDE_T, codes, cap, off); }
 
 int pep_set_target_groups(pep_ctx *ctx, const uint32_t *group, uint32_t n)
 {
@@ -672,9 +665,7 @@ int pep_set_target_groups(pep_ctx *ctx, const uint32_t *group, uint32_t n)
     for (uint32_t i = 1; i < n; ++i)
         if (group[i] < group[i - 1]) return pep_fail(ctx, PEP_ERR_ARG, "pep_set_target_groups: groups must be contiguous and non-decreasing");
     if (ctx->group_of_seq.size() == n && (n == 0 || memcmp(ctx->group_of_seq.data(), group, (size_t)n * sizeof(uint32_t)) == 0)) return PEP_OK;      // (nothing changes: what was derived from the groups stays)
-    ctx->group_of_seq.assign(group, group + n);
-    ctx->t_class_ready = false;
-    ctx->nucl_valid = false;                    // (the nucleotide tool's targets are laid out group by group)
+    sets_groups_changed(ctx, group, n);
     return PEP_OK;
 }
 
@@ -683,9 +674,9 @@ static int build_t_class(pep_ctx *ctx)
 {
     ctx->t_class_ready = false;
     if (ctx->group_of_seq.empty()) return PEP_OK;
-    const uint32_t n_seq = ctx->t_from_nt ? ctx->r_nt.n : ctx->t.n;
+    const uint32_t n_seq = ctx->side[PEP_SIDE_T].from_nt() ? ctx->r_nt.n : ctx->t.n;
     if (ctx->group_of_seq.size() != n_seq) return pep_fail(ctx, PEP_ERR_ARG, "pep_set_target_groups: one group per reference sequence expected");
-    PEP_TRY(pep_k1_host_tables(ctx));
+    PEP_TRY(pep_k1_host_tables(ctx, PEP_SIDE_T));
     const uint32_t nt = ctx->t.n, ns = (uint32_t)ctx->params.n_splits;
     std::vector<uint32_t> cls(nt + 1, 0u);
     uint32_t cur = 0xFFFFFFFFu, local = 0;
@@ -702,6 +693,70 @@ static int build_t_class(pep_ctx *ctx)
     return PEP_OK;
 }
 
+static int check_params(pep_ctx *ctx, const pep_search_params *params)
+{
+    if (params->n_shapes < 1 || params->n_shapes > 4 || params->base < 2 || params->top_k < 1 || params->n_splits < 1)
+        return pep_fail(ctx, PEP_ERR_ARG, "invalid search parameters");
+    // (the packed 16-bit passes keep H - open - extend inside a signed half word)
+    if (params->gap_open < 0 || params->gap_open > 255 || params->gap_ext < 1 || params->gap_ext > 255)
+        return pep_fail(ctx, PEP_ERR_ARG, "gap costs: 0 <= gap_open <= 255 and 1 <= gap_ext <= 255");
+    for (int s = 0; s < params->n_shapes; ++s) {
+        if (params->weight[s] < 1 || params->weight[s] > 32) return pep_fail(ctx, PEP_ERR_ARG, "invalid seed weight");
+        if (params->offs[s][params->weight[s] - 1] > 31) return pep_fail(ctx, PEP_ERR_ARG, "seed span above 32");
+        if (pow((double)params->base, params->weight[s]) > 34359738368.0) return pep_fail(ctx, PEP_ERR_ARG, "seed key does not fit 35 bits");
+        if (params->base > 15 || pow((double)params->base, (params->weight[s] + 1) / 2) > 4294967295.0)
+            return pep_fail(ctx, PEP_ERR_ARG, "reduced alphabet above 15 letters / half key above 32 bits");
+        for (int c = 0; c < 32; ++c)
+            if (params->reduce[c] != 0xFF && params->reduce[c] >= params->base) return pep_fail(ctx, PEP_ERR_ARG, "reduced letter outside the alphabet");
+    }
+    if (params->t_index_base < 0) return pep_fail(ctx, PEP_ERR_ARG, "t_index_base must not be negative");
+    if (params->hsp_mode < 0 || params->hsp_mode > 2) return pep_fail(ctx, PEP_ERR_ARG, "hsp_mode must be 0, 1 or 2");
+    if (params->stage1_min < 0 || (params->ungapped_min > 0 && params->stage1_min > params->ungapped_min))
+        return pep_fail(ctx, PEP_ERR_ARG, "stage1_min must lie between 0 and ungapped_min");
+    if (!(params->ka_lambda > 0.) || !(params->ka_k > 0.)) return pep_fail(ctx, PEP_ERR_ARG, "invalid Karlin-Altschul parameters");
+    if (!(params->dbsize > 0.) || !(params->max_evalue > 0.)) return pep_fail(ctx, PEP_ERR_ARG, "dbsize and max_evalue must be positive");
+    if (params->xdrop < 0 || params->xdrop > 48 || params->ext_right < 1 || params->ext_right > 48 || params->ext_left < 0 || params->ext_left > 48)
+        return pep_fail(ctx, PEP_ERR_ARG, "invalid ungapped-extension parameters");
+    // code 31 is the padding between packed sequences: its scores end every extension and keep the DP out of the padding
+    for (int c = 0; c < 32; ++c)
+        if (params->sub[PEP_PAD_CODE * 32 + c] > -64 || params->sub[c * 32 + PEP_PAD_CODE] > -64)
+            return pep_fail(ctx, PEP_ERR_ARG, "substitution table: row and column 31 (the padding code) must be <= -64");
+    return PEP_OK;
+}
+
+// pep_find_candidates' before_sync: host work that only the alignment stage needs - the score thresholds (from the query lengths K1 left in pinned memory) and
+// their upload - is done while the seed stage's kernels run (between its last launch and its synchronisation)
+static int prepare_thresholds(pep_ctx *c)
+{
+    PEP_TRY(dev_reserve(c, c->d_min_score, (size_t)(c->q.n + 1) * 4));
+    PEP_TRY(pin_reserve(c, c->pin_ms, (size_t)(c->q.n + 1) * 4));
+    int32_t *ms = reinterpret_cast<int32_t *>(c->pin_ms.p);
+    // the threshold depends on the length only and lengths repeat: one logarithm per distinct length (direct-mapped memo)
+    uint32_t memo_len[1024];
+    int32_t memo_val[1024];
+    for (int i = 0; i < 1024; ++i) memo_len[i] = 0xFFFFFFFFu;
+    for (uint32_t i = 0; i < c->q.n; ++i) {
+        const uint32_t L = c->q.h_len[i], slot = L & 1023u;
+        if (memo_len[slot] != L) {
+            memo_len[slot] = L;
+            memo_val[slot] = pep_min_score_ka(L, c->params.dbsize, c->params.max_evalue, c->params.ka_lambda, c->params.ka_k);
+        }
+        ms[i] = memo_val[slot];
+    }
+    c->upload.d_dst = c->d_min_score.p; c->upload.pinned_src = c->pin_ms.p; c->upload.n_words = c->q.n;      // (rides on the seed stage's read-back kernel)
+    return PEP_OK;
+}
+
+// pep_find_candidates' need_targets: the summary of a reference side that pep_search left queued, taken after the first index build has been queued behind it
+static int finish_targets(pep_ctx *c)
+{
+    if (c->side[PEP_SIDE_T].packed != Packed::Queued) return PEP_OK;
+    PEP_TRY(pep_k1_ref_take(c));
+    side_taken(c, PEP_SIDE_T);
+    c->stats.target_residues = c->t.residues;
+    return PEP_OK;
+}
+
 int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out)
 {
     if (!ctx || !out) return PEP_ERR_ARG;
@@ -709,63 +764,25 @@ int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out)
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     pep_materialise_staged(ctx);                 // an earlier result that was not copied out yet keeps its own copy
     if (params) {
-        if (params->n_shapes < 1 || params->n_shapes > 4 || params->base < 2 || params->top_k < 1 || params->n_splits < 1)
-            return pep_fail(ctx, PEP_ERR_ARG, "invalid search parameters");
-        // (the packed 16-bit passes keep H - open - extend inside a signed half word)
-        if (params->gap_open < 0 || params->gap_open > 255 || params->gap_ext < 1 || params->gap_ext > 255)
-            return pep_fail(ctx, PEP_ERR_ARG, "gap costs: 0 <= gap_open <= 255 and 1 <= gap_ext <= 255");
-        for (int s = 0; s < params->n_shapes; ++s) {
-            if (params->weight[s] < 1 || params->weight[s] > 32) return pep_fail(ctx, PEP_ERR_ARG, "invalid seed weight");
-            if (params->offs[s][params->weight[s] - 1] > 31) return pep_fail(ctx, PEP_ERR_ARG, "seed span above 32");
-            if (pow((double)params->base, params->weight[s]) > 34359738368.0) return pep_fail(ctx, PEP_ERR_ARG, "seed key does not fit 35 bits");
-            if (params->base > 15 || pow((double)params->base, (params->weight[s] + 1) / 2) > 4294967295.0)
-                return pep_fail(ctx, PEP_ERR_ARG, "reduced alphabet above 15 letters / half key above 32 bits");
-            for (int c = 0; c < 32; ++c)
-                if (params->reduce[c] != 0xFF && params->reduce[c] >= params->base) return pep_fail(ctx, PEP_ERR_ARG, "reduced letter outside the alphabet");
-        }
-        if (params->t_index_base < 0) return pep_fail(ctx, PEP_ERR_ARG, "t_index_base must not be negative");
-        if (params->hsp_mode < 0 || params->hsp_mode > 2) return pep_fail(ctx, PEP_ERR_ARG, "hsp_mode must be 0, 1 or 2");
-        if (params->stage1_min < 0 || (params->ungapped_min > 0 && params->stage1_min > params->ungapped_min))
-            return pep_fail(ctx, PEP_ERR_ARG, "stage1_min must lie between 0 and ungapped_min");
-        if (!(params->ka_lambda > 0.) || !(params->ka_k > 0.)) return pep_fail(ctx, PEP_ERR_ARG, "invalid Karlin-Altschul parameters");
-        if (!(params->dbsize > 0.) || !(params->max_evalue > 0.)) return pep_fail(ctx, PEP_ERR_ARG, "dbsize and max_evalue must be positive");
-        if (params->xdrop < 0 || params->xdrop > 48 || params->ext_right < 1 || params->ext_right > 48 || params->ext_left < 0 || params->ext_left > 48)
-            return pep_fail(ctx, PEP_ERR_ARG, "invalid ungapped-extension parameters");
-        // code 31 is the padding between packed sequences: its scores end every extension and keep the DP out of the padding
-        for (int c = 0; c < 32; ++c)
-            if (params->sub[PEP_PAD_CODE * 32 + c] > -64 || params->sub[c * 32 + PEP_PAD_CODE] > -64)
-                return pep_fail(ctx, PEP_ERR_ARG, "substitution table: row and column 31 (the padding code) must be <= -64");
+        PEP_TRY(check_params(ctx, params));
         if (memcmp(ctx->params.sub, params->sub, sizeof(params->sub)) != 0) ctx->sub_ready = false;      // the LDS image follows the table only
         ctx->params = *params;
     }
-    ctx->k1_t_deferred = false;
-    if (!ctx->resid_from_nucl) {
-        const bool do_q = ctx->q_from_nt && !ctx->q_ready, do_t = ctx->t_from_nt && !ctx->t_ready;
+    DropQueuedOnExit guard{ctx};                 // whatever fails below while a side is queued: the next search translates it again
+    if (ctx->holds != SetsHold::BaseCodes) {
+        const bool do_q = k1_wanted(ctx, PEP_SIDE_Q, 0), do_t = k1_wanted(ctx, PEP_SIDE_T, 0);
         if ((do_q || do_t) && ctx->timing_level < 2 && ctx->group_of_seq.empty()) {
-            // K1 inside the search (sets given or invalidated since the last one): both sides are queued, queries first, and only the query
-            // side is waited for here - the reference side's summary is picked up after the first index build has been queued behind it
-            // (pep_find_candidates' need_targets), so the GPU runs from K1 into the seed stage without waiting for the host
-            if (do_q) PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 1));
-            if (do_t) PEP_TRY(pep_k1_ref(ctx, ctx->t_frames, ctx->t_gtable, 1));
-            if (do_q) { PEP_TRY(pep_k1_query(ctx, ctx->q_gtable, 2)); ctx->q_ready = true; }
-            ctx->k1_t_deferred = do_t;
+            // K1 inside the search: only the query side is waited for here, so the GPU runs from K1 into the seed stage without waiting for the host (finish_targets)
+            PEP_TRY(run_k1(ctx, do_q, do_t, false, false));
             ctx->stats.ms_k1 = 0.;
         } else PEP_TRY(pep_translate(ctx, 0));
-        if (!ctx->q_ready || !(ctx->t_ready || ctx->k1_t_deferred)) { ctx->k1_t_deferred = false; return pep_fail(ctx, PEP_ERR_STATE, "pep_search before both sequence sets were given"); }
+        if (ctx->side[PEP_SIDE_Q].packed != Packed::Yes || ctx->side[PEP_SIDE_T].packed == Packed::No) return pep_fail(ctx, PEP_ERR_STATE, "pep_search before both sequence sets were given");
     }
-    auto finish_targets = [](pep_ctx *c) -> int {
-        if (!c->k1_t_deferred) return PEP_OK;
-        c->k1_t_deferred = false;
-        PEP_TRY(pep_k1_ref(c, c->t_frames, c->t_gtable, 2));
-        c->t_ready = true;
-        c->stats.target_residues = c->t.residues;
-        return PEP_OK;
-    };
-    if (!ctx->sub_ready) { const int rc0 = upload_sub_image(ctx); if (rc0 != PEP_OK) { ctx->k1_t_deferred = false; return rc0; } ctx->sub_ready = true; }
-    { const int rc0 = build_t_class(ctx); if (rc0 != PEP_OK) { ctx->k1_t_deferred = false; return rc0; } }
+    if (!ctx->sub_ready) { PEP_TRY(upload_sub_image(ctx)); ctx->sub_ready = true; }
+    PEP_TRY(build_t_class(ctx));
 
     pep_result *res = new (std::nothrow) pep_result();
-    if (!res) { ctx->k1_t_deferred = false; return pep_fail(ctx, PEP_ERR_INTERNAL, "out of host memory"); }
+    if (!res) return pep_fail(ctx, PEP_ERR_INTERNAL, "out of host memory");
     res->ctx = ctx;
     const double ms_k1 = ctx->stats.ms_k1;
     memset(&ctx->stats, 0, sizeof(ctx->stats));
@@ -776,30 +793,8 @@ int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out)
     for (int id = 0; id < TM_COUNT; ++id) ctx->tm_state[id] = 0;
     pep_timer_begin(ctx, TM_SEED); pep_timer_begin(ctx, TM_TOTAL);
     uint64_t *d_cands = nullptr, n_cands = 0;
-    // host work that only the alignment stage needs - the score thresholds (from the query lengths K1 left in pinned memory) and their upload - is done while the
-    // seed stage's kernels run (between its last launch and its synchronisation)
-    auto prepare_thresholds = [](pep_ctx *c) -> int {
-        PEP_TRY(dev_reserve(c, c->d_min_score, (size_t)(c->q.n + 1) * 4));
-        PEP_TRY(pin_reserve(c, c->pin_ms, (size_t)(c->q.n + 1) * 4));
-        int32_t *ms = reinterpret_cast<int32_t *>(c->pin_ms.p);
-        // the threshold depends on the length only and lengths repeat: one logarithm per distinct length (direct-mapped memo)
-        uint32_t memo_len[1024];
-        int32_t memo_val[1024];
-        for (int i = 0; i < 1024; ++i) memo_len[i] = 0xFFFFFFFFu;
-        for (uint32_t i = 0; i < c->q.n; ++i) {
-            const uint32_t L = c->q.h_len[i], slot = L & 1023u;
-            if (memo_len[slot] != L) {
-                memo_len[slot] = L;
-                memo_val[slot] = pep_min_score_ka(L, c->params.dbsize, c->params.max_evalue, c->params.ka_lambda, c->params.ka_k);
-            }
-            ms[i] = memo_val[slot];
-        }
-        c->upload.d_dst = c->d_min_score.p; c->upload.pinned_src = c->pin_ms.p; c->upload.n_words = c->q.n;      // (rides on the seed stage's read-back kernel)
-        return PEP_OK;
-    };
     int rc = pep_find_candidates(ctx, &d_cands, &n_cands, prepare_thresholds, finish_targets);
-    if (rc == PEP_OK && ctx->k1_t_deferred) rc = finish_targets(ctx);
-    ctx->k1_t_deferred = false;                   // (after a failure the reference side simply is not ready: the next search translates again)
+    if (rc == PEP_OK) rc = finish_targets(ctx);
     pep_timer_end(ctx, TM_SEED);
     if (rc == PEP_OK) rc = pep_extend(ctx, d_cands, n_cands, nullptr, res, true);
     const bool grouped = rc == PEP_OK && ctx->grp_nodes != 0;

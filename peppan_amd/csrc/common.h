@@ -128,6 +128,18 @@ static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_
 
 struct pep_result;
 
+enum PepSide { PEP_SIDE_Q = 0, PEP_SIDE_T = 1 };         // the state of the context's two packed sequence sets, one record per side (the transitions: setstate.h)
+enum class SetSource { None, Nt, Residues };            // what the side was given: nothing yet, nucleotides (K1 packs them), residues (packed by the upload)
+enum class Packed { No, Queued, Yes };                  // No: given or invalidated; Queued: K1 is on the stream, its summary not taken; Yes: the summary is in the SeqSet
+enum class SetsHold { Inputs, BaseCodes, TakenOver };   // ctx->q / ctx->t hold: the inputs as K1 or an upload packed them; the nucleotide tool's base codes; what K9's gapped stage put there
+struct SideState {
+    SetSource source = SetSource::None;
+    int gtable = 11, frames = 6;            // (frames: reference side)
+    Packed packed = Packed::No;
+    bool tables_built = true;               // false: the host tables (meta records, h_off, h_len) are still to be made from K1's descriptors on the device (pep_k1_host_tables)
+    bool from_nt() const { return source == SetSource::Nt; }
+};
+
 // K1's descriptor of a packed sequence (translate.hip): the nucleotide sequence it was translated from, the frame (1 - 3 forward, 4 - 6 reverse strand), the residue its
 // chunk starts at inside that frame, its length in residues.  One per query (d_k1_desc_q) / target (d_k1_desc_t), on the device; the host's meta records are made from them.
 struct PackDesc {
@@ -206,18 +218,13 @@ struct pep_ctx {
     DevBuf d_k1_desc_q, d_k1_desc_t;        // K1's descriptors (+ the summary's accumulators behind them): fetched only when the host tables are asked for
     DevBuf d_self_delta, d_self_t;          // seed stage, self-search: per 32-byte block of the target layout the distance to the query that IS that target (pep_self_map, self_prepare);
                                             // per reference sequence the packed sequence its frame 1 starts with (K1: k1_ref_desc)
-    uint32_t self_first_n = 0;              // entries of d_self_t (reference sequences of the last K1 of the reference side)
     const uint32_t *self_first = nullptr;   // what pep_self_map found applicable to the current sets: d_self_t (K1's) or the nucleotide tool's nucl_t.d_first; its entries; may a target be longer than its query
     uint32_t self_first_cnt = 0;
     int self_exact_len = 0;
     Event k1_event;                         // the point of the stream where the reference side's downloads have arrived
     Event k1q_event;                        // ... and the query side's
-    bool k1q_event_set = false;
-    bool k1_t_deferred = false;             // pep_search: the reference side's K1 is queued, its summary not taken yet
     Event wait_event;                       // pep_stream_wait: marks the point of the stream the host is waiting for
     Event k1_t0, k1_t1;                     // pep_translate's timing pair (created once)
-    uint32_t k1_desc_cap = 0;               // descriptor slots of the reference side's last K1 (the summary sits behind them in pin_k1)
-    bool t_tables_lazy = false, q_tables_lazy = false;   // a side's host tables (meta records, h_off, h_len) have not been built from its pinned descriptors yet (pep_k1_host_tables)
     PinBuf pin_up;                          // grow-only: staging area of uploads out of pageable memory (pep_h2d)
     size_t pin_up_used = 0;
     Event up_event;                         // the point of the stream where the last upload out of pin_up has left it
@@ -236,15 +243,17 @@ struct pep_ctx {
     SeqSet q, t;
     std::vector<pep_query_meta> q_meta;     // frame chosen per query (K1)
     std::vector<pep_target_meta> t_meta;    // (seq, frame, chunk offset, length) per target (K1)
-    bool q_from_nt = false, t_from_nt = false;
-    bool q_ready = false, t_ready = false, sub_ready = false, codon_ready = false;
-    bool resid_from_nucl = false;           // ctx->q / ctx->t hold base codes made by pep_use_nt_as_residues (until the next pep_translate / pep_set_*)
-    int q_gtable = 11, t_gtable = 11, t_frames = 6;
+    // what q / t hold: assigned by the transitions of setstate.h alone, which also drop what was derived from the sets - nucl_valid .. self_first_n below
+    SideState side[2];                      // [PEP_SIDE_Q], [PEP_SIDE_T]
+    SetsHold holds = SetsHold::Inputs;
+    bool nucl_valid = false, t_class_ready = false;
+    int k1_base_frames = 0;                 // 0 = K1's length-derived reference tables (below) are not computed for the current reference set
+    uint32_t self_first_n = 0;              // entries of d_self_t (reference sequences of the last K1 of the reference side)
+    bool sub_ready = false, codon_ready = false;
     // K1 reference side: chunk-slot prefix per (sequence, frame), a function of the input lengths only - kept between translations
     DevBuf d_k1_base;
     std::vector<uint64_t> k1_base;
     uint64_t k1_upper = 0;
-    int k1_base_frames = 0;            // 0 = not computed for the current reference set
     // ... and the tables of its LONG frames (contigs of genomes: k1_stop_mask / k1_ref_chunks_mask / k1_ref_desc_fill): tiles of the stop mask, the long frames'
     // records (+ frame -> record), the stop mask itself, tiles of chunk slots
     DevBuf d_k1_seg, d_k1_long, d_k1_spec, d_k1_tiles;
@@ -260,7 +269,6 @@ struct pep_ctx {
         DevBuf d_first;                     // targets: per reference sequence the packed sequence that is its forward strand (seeds.hip: self_prepare)
         uint32_t n_first = 0;
     } nucl_q, nucl_t;
-    bool nucl_valid = false;
     int nucl_strands = 0;
     DevBuf d_min_score;
     DevBuf d_trace_defer;                   // traceback pass: pairs that left their sub-band, waiting for their full-band sweep (sw.hip: run_deferred)
@@ -268,7 +276,6 @@ struct pep_ctx {
     std::vector<uint32_t> group_of_seq;     // optional: competition group of every reference sequence (pep_set_target_groups)
     DevBuf d_t_class;
     DevBuf d_t_subject;                         // hsp_mode 2: the reference sequence every target is a strand / frame / chunk of (uploaded per search)
-    bool t_class_ready = false;
     // workspaces (grow-only, reused between searches and between calls: PepWsSlot above)
     DevBuf ws[PEP_WS_COUNT];
     DevBuf sub_lds;                         // replicated substitution table image (32 KiB)
@@ -315,6 +322,7 @@ struct pep_ctx {
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
 };
 
+inline SeqSet &pep_set_of(pep_ctx *ctx, PepSide s) { return s == PEP_SIDE_Q ? ctx->q : ctx->t; }
 struct pep_result {
     pep_ctx *ctx = nullptr;
     std::vector<pep_hit> hits;              // used once the result no longer lives in the context's staging area
@@ -363,7 +371,6 @@ int pep_sync_reads(pep_ctx *ctx);
 // before falling back to a blocking wait: the searches are chains of short kernels with a handful of host decisions in between, and a
 // sleeping host thread adds tens of microseconds of wake-up latency to each of them.
 hipError_t pep_stream_wait(pep_ctx *ctx);
-hipError_t pep_event_wait(hipEvent_t ev);
 int pin_reserve(pep_ctx *ctx, PinBuf &b, size_t bytes);
 // stream-ordered upload of caller memory: through the context's pinned staging area for anything of size (a copy command straight out of pageable
 // memory has the runtime pin the pages first - 15 ms for the 10 MB of a gene set it has not seen before, 0.2 ms the second time); the caller's buffer
@@ -439,10 +446,9 @@ int pep_sort_u64(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, const uint32_t
                  const pep_key_unpack *unpack);   // result in d_keys
 int pep_sort_u64_two_level(pep_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint64_t n, int bits, const uint32_t *d_top_hist, const pep_key_unpack *unpack);
 // ---- translate.hip  (K1)
-int pep_k1_query(pep_ctx *ctx, int gtable, int phase = 0);
-int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase = 0);
-int pep_k1_host_tables(pep_ctx *ctx);      // builds the per-sequence host tables of both sides if their last K1 left them to be built on demand
-int pep_k1_host_tables_q(pep_ctx *ctx);    // the query side only (the search needs the query lengths for its score thresholds)
+int pep_k1_query_queue(pep_ctx *ctx, int gtable), pep_k1_query_take(pep_ctx *ctx);     // queue: a side's device work and the download of its summary; take: wait for that download, fill in the SeqSet
+int pep_k1_ref_queue(pep_ctx *ctx, int frames, int gtable), pep_k1_ref_take(pep_ctx *ctx);
+int pep_k1_host_tables(pep_ctx *ctx, PepSide side);    // the per-sequence host tables of one side, if its last K1 left them to be built on demand
 int pep_nucl_sets(pep_ctx *ctx, int strands);      // the nucleotide sets themselves as residue sets (base codes; reference: forward strands + reverse complements)
 // ---- seeds.hip  (K2-K4)
 // before_sync (optional): host work to do once every kernel of the stage is queued, while the GPU runs them (the stage ends with a synchronisation)
@@ -470,5 +476,5 @@ int pep_upload_blk2seq(pep_ctx *ctx, SeqSet &s);
 #define PEP_SELF_NONE 0xFFFFFFFFu
 #define PEP_SELF_NO_DELTA ((int32_t)0x80808080)
 int pep_self_map(pep_ctx *ctx, int *on);
-int pep_upload_codes(pep_ctx *ctx, SeqSet &s, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n);
+int pep_upload_codes(pep_ctx *ctx, PepSide side, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n);
 int pep_upload_sub(pep_ctx *ctx);

@@ -9,6 +9,7 @@
 //   lc_assign  rounds of a monotone fixed point that equals the sequential greedy assignment                (random 4 B)
 // All integer except the two threshold comparisons, done in IEEE double exactly as the oracle does.
 #include "common.h"
+#include "setstate.h"
 #include <algorithm>
 
 namespace {
@@ -272,10 +273,7 @@ int k9_gapped(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, int bas
     pep_default_params(&defaults);
     k9_params(base, defaults, ctx->params);
     int rc = pep_upload_sub(ctx);
-    // the sequence sets of the context are taken over: a later pep_search needs its inputs again (nucleotide inputs are re-translated)
-    ctx->q_ready = ctx->t_ready = false;
-    ctx->resid_from_nucl = false;
-    ctx->t_class_ready = false;
+    sets_hold(ctx, SetsHold::TakenOver);
     const uint64_t BYTES = 200ull << 20;                 // packed bytes per side and batch
     size_t at = 0;
     std::vector<uint8_t> codes;
@@ -304,17 +302,17 @@ int k9_gapped(pep_ctx *ctx, const uint8_t *h_res, const uint64_t *h_off, int bas
         std::sort(q_list.begin(), q_list.end());
         q_list.erase(std::unique(q_list.begin(), q_list.end()), q_list.end());
         if (q_list.size() > PEP_MAX_QUERIES) { rc = pep_fail(ctx, PEP_ERR_LIMIT, "pep_linclust: gapped batch exceeds the query limit"); break; }    // (the parameters are restored below)
-        auto upload = [&](SeqSet &set, const std::vector<uint32_t> &list, uint32_t max_n) {
+        auto upload = [&](PepSide side, const std::vector<uint32_t> &list, uint32_t max_n) {
             codes.clear(); off.assign(1, 0);
             for (uint32_t x : list) {
                 codes.insert(codes.end(), h_res + h_off[x], h_res + h_off[x + 1]);
                 off.push_back(codes.size());
             }
             if (codes.empty()) codes.push_back(0);
-            return pep_upload_codes(ctx, set, codes.data(), off.data(), (uint32_t)list.size(), max_n);
+            return pep_upload_codes(ctx, side, codes.data(), off.data(), (uint32_t)list.size(), max_n);
         };
-        rc = upload(ctx->q, q_list, PEP_MAX_QUERIES);
-        if (rc == PEP_OK) rc = upload(ctx->t, t_list, PEP_MAX_TARGETS);
+        rc = upload(PEP_SIDE_Q, q_list, PEP_MAX_QUERIES);
+        if (rc == PEP_OK) rc = upload(PEP_SIDE_T, t_list, PEP_MAX_TARGETS);
         if (rc != PEP_OK) break;
         for (size_t i = at, ti = 0; i < end; ++i) {
             while (t_list[ti] != cands[i].c) ++ti;

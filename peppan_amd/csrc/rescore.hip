@@ -220,8 +220,8 @@ int pep_k7_hits_queue(pep_ctx *ctx, uint64_t n, const pep_hit *d_hits, const uin
 {
     if (n == 0) return PEP_OK;
     if (!ctx->q_nt.nt.p || !ctx->r_nt.nt.p) return pep_fail(ctx, PEP_ERR_STATE, "pep_set_nt_match needs pep_set_query_nt and pep_set_ref_nt first");
-    const bool nucl = ctx->resid_from_nucl;
-    if (!nucl && !(ctx->q_from_nt && ctx->t_from_nt))
+    const bool nucl = ctx->holds == SetsHold::BaseCodes;
+    if (!nucl && !(ctx->side[PEP_SIDE_Q].from_nt() && ctx->side[PEP_SIDE_T].from_nt()))
         return pep_fail(ctx, PEP_ERR_STATE, "pep_set_nt_match: the packed sets of this search were not made from the context's nucleotide sets");
     if (nucl ? (!ctx->nucl_q.d_desc.p || !ctx->nucl_t.d_desc.p) : (!ctx->d_k1_desc_q.p || !ctx->d_k1_desc_t.p))
         return pep_fail(ctx, PEP_ERR_STATE, "pep_set_nt_match: no descriptors of the packed sets on the device");

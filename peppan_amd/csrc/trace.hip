@@ -744,7 +744,7 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
             hipLaunchKernelGGL(cull_hsps, dim3((unsigned)ceil_div(n_b, 256)), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys);
             hipLaunchKernelGGL(apply_dedupe, dim3((unsigned)ceil_div(n_b, 256)), dim3(256), 0, st, d_n_sel, sel);
             // the subject of every target: the reference sequence it is a strand / frame / chunk of (K1's table)
-            PEP_TRY(pep_k1_host_tables(ctx));
+            PEP_TRY(pep_k1_host_tables(ctx, PEP_SIDE_T));
             if (ctx->t_meta.size() != ctx->t.n) return pep_fail(ctx, PEP_ERR_STATE, "hsp_mode 2 needs the targets' sequence table (targets made by pep_translate / pep_use_nt_as_residues)");
             std::vector<uint32_t> subj(ctx->t.n + 1, 0u);
             for (uint32_t t = 0; t < ctx->t.n; ++t) subj[t] = ctx->t_meta[t].seq;

@@ -9,6 +9,7 @@
 // Byte-granular, HBM-bound: 3 nt bytes read per residue byte written.
 #include "common.h"
 #include "lookback.h"
+#include "setstate.h"
 #include <algorithm>
 
 namespace {
@@ -655,12 +656,11 @@ int reserve_packed(pep_ctx *ctx, SeqSet &out, uint32_t cap, uint64_t upper)
     return PEP_OK;
 }
 
-// Device-side layout + packing (after reserve_packed).  d_desc / d_padded hold up to `cap` entries (padded = 0 beyond the *d_n real ones); `upper` bounds the
-// layout's size.  Nothing is read back here: the caller downloads the descriptors once, after everything is queued.
+// Device-side layout + packing (after reserve_packed).  d_desc / d_padded hold up to `cap` entries (padded = 0 beyond the *d_n real ones).
+// Nothing is read back here: k1_pack leaves the set's summary in pinned memory, the descriptors stay on the device.
 int layout_and_pack(pep_ctx *ctx, const NtSet &nt, int tab, const PackDesc *d_desc, const uint32_t *d_padded, uint32_t cap, const uint32_t *d_n,
-                    uint64_t upper, SeqSet &out, DevBuf &d_scan, DevBuf &tmp, K1Summary *pin_sum)
+                    SeqSet &out, K1Summary *pin_sum)
 {
-    (void)d_scan; (void)tmp;
     K1Summary *d_sum = reinterpret_cast<K1Summary *>(const_cast<PackDesc *>(d_desc) + cap);        // behind the descriptors
     LbLaunch sc;
     const uint64_t tiles = ceil_div((uint64_t)cap + 1, 256);
@@ -672,9 +672,10 @@ int layout_and_pack(pep_ctx *ctx, const NtSet &nt, int tab, const PackDesc *d_de
     return PEP_OK;
 }
 
-// the eager part of a finished K1 side: the set's summary (computed by k1_offsets, downloaded behind the descriptors)
-int take_summary(pep_ctx *ctx, const void *pinned, SeqSet &out)
+// the eager part of a finished K1 side: the set's summary (computed by k1_offsets, written into pinned memory by k1_pack; `ev` marks where it has arrived)
+int k1_take(pep_ctx *ctx, hipEvent_t ev, const void *pinned, SeqSet &out)
 {
+    PEP_HIP(ctx, pep_event_wait(ev));
     const K1Summary *sum = reinterpret_cast<const K1Summary *>(pinned);
     if (sum->total > PEP_MAX_RESIDUES) return pep_fail(ctx, PEP_ERR_LIMIT, "packed protein set exceeds 2^29 bytes");
     if (sum->max_len > PEP_MAX_SEQ_LEN) return pep_fail(ctx, PEP_ERR_LIMIT, "protein longer than PEP_MAX_SEQ_LEN");
@@ -682,129 +683,95 @@ int take_summary(pep_ctx *ctx, const void *pinned, SeqSet &out)
     return PEP_OK;
 }
 
-// host mirrors of a packed set from its downloaded descriptors (same arithmetic as k1_offsets)
-void finish_layout(const PackDesc *desc, uint32_t n, SeqSet &out)
-{
-    out.h_off.resize((size_t)n + 1);
-    out.h_len.resize(n);
-    uint64_t pos = PEP_END_PAD;
-    for (uint32_t i = 0; i < n; ++i) {
-        out.h_off[i] = (uint32_t)pos;
-        out.h_len[i] = desc[i].len;
-        pos += ((uint64_t)desc[i].len + 15) / 16 * 16 + PEP_SEQ_GAP;
-    }
-    out.h_off[n] = (uint32_t)(pos + PEP_END_PAD);
-}
-
-int k1_ref_finish(pep_ctx *ctx)
-{
-    PEP_HIP(ctx, pep_event_wait(ctx->k1_event));
-    PEP_TRY(take_summary(ctx, ctx->pin_k1.p, ctx->t));
-    ctx->t_tables_lazy = true;               // t_meta, h_off, h_len: pep_k1_host_tables, when somebody needs them
-    return PEP_OK;
-}
-
 // The slots of pep_ctx::ws: the query side's, then the reference side's.  The two sides share slots with each other and with the seed stage (PepWsSlot), whose
 // kernels pep_search queues right behind them without a wait: stream order is what makes that safe - a side's kernels have read their slots before anything
 // queued later writes them - and what has to outlive the call (descriptors, summaries) has buffers of its own.
 enum {
-    K1Q_SPARE_A = 0, K1Q_SPARE_B = 1,       // reserved for n + 1 words each, used by no kernel
     K1Q_PADDED = 3,                         // padded length per query, u32: k1_query_frames, read last by k1_offsets
-    K1Q_PACK_SCAN = 4,                      // handed to layout_and_pack, which touches neither of its two workspace arguments (with K1Q_PACK_TMP)
     K1Q_COUNT = 5,                          // number of queries, u32: k1_query_frames, read last by k1_pack
-    K1Q_PACK_TMP = 6,
     K1R_CHUNK_CNT = 1, K1R_CHUNK_OFF, K1R_CHUNK_LEN,    // chunks per frame u32; first residue and length per chunk slot u32: k1_ref_chunks(_mask), read last by k1_ref_desc(_fill)
     K1R_FIRST = 5,                          // first packed sequence per frame, the number of targets behind them, u32: k1_ref_desc, read last by k1_pack
     K1R_PADDED,                             // padded length per target, u32: k1_ref_desc(_fill), read last by k1_offsets
-    K1R_PACK_SCAN, K1R_PACK_TMP,            // handed to layout_and_pack (as K1Q_PACK_SCAN)
     K1_SLOTS
 };
-static_assert(K1Q_PACK_TMP < K1_SLOTS && K1_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
+static_assert(K1Q_COUNT < K1_SLOTS && K1_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
 
 }  // namespace
 
-// phase 1 = queue the device work and the download of the descriptors, 2 = wait for it and build the host-side tables, 0 = both.
-// pep_translate queues the reference side, then the query side, and builds the reference tables while the query kernels run.
-int pep_k1_query(pep_ctx *ctx, int gtable, int phase)
+// K1 in two steps per side: queue puts the device work and the download of the set's summary on the stream, take waits for that download and fills in the SeqSet.
+// Who queues what in which order, and who takes when: run_k1 and finish_targets (capi.hip).
+int pep_k1_query_queue(pep_ctx *ctx, int gtable)
 {
     const NtSet &nt = ctx->q_nt;
     const int tab = gtable == 4 ? 1 : 0;
     const uint32_t n = nt.n;
-    if (phase != 2) {
-        PEP_TRY(upload_codon_table(ctx));
-        if (n > PEP_MAX_QUERIES) return pep_fail(ctx, PEP_ERR_LIMIT, "too many queries");
-        DevBuf *W = ctx->ws;
-        PEP_TRY(dev_reserve(ctx, W[K1Q_SPARE_A], ((size_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[K1Q_SPARE_B], ((size_t)n + 1) * 4));
-        DevBuf &D = ctx->d_k1_desc_q;              // the descriptors stay on the device (a buffer of their own): fetched when somebody asks for the host tables
-        PEP_TRY(dev_reserve(ctx, D, (2 * (size_t)n + 4) * sizeof(PackDesc)));      // + the summary and the source records behind the descriptors
-        PEP_TRY(pin_reserve(ctx, ctx->pin_k1q, sizeof(K1Summary) + ((size_t)n + 1) * 4));
-        K1Summary *pin_sum = reinterpret_cast<K1Summary *>(ctx->pin_k1q.p);
-        uint32_t *pin_len = reinterpret_cast<uint32_t *>(ctx->pin_k1q.p + sizeof(K1Summary));
-        PEP_TRY(dev_reserve(ctx, W[K1Q_PADDED], ((size_t)n + 1) * 4));
-        PEP_TRY(dev_reserve(ctx, W[K1Q_COUNT], 16));
-        const uint64_t upper = 2 * PEP_END_PAD + (nt.total + 2 * (uint64_t)n) / 3 + (uint64_t)n * (16 + PEP_SEQ_GAP);
-        PEP_TRY(reserve_packed(ctx, ctx->q, n, upper));
-        if (n) hipLaunchKernelGGL(k1_query_frames, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, tab,
-                                  D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len,
-                                  k1_src_of(D.as<const PackDesc>(), n));
-        else hipLaunchKernelGGL(k1_query_desc, dim3(1), dim3(64), 0, ctx->stream, 0u, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                                D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len);
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1Q_PADDED].as<const uint32_t>(), n, W[K1Q_COUNT].as<const uint32_t>(), upper, ctx->q, W[K1Q_PACK_SCAN], W[K1Q_PACK_TMP], pin_sum));
-        // an event of its own: whoever waits for the query side must not wait for what was queued behind it (pep_search queues the reference side next)
-        ctx->k1q_event_set = false;
-        if (ctx->k1q_event.ensure(pep_wait_event_flags()))
-            ctx->k1q_event_set = hipEventRecord(ctx->k1q_event, ctx->stream) == hipSuccess;
-    }
-    if (phase == 1) return PEP_OK;
-    if (ctx->k1q_event_set) PEP_HIP(ctx, pep_event_wait(ctx->k1q_event));
-    else PEP_HIP(ctx, pep_stream_wait(ctx));
-    ctx->k1q_event_set = false;
-    PEP_TRY(take_summary(ctx, ctx->pin_k1q.p, ctx->q));
-    // the lengths are here already (k1_query_desc wrote them into the pinned buffer); q_meta and h_off wait for pep_k1_host_tables_q
-    const uint32_t *pin_len = reinterpret_cast<const uint32_t *>(ctx->pin_k1q.p + sizeof(K1Summary));
-    ctx->q.h_len.assign(pin_len, pin_len + n);
-    ctx->q_tables_lazy = true;
+    PEP_TRY(upload_codon_table(ctx));
+    DevBuf *W = ctx->ws;
+    DevBuf &D = ctx->d_k1_desc_q;              // the descriptors stay on the device (a buffer of their own): fetched when somebody asks for the host tables
+    PEP_TRY(dev_reserve(ctx, D, (2 * (size_t)n + 4) * sizeof(PackDesc)));      // + the summary and the source records behind the descriptors
+    PEP_TRY(pin_reserve(ctx, ctx->pin_k1q, sizeof(K1Summary) + ((size_t)n + 1) * 4));
+    K1Summary *pin_sum = reinterpret_cast<K1Summary *>(ctx->pin_k1q.p);
+    uint32_t *pin_len = reinterpret_cast<uint32_t *>(ctx->pin_k1q.p + sizeof(K1Summary));
+    PEP_TRY(dev_reserve(ctx, W[K1Q_PADDED], ((size_t)n + 1) * 4));
+    PEP_TRY(dev_reserve(ctx, W[K1Q_COUNT], 16));
+    const uint64_t upper = 2 * PEP_END_PAD + (nt.total + 2 * (uint64_t)n) / 3 + (uint64_t)n * (16 + PEP_SEQ_GAP);
+    PEP_TRY(reserve_packed(ctx, ctx->q, n, upper));
+    if (n) hipLaunchKernelGGL(k1_query_frames, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, tab,
+                              D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len,
+                              k1_src_of(D.as<const PackDesc>(), n));
+    else hipLaunchKernelGGL(k1_query_desc, dim3(1), dim3(64), 0, ctx->stream, 0u, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                            D.as<PackDesc>(), W[K1Q_PADDED].as<uint32_t>(), ctx->q.len.as<uint32_t>(), W[K1Q_COUNT].as<uint32_t>(), reinterpret_cast<K1Summary *>(D.as<PackDesc>() + n), pin_len);
+    PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1Q_PADDED].as<const uint32_t>(), n, W[K1Q_COUNT].as<const uint32_t>(), ctx->q, pin_sum));
+    // an event of its own: whoever waits for the query side must not wait for what was queued behind it (pep_search queues the reference side next)
+    if (!ctx->k1q_event.ensure(pep_wait_event_flags())) return pep_fail(ctx, PEP_ERR_HIP, "hipEventCreate failed");
+    PEP_HIP(ctx, hipEventRecord(ctx->k1q_event, ctx->stream));
     return PEP_OK;
 }
 
-// the per-sequence host tables of both sides (meta records, offsets, lengths) from the descriptors their last K1 downloaded
-int pep_k1_host_tables(pep_ctx *ctx)
+int pep_k1_query_take(pep_ctx *ctx)
 {
-    if (ctx->t_tables_lazy) {
-        const uint32_t n = ctx->t.n;
-        std::vector<PackDesc> fetched((size_t)n + 1);
-        if (n) { PEP_TRY(pep_d2h_queue(ctx, fetched.data(), ctx->d_k1_desc_t.p, (size_t)n * sizeof(PackDesc))); PEP_HIP(ctx, pep_stream_wait(ctx)); pep_d2h_finish(ctx); }
-        const PackDesc *desc = fetched.data();
-        ctx->t_meta.resize(n);
-        for (uint32_t i = 0; i < n; ++i) ctx->t_meta[i] = pep_target_meta{desc[i].seq, desc[i].frame, desc[i].aa_off, desc[i].len};
-        finish_layout(desc, n, ctx->t);
-        ctx->t_tables_lazy = false;
-    }
-    return pep_k1_host_tables_q(ctx);
+    PEP_TRY(k1_take(ctx, ctx->k1q_event, ctx->pin_k1q.p, ctx->q));
+    // the lengths are here already (k1_query_frames wrote them into the pinned buffer); q_meta and h_off wait for pep_k1_host_tables
+    const uint32_t *pin_len = reinterpret_cast<const uint32_t *>(ctx->pin_k1q.p + sizeof(K1Summary));
+    ctx->q.h_len.assign(pin_len, pin_len + ctx->q_nt.n);
+    return PEP_OK;
 }
 
-int pep_k1_host_tables_q(pep_ctx *ctx)
+// the per-sequence host tables of one side (meta records, offsets, lengths) from the descriptors its last K1 left on the device; the other side's are not touched
+int pep_k1_host_tables(pep_ctx *ctx, PepSide side)
 {
-    if (ctx->q_tables_lazy) {
+    if (ctx->side[side].tables_built) return PEP_OK;
+    SeqSet &set = pep_set_of(ctx, side);
+    const DevBuf &D = side == PEP_SIDE_Q ? ctx->d_k1_desc_q : ctx->d_k1_desc_t;
+    const uint32_t n = set.n;
+    std::vector<PackDesc> fetched((size_t)n + 1);
+    if (n) { PEP_TRY(pep_d2h_queue(ctx, fetched.data(), D.p, (size_t)n * sizeof(PackDesc))); PEP_HIP(ctx, pep_stream_wait(ctx)); pep_d2h_finish(ctx); }
+    const PackDesc *desc = fetched.data();
+    if (side == PEP_SIDE_Q) {
         const NtSet &nt = ctx->q_nt;
-        const uint32_t n = ctx->q.n;
-        std::vector<PackDesc> fetched((size_t)n + 1);
-        if (n) { PEP_TRY(pep_d2h_queue(ctx, fetched.data(), ctx->d_k1_desc_q.p, (size_t)n * sizeof(PackDesc))); PEP_HIP(ctx, pep_stream_wait(ctx)); pep_d2h_finish(ctx); }
-        const PackDesc *desc = fetched.data();
         ctx->q_meta.resize(n);
         for (uint32_t i = 0; i < n; ++i) ctx->q_meta[i] = pep_query_meta{i, desc[i].frame, desc[i].len, (uint32_t)(nt.h_off[i + 1] - nt.h_off[i])};
-        finish_layout(desc, n, ctx->q);
-        ctx->q_tables_lazy = false;
+    } else {
+        ctx->t_meta.resize(n);
+        for (uint32_t i = 0; i < n; ++i) ctx->t_meta[i] = pep_target_meta{desc[i].seq, desc[i].frame, desc[i].aa_off, desc[i].len};
     }
+    set.h_off.resize((size_t)n + 1);            // the host mirrors of the layout (same arithmetic as k1_offsets)
+    set.h_len.resize(n);
+    uint64_t pos = PEP_END_PAD;
+    for (uint32_t i = 0; i < n; ++i) {
+        set.h_off[i] = (uint32_t)pos;
+        set.h_len[i] = desc[i].len;
+        pos += ((uint64_t)desc[i].len + 15) / 16 * 16 + PEP_SEQ_GAP;
+    }
+    set.h_off[n] = (uint32_t)(pos + PEP_END_PAD);
+    side_tables_built(ctx, side);
     return PEP_OK;
 }
 
-int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
+int pep_k1_ref_queue(pep_ctx *ctx, int frames, int gtable)
 {
     const NtSet &nt = ctx->r_nt;
     const int tab = gtable == 4 ? 1 : 0;
-    if (phase == 2) return k1_ref_finish(ctx);
     PEP_TRY(upload_codon_table(ctx));
     const uint32_t n = nt.n;
     const int nf = frames == 3 ? 3 : 6;
@@ -814,7 +781,11 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
         // Depends on the input lengths only: computed and uploaded once per reference set.
         std::vector<uint64_t> &base = ctx->k1_base;
         base.assign(nw + 1, 0);
-        uint64_t upper = 2 * PEP_END_PAD;
+        uint64_t upper = 2 * PEP_END_PAD, mask_words = 0;
+        // ... and the long frames' tables (k1_stop_mask / k1_ref_chunks_mask / k1_ref_desc_fill): a function of the lengths as well
+        std::vector<K1Seg> segs, tiles;                 // tiles of 4 096 characters of the stop mask / of 256 chunk slots
+        std::vector<K1Long> longs;
+        std::vector<uint32_t> long_of_w;
         for (uint32_t g = 0; g < n; ++g) {
             const uint64_t L = nt.h_off[g + 1] - nt.h_off[g];
             for (int f = 1; f <= nf; ++f) {
@@ -823,21 +794,6 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
                 const uint64_t slots_w = (na + 1) / 1001 + 1;
                 base[(uint64_t)g * nf + f] = base[(uint64_t)g * nf + f - 1] + slots_w;
                 upper += na + slots_w * (15 + PEP_SEQ_GAP);
-            }
-        }
-        ctx->k1_upper = upper;
-        PEP_TRY(dev_reserve(ctx, ctx->d_k1_base, (nw + 1) * 8));
-        PEP_HIP(ctx, hipMemcpy(ctx->d_k1_base.p, base.data(), (nw + 1) * 8, hipMemcpyHostToDevice));
-        // the long frames' tables (k1_stop_mask / k1_ref_chunks_mask / k1_ref_desc_fill): a function of the lengths as well
-        std::vector<K1Seg> segs, tiles;                 // tiles of 4 096 characters of the stop mask / of 256 chunk slots
-        std::vector<K1Long> longs;
-        std::vector<uint32_t> long_of_w;
-        uint64_t mask_words = 0;
-        for (uint32_t g = 0; g < n; ++g) {
-            const uint64_t L = nt.h_off[g + 1] - nt.h_off[g];
-            for (int f = 1; f <= nf; ++f) {
-                const uint64_t shift = (uint64_t)(f <= 3 ? f - 1 : f - 4);
-                const uint64_t na = L > shift ? (L - shift + 2) / 3 : 0;
                 if (na + 1 <= (uint64_t)K1_LONG) continue;
                 const uint32_t w = g * (uint32_t)nf + (uint32_t)(f - 1);
                 if (long_of_w.empty()) long_of_w.assign(nw, 0u);
@@ -849,6 +805,9 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
                 for (uint32_t k = 0, n_tiles = (uint32_t)(((na + 1) / 1001 + 1 + 255) / 256); k < n_tiles; ++k) tiles.push_back(K1Seg{w, k});
             }
         }
+        ctx->k1_upper = upper;
+        PEP_TRY(dev_reserve(ctx, ctx->d_k1_base, (nw + 1) * 8));
+        PEP_HIP(ctx, hipMemcpy(ctx->d_k1_base.p, base.data(), (nw + 1) * 8, hipMemcpyHostToDevice));
         ctx->k1_n_seg = (uint32_t)segs.size();
         ctx->k1_n_long = (uint32_t)longs.size();
         if (!segs.empty()) {
@@ -906,21 +865,20 @@ int pep_k1_ref(pep_ctx *ctx, int frames, int gtable, int phase)
                                    W[K1R_CHUNK_OFF].as<const uint32_t>(), W[K1R_CHUNK_LEN].as<const uint32_t>(), W[K1R_FIRST].as<const uint32_t>(), K1_FILL_FROM, D.as<PackDesc>(), W[K1R_PADDED].as<uint32_t>(),
                                    ctx->t.len.as<uint32_t>(), nt.off.as<const uint64_t>(), k1_src_of(D.as<const PackDesc>(), (uint32_t)slots));
         }
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), (uint32_t)slots, W[K1R_FIRST].as<const uint32_t>() + nw, upper, ctx->t,
-                                W[K1R_PACK_SCAN], W[K1R_PACK_TMP], pin_sum));
+        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), (uint32_t)slots, W[K1R_FIRST].as<const uint32_t>() + nw, ctx->t, pin_sum));
     } else {
         PEP_HIP(ctx, hipMemsetAsync(W[K1R_FIRST].p, 0, 8, ctx->stream));
         PEP_HIP(ctx, hipMemsetAsync(W[K1R_PADDED].p, 0, 4, ctx->stream));
         PEP_HIP(ctx, hipMemsetAsync(D.p, 0, 3 * sizeof(PackDesc), ctx->stream));               // (the summary's accumulators)
-        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), 0, W[K1R_FIRST].as<const uint32_t>(), upper, ctx->t, W[K1R_PACK_SCAN], W[K1R_PACK_TMP], pin_sum));
+        PEP_TRY(layout_and_pack(ctx, nt, tab, D.as<const PackDesc>(), W[K1R_PADDED].as<const uint32_t>(), 0, W[K1R_FIRST].as<const uint32_t>(), ctx->t, pin_sum));
     }
     // the summary has been written into pinned memory by k1_pack; an event marks the point of the stream where it is there
-    ctx->k1_desc_cap = (uint32_t)slots;
     if (!ctx->k1_event.ensure(pep_wait_event_flags())) return pep_fail(ctx, PEP_ERR_HIP, "hipEventCreate failed");
     PEP_HIP(ctx, hipEventRecord(ctx->k1_event, ctx->stream));
-    if (phase == 1) return PEP_OK;
-    return k1_ref_finish(ctx);
+    return PEP_OK;
 }
+
+int pep_k1_ref_take(pep_ctx *ctx) { return k1_take(ctx, ctx->k1_event, ctx->pin_k1.p, ctx->t); }     // (t_meta, h_off, h_len: pep_k1_host_tables, when somebody needs them)
 
 // ---- self-search (round 6): PEPPAN's hot call searches a gene set against itself (-r CL -q CL, PEPPAN.py:229-230).  Frame 1 of reference gene g then IS protein
 // query g - the same residues at the same offsets - and 57 % of the raw seed hits of the 10 000-gene search are a gene against itself on diagonal 0
@@ -932,8 +890,8 @@ int pep_self_map(pep_ctx *ctx, int *on)
 {
     *on = 0;
     const SeqSet &Q = ctx->q, &T = ctx->t;
-    if (!ctx->q_from_nt || !ctx->t_from_nt || Q.n == 0 || T.n == 0) return PEP_OK;
-    if (ctx->resid_from_nucl) {
+    if (!ctx->side[PEP_SIDE_Q].from_nt() || !ctx->side[PEP_SIDE_T].from_nt() || Q.n == 0 || T.n == 0) return PEP_OK;
+    if (ctx->holds == SetsHold::BaseCodes) {
         // the nucleotide tool's sets (pep_use_nt_as_residues): the forward strand of reference sequence g; it must have the query's length exactly - the matcher judges the
         // bases next to a look-up word by the target's side alone where the hit is a gene against itself
         if (!ctx->nucl_valid || !ctx->nucl_t.d_first.p || ctx->nucl_t.n_first == 0) return PEP_OK;
@@ -956,7 +914,7 @@ int pep_self_map(pep_ctx *ctx, int *on)
 // themselves - offsets, lengths, descriptors, the host mirrors - depends on the uploaded nucleotide sets (and the target groups) only and is kept
 // (NuclSide) between calls: PEPPAN's hot call runs the nucleotide tool and the translated tool in turn on the same sets, and K1 overwrites the packed
 // sets in between.  A repeat costs four small device-to-device copies and the two pack kernels, queued without a wait.
-static int nucl_build(pep_ctx *ctx, const NtSet &nt, const std::vector<NuclDesc> &order, uint32_t max_n, SeqSet &out, pep_ctx::NuclSide &keep)
+static int nucl_build(pep_ctx *ctx, const NtSet &nt, const std::vector<NuclDesc> &order, uint32_t max_n, pep_ctx::NuclSide &keep)
 {
     const uint32_t n = (uint32_t)order.size();
     if (n > max_n) return pep_fail(ctx, PEP_ERR_LIMIT, "too many sequences");
@@ -982,7 +940,6 @@ static int nucl_build(pep_ctx *ctx, const NtSet &nt, const std::vector<NuclDesc>
     if (n) PEP_HIP(ctx, hipMemcpyAsync(keep.d_len.p, keep.h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (n) PEP_HIP(ctx, hipMemcpyAsync(keep.d_desc.p, order.data(), (size_t)n * sizeof(NuclDesc), hipMemcpyHostToDevice, ctx->stream));
     PEP_HIP(ctx, hipStreamSynchronize(ctx->stream));           // (the descriptor vector is the caller's; once per pair of uploads)
-    (void)out;
     return PEP_OK;
 }
 
@@ -1010,7 +967,7 @@ int pep_nucl_sets(pep_ctx *ctx, int strands)
         ctx->nucl_valid = false;
         std::vector<NuclDesc> qo(ctx->q_nt.n), to;
         for (uint32_t i = 0; i < ctx->q_nt.n; ++i) qo[i] = NuclDesc{i, 0u};
-        PEP_TRY(nucl_build(ctx, ctx->q_nt, qo, PEP_MAX_QUERIES, ctx->q, ctx->nucl_q));
+        PEP_TRY(nucl_build(ctx, ctx->q_nt, qo, PEP_MAX_QUERIES, ctx->nucl_q));
         // targets: per reference set (pep_set_target_groups; one set otherwise) all forward strands, then all reverse complements
         const uint32_t nr = ctx->r_nt.n;
         const bool grouped = ctx->group_of_seq.size() == nr && nr > 0;
@@ -1022,7 +979,7 @@ int pep_nucl_sets(pep_ctx *ctx, int strands)
                 for (uint32_t i = a; i < b; ++i) to.push_back(NuclDesc{i, (uint32_t)rev});
             a = b;
         }
-        PEP_TRY(nucl_build(ctx, ctx->r_nt, to, PEP_MAX_TARGETS, ctx->t, ctx->nucl_t));
+        PEP_TRY(nucl_build(ctx, ctx->r_nt, to, PEP_MAX_TARGETS, ctx->nucl_t));
         {
             // per reference sequence its forward strand among the targets: where a self-search finds the target that repeats query g (seeds.hip: self_prepare)
             std::vector<uint32_t> first(nr, PEP_SELF_NONE);
@@ -1040,8 +997,6 @@ int pep_nucl_sets(pep_ctx *ctx, int strands)
     }
     PEP_TRY(nucl_apply(ctx, ctx->q_nt, ctx->nucl_q, ctx->q));
     PEP_TRY(nucl_apply(ctx, ctx->r_nt, ctx->nucl_t, ctx->t));
-    ctx->q_tables_lazy = false;
-    ctx->t_tables_lazy = false;
     ctx->q_meta = ctx->nucl_q.q_meta;
     ctx->t_meta = ctx->nucl_t.t_meta;
     return PEP_OK;
