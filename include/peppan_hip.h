@@ -64,6 +64,7 @@ extern "C" {
  * 19 took in the sections of K18, K19 and K20, which had headers and version numbers of their own (pep_synteny_version, pep_genestruct_version and
  * pep_parser_version are gone), and replaced the six pep_*_times read-outs of K15 - K20 by pep_call_times. */
 #define PEP_ABI_VERSION 19
+/* K21 (neighbour-joining trees), additive under ABI 19, is declared in a header of its own for now: include/peppan_hip_tree.h */
 
 #define PEP_OK 0
 #define PEP_ERR_HIP (-1)       /* a HIP runtime call failed */

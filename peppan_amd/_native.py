@@ -114,6 +114,17 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
+# ... and of include/peppan_hip_tree.h (K21), a table of its own for as long as it is a header of its own: tests/test_abi.py holds SIGNATURES and EXPORTS to
+# the prototypes of peppan_hip.h alone, tests/test_njtree_host.py holds this one to the second header
+TREE_SIGNATURES = {
+    'pep_kimura_pairs': (I, P, P, P, P, U64, U32, P, P, P, P, U64, P),
+    'pep_nj_trees': (I, P, P, P, P, U32, P, P, P, P),
+    'pep_nj_trees_check': (I, P, U32, P, P, P, U64),
+}
+NJ_BLOCK_LEAVES = 256                    # PEP_NJ_BLOCK_LEAVES: trees up to this size are joined by one workgroup, larger ones by a chain of launches
+NJ_MAX_LEAVES = 8192                     # PEP_NJ_MAX_LEAVES: leaves of one tree
+NJ_MAX_BYTES = 1 << 30                   # PEP_NJ_MAX_BYTES: distance matrices of one pep_nj_trees call, pair counts of one pep_kimura_pairs call
+
 # limits and codes of the header's K18, K19 and K20 sections; the host test of each kernel holds them to its #defines
 SYNTENY_MAX_PAIRS = 1 << 27              # PEP_SYNTENY_MAX_PAIRS: pairs of one pep_synteny_pairs call
 SYNTENY_MAX_COUNTERS = 1 << 26           # PEP_SYNTENY_MAX_COUNTERS: rank counters of one call, n * (6 * longest list + 14) per group of two members and more
@@ -220,7 +231,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in SIGNATURES.items():
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -622,6 +633,16 @@ def profile_pairs_check(n, n_genes):
     if not (0 <= int(n) < 1 << 32 and 0 <= int(n_genes) < 1 << 64):
         raise ValueError('profile_pairs: sizes outside their columns')
     _check_only('pep_profile_pairs_check', int(n), int(n_genes))
+
+
+def nj_trees_check(n_leaves, dist_off, out_off):
+    """the host checks of pep_nj_trees that read no distance (no context, no device): PepError with the library's code and text, else None.  dist_off and out_off
+    have one entry more than n_leaves: the lengths of the arrays"""
+    n = np.ascontiguousarray(n_leaves, dtype=np.uint32).reshape(-1)
+    dist_off, out_off = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (dist_off, out_off))
+    if len(dist_off) != len(n) + 1 or len(out_off) != len(n) + 1:
+        raise ValueError('nj_trees: dist_off and out_off need one entry more than n_leaves')
+    _check_only('pep_nj_trees_check', _ptr(_some(n)), len(n), _ptr(dist_off), _ptr(out_off))
 
 
 def codon_tables(table_id=11):
@@ -1212,6 +1233,7 @@ class Context(object):
         self._nt_match_on, self.last_nt_match = False, None
         self._grouping, self.labels = 0, None           # set_grouping: K10 as the tail of every search
         self._verdict_stats = [np.zeros(4), 0]          # kernel times and bytes to the host, summed over the library calls of the newest group_verdicts
+        self.kimura_ms = self.nj_ms = (0., 0.)          # kernel times summed over the library calls of the newest kimura_pairs / nj_trees
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1710,6 +1732,65 @@ class Context(object):
         calls sent to the device; bytes it sent to the host)"""
         t = self._times(CALL_PARSER)
         return float(t.ms[0]), float(t.ms[1]), int(t.bytes_to_device), int(t.bytes_to_host)
+
+    # ---- K21
+    def kimura_pairs(self, packed, row_off, row_len, groups, out_budget=1 << 30):
+        """the three pair counts of Kimura's distance, which `rapidnj -i fa` computes (PEPPAN.py:19, 409-417).  Rows and groups as for allele_diff.
+        -> per group int32[n (n - 1) / 2, 3]: (comparable columns, transitions, transversions) of every pair a < b in the row-major order of allele_diff's
+        packed triangle.  A batch beyond `out_budget` bytes of counts (at most the library's PEP_NJ_MAX_BYTES) or the library's budget of bit planes goes to
+        the library in several calls.  The kernel times, summed over the library calls: self.kimura_ms (bit planes, pairs; zeros unless set_timing(2))."""
+        out_budget = min(int(out_budget), NJ_MAX_BYTES)
+        packed, row_off, row_len, groups = _group_inputs('kimura_pairs', packed, row_off, row_len, groups)
+        n = np.array([len(g) for g in groups], dtype=np.int64)
+        need = 3 * (n * (n - 1) // 2)                                 # int32 values per group
+        results, self.kimura_ms = [], (0., 0.)
+        for lo, hi, whole in _plan_batch('kimura_pairs', 'pair counts', 4 * need, row_len, groups, out_budget):
+            pk, ro, rl, gr = packed, row_off, row_len, groups[lo:hi]
+            if not whole and len(gr):
+                pk, ro, rl, gr = _rows_of_groups(pk, ro, rl, gr, n[lo:hi])
+            n_rows = len(rl)
+            pk, rl, grp_off, grp_rows = _group_tables(pk, rl, gr)
+            out_off = np.concatenate([[0], np.cumsum(need[lo:hi])]).astype(np.uint64)
+            out = np.empty(max(int(out_off[-1]), 1), dtype=np.int32)
+            ms = np.zeros(4)
+            self._call('pep_kimura_pairs', _ptr(pk), _ptr(ro), _ptr(rl), n_rows, len(gr), _ptr(grp_off), _ptr(grp_rows),
+                       _ptr(out), _ptr(out_off), int(out_off[-1]), _ptr(ms))
+            self.kimura_ms = (self.kimura_ms[0] + float(ms[0]), self.kimura_ms[1] + float(ms[1]))
+            results += [out[int(out_off[g]):int(out_off[g + 1])].reshape(-1, 3) for g in range(len(gr))]
+        return results
+
+    def nj_trees(self, matrices):
+        """neighbour joining (what rapidnj does for PEPPAN.py:416 and PEPPAN_parser.py:168) over a list of square float64 distance matrices, of which the
+        entries with row < column are read.  -> per matrix (node uint32[2 n - 3], length float64[2 n - 3]) as include/peppan_hip_tree.h states them: for
+        every join the two joined node ids and their branch lengths, then the last three nodes; two entries for n = 2.  Batches beyond the library's
+        PEP_NJ_MAX_BYTES of matrices go to it in several calls.  The kernel times, summed over the library calls: self.nj_ms (one-workgroup kernels,
+        launch chains; zeros unless set_timing(2))."""
+        mats = [np.ascontiguousarray(m, dtype=np.float64) for m in matrices]
+        for t, m in enumerate(mats):
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError('nj_trees: matrix %d is %s, not square' % (t, m.shape))
+        sizes = [m.size * 8 for m in mats]
+        self.nj_ms = (0., 0.)
+        results, lo = [], 0
+        while lo < len(mats):
+            hi, total = lo + 1, sizes[lo]                             # (a matrix beyond the budget goes alone: the library refuses it in its words)
+            while hi < len(mats) and total + sizes[hi] <= NJ_MAX_BYTES:
+                total += sizes[hi]
+                hi += 1
+            results += self._nj_trees_call(mats[lo:hi])
+            lo = hi
+        return results
+
+    def _nj_trees_call(self, mats):
+        n = np.array([m.shape[0] for m in mats], dtype=np.uint32)
+        dist_off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)]).astype(np.uint64)
+        out_off = np.concatenate([[0], np.cumsum(np.where(n == 2, 2, 2 * n.astype(np.int64) - 3))]).astype(np.uint64)
+        _check_only('pep_nj_trees_check', _ptr(n), len(n), _ptr(dist_off), _ptr(out_off))       # (before the copy below: a tree of one leaf would lay the offsets out wrongly)
+        dist = np.concatenate([m.reshape(-1) for m in mats])
+        node, length, ms = np.zeros(int(out_off[-1]), np.uint32), np.zeros(int(out_off[-1]), np.float64), np.zeros(4)
+        self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off), _ptr(ms))
+        self.nj_ms = (self.nj_ms[0] + float(ms[0]), self.nj_ms[1] + float(ms[1]))
+        return [(node[int(a):int(b)], length[int(a):int(b)]) for a, b in zip(out_off[:-1], out_off[1:])]
 
     # ---- K13
     def sha1(self, seqs):

@@ -1,5 +1,6 @@
 // The 64 x 64 tile of pair counts over K15's bit planes, shared by allelediff.hip (K15: stores every pair) and divergence.hip (K16: reduces
-// the pairs of a tile to one flag).  See allelediff.hip for the layout of the planes.
+// the pairs of a tile to one flag); with SPLIT also the transitions among the mismatches, for njtree.hip (K21: Kimura's pair counts).  See allelediff.hip
+// for the layout of the planes.
 #pragma once
 #include "common.h"
 
@@ -11,10 +12,12 @@ struct DiffTile { uint32_t g, ti, tj, kind; };      // kind 0: pairs a < b of ti
 
 // Called by all 256 threads of a workgroup.  idx: the group's row indices (n of them, rows of `words` words per plane).  Thread (tx, ty) =
 // (tid & 15, tid >> 4) gets mis / cmp of rows A = ti * 64 + ty * 4 + i (kind 1: row 0 for ty * 4 + i == 0, row n - 1 for == 1, none else)
-// against rows B = tj * 64 + tx + 16 * j; rows past n count as all zero.
-__device__ __forceinline__ void k15_tile_counts(const uint32_t *__restrict__ idx, uint32_t n, uint32_t words, const DiffTile T,
-                                                const uint64_t *__restrict__ plane_off, const unsigned long long *__restrict__ planes,
-                                                uint32_t (&mis)[4][4], uint32_t (&cmp)[4][4])
+// against rows B = tj * 64 + tx + 16 * j; rows past n count as all zero.  SPLIT: ts = the mismatches whose codes differ in plane B1 alone - codes are digit - 1, so
+// A = 0, C = 1, G = 2, T = 3 and those are A <-> G and C <-> T; not SPLIT: ts is left alone.
+template <bool SPLIT>
+__device__ __forceinline__ void k15_tile_counts_of(const uint32_t *__restrict__ idx, uint32_t n, uint32_t words, const DiffTile T,
+                                                   const uint64_t *__restrict__ plane_off, const unsigned long long *__restrict__ planes,
+                                                   uint32_t (&mis)[4][4], uint32_t (&cmp)[4][4], uint32_t (&ts)[4][4])
 {
     // [plane * KW + word][row]: the threads of a wavefront read 16 consecutive B rows (no bank conflict) and 4 A rows (broadcast)
     __shared__ unsigned long long sA[3 * K15_KW][K15_TILE], sB[3 * K15_KW][K15_TILE];
@@ -31,7 +34,10 @@ __device__ __forceinline__ void k15_tile_counts(const uint32_t *__restrict__ idx
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mis[i][j] = cmp[i][j] = 0;
+        for (int j = 0; j < 4; ++j) {
+            mis[i][j] = cmp[i][j] = 0;
+            if constexpr (SPLIT) ts[i][j] = 0;
+        }
     for (uint32_t w0 = 0; w0 < words; w0 += K15_KW) {
         __syncthreads();                                            // the previous step's words are consumed (first step: offA / offB are written)
         for (uint32_t e = tid; e < 2 * 3 * K15_KW * K15_TILE; e += 256) {
@@ -57,9 +63,17 @@ __device__ __forceinline__ void k15_tile_counts(const uint32_t *__restrict__ idx
                     const unsigned long long c = av[i] & bv[j];
                     cmp[i][j] += (uint32_t)__popcll(c);
                     mis[i][j] += (uint32_t)__popcll(c & ((a0[i] ^ b0[j]) | (a1[i] ^ b1[j])));
+                    if constexpr (SPLIT) ts[i][j] += (uint32_t)__popcll(c & ~(a0[i] ^ b0[j]) & (a1[i] ^ b1[j]));
                 }
         }
     }
+}
+
+__device__ __forceinline__ void k15_tile_counts(const uint32_t *__restrict__ idx, uint32_t n, uint32_t words, const DiffTile T,
+                                                const uint64_t *__restrict__ plane_off, const unsigned long long *__restrict__ planes,
+                                                uint32_t (&mis)[4][4], uint32_t (&cmp)[4][4])
+{
+    k15_tile_counts_of<false>(idx, n, words, T, plane_off, planes, mis, cmp, mis);
 }
 
 // allelediff.hip: queues K15's bit-plane kernel for n_rows packed rows (d_bad_row: the smallest row holding a byte above 124, untouched otherwise)

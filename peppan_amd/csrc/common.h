@@ -317,6 +317,7 @@ struct pep_ctx {
     DevBuf k18[18];                          // grow-only: its tables, counters and the two lists (the slots: synteny.hip)
     DevBuf k19[5];                           // grow-only, pep_gene_structure: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
     DevBuf k20[6];                           // grow-only, pep_rarefaction_curves and pep_profile_pairs: bit rows, orders and curves; profiles and the two pair matrices (the slots: parser.hip)
+    DevBuf k21[5];                           // grow-only, pep_nj_trees: the matrices, the tree records, the two outputs and the state of a launch chain (the slots: njtree.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose

@@ -4,12 +4,13 @@
     group_differences           PEPPAN.py:330-333 + :346 + :370 for a whole `to_run` list (:624-626) in one GPU batch
     group_verdicts              PEPPAN.py:335-392: what filt_per_group decides from those differences, decided on the GPU (K16); per-pair data
                                 comes back only for the groups that go on to the tree test
+    group_trees                 PEPPAN.py:393-417: the neighbour-joining tree text of those groups (K21, njtree.py)
     gd_table, distances_from_diff, incompatible_of   the host halves of it (the exp() per genome pair; :371-380; :400-406)
 
 Both counts are sums over columns, so the rows never leave the base-5 packing of the .seq store (mapbsn.encodeSeq): K15
 (csrc/allelediff.hip, Context.allele_diff) turns the packed bytes into bit planes and counts with population counts.  The float layer
-of filt_per_group up to the decision to build a tree is K16 (csrc/divergence.hip, Context.group_verdicts); the tree itself and its cutting
-are not here: see DESIGN.md section 8.  There is no CPU fallback.
+of filt_per_group up to the decision to build a tree is K16 (csrc/divergence.hip, Context.group_verdicts); the tree text is K21 (njtree.py);
+the cutting of the tree is not here: see DESIGN.md section 8.  There is no CPU fallback.
 The drop-ins and group_differences share one cached context per process and device; close() releases it.
 """
 import collections
@@ -21,7 +22,7 @@ from . import _native as N
 from .mapbsn import MapBsn
 
 __all__ = ['compare_seq', 'compare_seqX', 'group_differences', 'iter_group_differences', 'pack_rows', 'close',
-           'group_verdicts', 'gd_table', 'distances_from_diff', 'incompatible_of', 'GdTable', 'GroupVerdict']
+           'group_verdicts', 'group_trees', 'gd_table', 'distances_from_diff', 'incompatible_of', 'GdTable', 'GroupVerdict']
 
 _CODE = np.full(256, 255, dtype=np.uint8)
 _CODE[[0, 65, 67, 71, 84]] = (0, 1, 2, 3, 4)
@@ -234,6 +235,12 @@ def incompatible_of(distances, groups):
             g2 = groups[i2]
             incompatible[g2[0], g1[0], :] = incompatible[g1[0], g2[0], :] = np.sum(distances[g1][:, g2, :], (0, 1))
     return incompatible, not bool(np.all(incompatible[:, :, 0] <= incompatible[:, :, 1]))
+
+
+def group_trees(seq_store, to_run_groups, verdicts, device=None, digits=5):
+    """PEPPAN.py:393-417 behind group_verdicts: the tree text of every group that goes on to the tree test, by K21 (njtree.gene_trees, which see)"""
+    from .njtree import gene_trees
+    return gene_trees(seq_store, to_run_groups, verdicts, device, digits)
 
 
 class GroupVerdict(object):

@@ -5,7 +5,7 @@ beside PEPPAN): the rarefaction curves of option -c and the core gene allelic di
     writeCurve             PEPPAN_parser.py:63-115    <prefix>_content.curve, byte for byte
     rarefaction_curves     its loop, :74-80           the `curves` array alone
     getDistance            PEPPAN_parser.py:172-179   drop-in, float64 [n, n]
-    writeCGAV              PEPPAN_parser.py:145-170   <prefix>_CGAV.profile and <prefix>_CGAV.dist, byte for byte
+    writeCGAV              PEPPAN_parser.py:145-170   <prefix>_CGAV.profile and <prefix>_CGAV.dist, byte for byte; <prefix>_CGAV.nwk by K21 (njtree.py) without rapidnj
 
 The reference walks 1 000 random genome orders and sums a counter per gene twice per step, and compares every pair of profiles with three numpy passes -
 minutes of Python at 2 000 genomes.  K20 (csrc/parser.hip) does both as integer kernels: Context.rarefaction_curves walks every order over bit rows
@@ -24,6 +24,7 @@ from collections import defaultdict
 import numpy as np
 
 from . import _native as N
+from . import njtree
 from .configure import logger, uopen
 from .orthofilter import _context, close
 
@@ -195,7 +196,8 @@ def dist_text(genomes, distances):
 
 
 def writeCGAV(prefix, ortho, pCore, device=None):
-    """PEPPAN_parser.py:145-170: writes <prefix>_CGAV.profile and <prefix>_CGAV.dist; <prefix>_CGAV.nwk only when rapidnj is installed"""
+    """PEPPAN_parser.py:145-170: writes <prefix>_CGAV.profile, <prefix>_CGAV.dist and <prefix>_CGAV.nwk - the tree by rapidnj when it is installed (:168), as the
+    reference makes it; else by K21 from the distances in memory (njtree.py: float64 where rapidnj computes in float32, the same five printed digits)"""
     genomes, genes, profiles = cgav_profiles(ortho, pCore)
     with open('{0}_CGAV.profile'.format(prefix), 'w') as fout:
         fout.write(profile_text(genomes, genes, profiles))
@@ -205,9 +207,12 @@ def writeCGAV(prefix, ortho, pCore, device=None):
     logger('Core gene allelic variation profile is saved in {0}_CGAV.profile'.format(prefix))
     rapidnj = shutil.which('rapidnj')
     if rapidnj is None:
-        logger('rapidnj is not installed: {0}_CGAV.nwk is skipped'.format(prefix))
-        return
-    tree = subprocess.run([rapidnj, '-i', 'pd', '{0}_CGAV.dist'.format(prefix)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True).stdout
+        if len(genomes) < 2:
+            logger('fewer than two genomes: {0}_CGAV.nwk is skipped'.format(prefix))
+            return
+        tree = njtree.newick(njtree.nj_trees([distances], device)[0], genomes) + '\n'
+    else:
+        tree = subprocess.run([rapidnj, '-i', 'pd', '{0}_CGAV.dist'.format(prefix)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True).stdout
     with open('{0}_CGAV.nwk'.format(prefix), 'w') as fout:
         fout.write(tree.replace("'", ''))
     logger('Core gene allelic variation tree is saved in {0}_CGAV.nwk'.format(prefix))
