@@ -121,6 +121,21 @@ TREE_SIGNATURES = {
     'pep_nj_trees': (I, P, P, P, P, U32, P, P, P, P),
     'pep_nj_trees_check': (I, P, U32, P, P, P, U64),
 }
+# ... and of include/peppan_hip_gdiff.h (K22), for the same reason; tests/test_globaldiff_host.py holds this one to the third header
+GDIFF_SIGNATURES = {
+    'pep_global_diff_walk': (I, P, U64, P, U64, P, P, U64, P, P, U64),
+    'pep_global_diff_walk_size': (I, P, P, P, P),
+    'pep_global_diff_walk_copy': (I, P, P, P, P),
+    'pep_global_diff_walk_free': (None, P),
+    'pep_global_diff': (I, P, P, U64, P, U64, U32, P, U64, P, P),
+    'pep_global_diff_copy': (I, P, U64, P, P, P, P, P),
+    'pep_global_diff_check': (I, P, U64, P, U64, U32, U64, P, U64),
+}
+GDIFF_MAX_GENOMES = 16384                # PEP_GDIFF_MAX_GENOMES: distinct genomes of one pep_global_diff call
+GDIFF_MAX_ITEMS = 1 << 32                # PEP_GDIFF_MAX_ITEMS: list-pair members of one call
+GDIFF_TABLE = 10050                      # PEP_GDIFF_TABLE: entries of the logarithm table, value codes 0 .. 10049
+GDIFF_CHUNK_ITEMS = 1 << 24              # PEP_GDIFF_CHUNK_ITEMS: items of one chunk when chunk_items is 0
+GDIFF_MAX_BYTES = 1 << 34                # PEP_GDIFF_MAX_BYTES: device workspace of one call
 NJ_BLOCK_LEAVES = 256                    # PEP_NJ_BLOCK_LEAVES: trees up to this size are joined by one workgroup, larger ones by a chain of launches
 NJ_MAX_LEAVES = 8192                     # PEP_NJ_MAX_LEAVES: leaves of one tree
 NJ_MAX_BYTES = 1 << 30                   # PEP_NJ_MAX_BYTES: distance matrices of one pep_nj_trees call, pair counts of one pep_kimura_pairs call
@@ -231,7 +246,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()):
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -643,6 +658,58 @@ def nj_trees_check(n_leaves, dist_off, out_off):
     if len(dist_off) != len(n) + 1 or len(out_off) != len(n) + 1:
         raise ValueError('nj_trees: dist_off and out_off need one entry more than n_leaves')
     _check_only('pep_nj_trees_check', _ptr(_some(n)), len(n), _ptr(dist_off), _ptr(out_off))
+
+
+def _gdiff_tables(events, arena):
+    """events and arena of a pep_global_diff / pep_global_diff_check call as the library's types; values that do not fit their column raise ValueError here"""
+    events = np.asarray(events)
+    if events.size == 0:
+        events = np.zeros((0, 6), dtype=np.int64)
+    if events.ndim != 2 or events.shape[1] != 6 or events.dtype.kind not in 'iu':
+        raise ValueError('global_diff: events is integer [n, 6]: a_off, a_len, b_off, b_len, value, drop_same')
+    arena = np.asarray(arena)
+    if arena.size and (arena.ndim != 1 or arena.dtype.kind not in 'iu'):
+        raise ValueError('global_diff: arena is a vector of genome ranks')
+    if arena.size and (int(arena.min()) < -(1 << 31) or int(arena.max()) >= 1 << 31):
+        raise ValueError('global_diff: arena holds values outside int32')
+    return np.ascontiguousarray(events, dtype=np.int64), np.ascontiguousarray(arena.reshape(-1), dtype=np.int32)
+
+
+def global_diff_check(events, arena, n_genomes, chunk_items=0):
+    """the host checks of pep_global_diff alone (no context, no device): PepError with the library's code and text, else None"""
+    events, arena = _gdiff_tables(events, arena)
+    _check_only('pep_global_diff_check', _ptr_or_null(events), len(events), _ptr_or_null(arena), len(arena), int(n_genomes), int(chunk_items))
+
+
+def global_diff_walk(clu, bsn, genes, genome_of):
+    """pep_global_diff_walk: the dictionary walk of get_global_difference (PEPPAN.py:1632-1659) over the selected rows -> (events int64[n, 6], arena int32[],
+    genomes int32[G]: the genome id of every rank).  clu / bsn: integer [n, 3] rows (r, q, value) in file order; genes ascending, genome_of their genomes.
+    No context, no device; PepError with the library's code and text (a gene that is not in the map, a value outside 0 .. 10049)."""
+    lib = load_library()
+    clu, bsn = (np.ascontiguousarray(np.asarray(t).reshape(-1, 3), dtype=np.int64) for t in (clu, bsn))
+    genes = np.ascontiguousarray(genes, dtype=np.int64).reshape(-1)
+    genome_of = np.asarray(genome_of).reshape(-1)
+    if len(genome_of) != len(genes):
+        raise ValueError('global_diff_walk: one genome per gene')
+    if len(genome_of) and (int(genome_of.min()) < -(1 << 31) or int(genome_of.max()) >= 1 << 31):
+        raise ValueError('global_diff_walk: genome ids outside int32')
+    genome_of = np.ascontiguousarray(genome_of, dtype=np.int32)
+    walk, msg = C.c_void_p(), C.create_string_buffer(512)
+    rc = lib.pep_global_diff_walk(_ptr_or_null(clu), len(clu), _ptr_or_null(bsn), len(bsn), _ptr_or_null(genes), _ptr_or_null(genome_of), len(genes),
+                                  C.byref(walk), msg, len(msg))
+    if rc != 0:
+        raise PepError('pep_global_diff_walk failed (%d): %s' % (rc, msg.value.decode()))
+    try:
+        n_events, arena_len, n_genomes = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        if lib.pep_global_diff_walk_size(walk, C.byref(n_events), C.byref(arena_len), C.byref(n_genomes)) != 0:
+            raise PepError('pep_global_diff_walk_size failed')
+        events, arena = np.zeros((n_events.value, 6), dtype=np.int64), np.zeros(arena_len.value, dtype=np.int32)
+        genomes = np.zeros(n_genomes.value, dtype=np.int32)
+        if lib.pep_global_diff_walk_copy(walk, _ptr_or_null(events), _ptr_or_null(arena), _ptr_or_null(genomes)) != 0:
+            raise PepError('pep_global_diff_walk_copy failed')
+    finally:
+        lib.pep_global_diff_walk_free(walk)
+    return events, arena, genomes
 
 
 def codon_tables(table_id=11):
@@ -1234,6 +1301,7 @@ class Context(object):
         self._grouping, self.labels = 0, None           # set_grouping: K10 as the tail of every search
         self._verdict_stats = [np.zeros(4), 0]          # kernel times and bytes to the host, summed over the library calls of the newest group_verdicts
         self.kimura_ms = self.nj_ms = (0., 0.)          # kernel times summed over the library calls of the newest kimura_pairs / nj_trees
+        self.global_diff_ms = (0., 0., 0.)              # kernel times of the newest global_diff
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1791,6 +1859,28 @@ class Context(object):
         self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off), _ptr(ms))
         self.nj_ms = (self.nj_ms[0] + float(ms[0]), self.nj_ms[1] + float(ms[1]))
         return [(node[int(a):int(b)], length[int(a):int(b)]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+    # ---- K22
+    def global_diff(self, events, arena, n_genomes, table, chunk_items=0):
+        """the genome-pair sums of get_global_difference (PEPPAN.py:1637-1645, 1650-1662) as include/peppan_hip_gdiff.h states them.  events int64[n, 6] and
+        arena as global_diff_walk leaves them, table float64[10050] the logarithm of every value code.  -> (g1, g2, n, mean, var): per genome pair, in the
+        order the reference's dictionary first meets them, the two ranks g1 <= g2, the number of values, numpy's mean of their logarithms and of the squared
+        deviations.  chunk_items (0 = the library's default) does not change the result.  The kernel times: self.global_diff_ms (counting, chunks, sums;
+        zeros unless set_timing(2))."""
+        events, arena = _gdiff_tables(events, arena)
+        table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        if len(table) != GDIFF_TABLE:
+            raise ValueError('global_diff: the table has %d entries, not %d' % (len(table), GDIFF_TABLE))
+        n_keys, ms = C.c_uint64(), np.zeros(4)
+        self.global_diff_ms = (0., 0., 0.)
+        self._call('pep_global_diff', _ptr_or_null(events), len(events), _ptr_or_null(arena), len(arena), int(n_genomes), _ptr(table), int(chunk_items),
+                   C.byref(n_keys), _ptr(ms))
+        self.global_diff_ms = (float(ms[0]), float(ms[1]), float(ms[2]))
+        k = n_keys.value
+        g1, g2, n = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.uint64)
+        mean, var = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
+        self._call('pep_global_diff_copy', k, _ptr_or_null(g1), _ptr_or_null(g2), _ptr_or_null(n), _ptr_or_null(mean), _ptr_or_null(var))
+        return g1, g2, n, mean, var
 
     # ---- K13
     def sha1(self, seqs):

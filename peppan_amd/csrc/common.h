@@ -318,6 +318,8 @@ struct pep_ctx {
     DevBuf k19[5];                           // grow-only, pep_gene_structure: the nucleotide set, the item records and the outputs (the slots: genestruct.hip)
     DevBuf k20[6];                           // grow-only, pep_rarefaction_curves and pep_profile_pairs: bit rows, orders and curves; profiles and the two pair matrices (the slots: parser.hip)
     DevBuf k21[5];                           // grow-only, pep_nj_trees: the matrices, the tree records, the two outputs and the state of a launch chain (the slots: njtree.hip)
+    uint64_t k22_n_keys = 0;                 // the keys the newest pep_global_diff left on the device, waiting for pep_global_diff_copy
+    DevBuf k22[13];                          // grow-only, pep_global_diff: events, arena, the per-key tables, a chunk's sort buffers, the value lists and the sums (the slots: globaldiff.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose
