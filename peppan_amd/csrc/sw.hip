@@ -384,14 +384,16 @@ __device__ __forceinline__ void sw_two_pk16(const SwArgs &a, uint64_t c0, uint64
 // ---- packed 16-bit TRACEBACK pass: the same two-candidates-per-wavefront sweep, plus the 4-bit codes of both candidates.
 // The codes come out of packed arithmetic instead of compare/select pairs (which would have to run once per candidate):
 //   gt(x, y) = (y - x) >> 15 per 16-bit half (the sign bit of the difference): 0/1 flags without compare instructions
-//   nz = min(H, 1), neh = gt(H, h), gfe = gt(F, E)                        (H >= 0, H >= h: "greater" is "not equal")
-//   src = nz * (1 + neh * (1 + gfe))                                      -> 0 none, 1 diagonal, 2 E, 3 F   (same priority as sw_one)
+//   hz = max(h, 0), H = max(hz, max(E, F) - open - extend)
+//   nz = min(H, 1), gap = gt(H, hz), gfe = gt(F, E)                       (H >= hz >= 0: "greater" is "not equal")
+//   src = nz + gap * (1 + gfe)                                            -> 0 none, 1 diagonal, 2 E, 3 F   (same priority as sw_one)
 //   eflag = gt(e_ext, e_open), fflag likewise;  nibble = src + 4 * eflag + 8 * fflag
 // Four nibbles per candidate accumulate in the halves of one register (one v_pk_mad_u16 with the place value 16^u each); two such
 // registers make the 8-cell word of one diagonal, rearranged per candidate with v_perm_b32 once per 16 steps.
-// The end cell is the first step at which H equals the candidate's score T, which the score pass already delivered.  The running
-// maximum of a lane only grows, so that step number is the count of steps at which the maximum was still below T:
-//   best = max(best, H);  first += gt(T, best)                             (four instructions per step; < 0x8000 steps)
+// The end cell is the first step at which H equals the candidate's score T, which the score pass already delivered.  No H of the
+// sub-band exceeds T (T is the maximum over the whole band, and a sub-band only takes paths away), so T - H >= 0 and a lane is
+// still below T exactly while every T - H it has seen was at least 1.  The step number is the count of such steps:
+//   below = min(below, T - H), starting at 1;  first += below               (three instructions per step; < 0x8000 steps)
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // The flag arithmetic goes through inline assembly: written as C, LLVM recognises the 0/1 values, turns the multiplications into
@@ -409,6 +411,9 @@ __device__ __forceinline__ u16x2 pk_mad(u16x2 a, u16x2 b, u16x2 c)
     asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+// counter += flag (0 / 1 per half) as ONE 32-bit addition: no half of the step counter reaches 0x8000 (the gate `nb < 2040` of sw_trace_kernel), so
+// nothing carries from the low half into the high one, and v_add_u32 issues at twice the rate of v_pk_add_u16
+__device__ __forceinline__ u16x2 count_up(u16x2 n, u16x2 flag) { return __builtin_bit_cast(u16x2, __builtin_bit_cast(uint32_t, n) + __builtin_bit_cast(uint32_t, flag)); }
 struct PkConst { u16x2 four, eight, place[4]; };      // place[u] = 16^u: the nibble of the u-th cell of a half block goes to bits 4u .. 4u+3
 
 // min(x, 1) per half = "x != 0" for x >= 0
@@ -418,14 +423,20 @@ __device__ __forceinline__ u16x2 pk_nonzero(s16x2 x)
     asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(r) : "v"(x));
     return r;
 }
-
-// E and F arrive in the pre-opened form (true value + open + extend, as in the score pass): H is neither h nor 0 exactly when it came
-// out of max(E, F), and then the source is F only if F is strictly greater (the same priority as sw_one: diagonal, E, F)
-__device__ __forceinline__ u16x2 pk_codes(const PkConst &K, s16x2 H, s16x2 h, s16x2 E, s16x2 F, s16x2 e_ext, s16x2 e_open, s16x2 f_ext, s16x2 f_open)
+__device__ __forceinline__ u16x2 pk_min_u16(u16x2 a, s16x2 b)
 {
-    const u16x2 nz = pk_nonzero(H), neh = pk_gt(H, h), gfe = pk_gt(F, E);       // H >= 0, H >= h: "greater" == "not equal"
-    const u16x2 t = pk_mad(neh, gfe, neh);
-    const u16x2 src = pk_mad(nz, t, nz);
+    u16x2 r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// E and F arrive in the pre-opened form (true value + open + extend, as in the score pass).  With hz = max(h, 0) and H = max(hz, max(E, F) - open - extend),
+// H > hz exactly when H is positive and came out of max(E, F) ("gap"), and then the source is F only if F is strictly greater (the same priority as
+// sw_one: diagonal, E, F): src = nz + gap * (1 + gfe) - one multiply-add and one 32-bit addition (0 .. 3 per half: nothing carries)
+__device__ __forceinline__ u16x2 pk_codes(const PkConst &K, s16x2 H, s16x2 hz, s16x2 E, s16x2 F, s16x2 e_ext, s16x2 e_open, s16x2 f_ext, s16x2 f_open)
+{
+    const u16x2 nz = pk_nonzero(H), gap = pk_gt(H, hz), gfe = pk_gt(F, E);      // H >= hz >= 0: "greater" == "not equal"
+    const u16x2 src = count_up(pk_mad(gap, gfe, gap), nz);
     const u16x2 ef = pk_gt(e_ext, e_open), ff = pk_gt(f_ext, f_open);
     return pk_mad(ff, K.eight, pk_mad(ef, K.four, src));
 }
@@ -454,7 +465,7 @@ __device__ __forceinline__ void stage_sub_windows(const SubGeom &g, int b0, int 
 // FOUR candidates per wavefront: lanes 0..31 sweep the sub-bands of candidates 0 / 1 (low / high half of every packed register), lanes
 // 32..63 those of candidates 2 / 3.  The recurrences, the 4-bit codes and the end-cell search are those of the two-candidate packed
 // sweep (see above); the only additions are the AND masks that make lanes 0 / 31 of each half read the band boundary instead of the
-// other half's edge lane (v_and_b32 issues at twice the rate of the packed operations).  ok[x] = candidate x reached its known score
+// other half's edge lane (one v_and_b32 with the lane move as its DPP operand: mask and move are ONE instruction).  ok[x] = candidate x reached its known score
 // inside its sub-band (wave-uniform); a candidate that did not is traced again in its full band by the caller.
 template <bool CHUNKED>
 __device__ __forceinline__ void sw_four_pk16_trace(const SwArgs &a, const uint64_t cc[4], const SubGeom gg[4], const int L0[4], bool ok[4],
@@ -477,7 +488,10 @@ __device__ __forceinline__ void sw_four_pk16_trace(const SwArgs &a, const uint64
     const s16x2 zero = {0, 0};
     const s16x2 oe2 = {(short)a.oe, (short)a.oe}, ext2 = {(short)a.ext, (short)a.ext};
     const s16x2 T2 = {(short)a.known[c0], (short)a.known[c1]};
-    const int keep_l = ln == 0 ? 0 : -1, keep_r = ln == SUB_LANES - 1 ? 0 : -1;
+    int keep_l = ln == 0 ? 0 : -1, keep_r = ln == SUB_LANES - 1 ? 0 : -1;
+    // the masks as opaque vector registers: where hipcc sees that they come out of a comparison it keeps the comparison (a pair of scalar registers)
+    // and emits the lane move and a v_cndmask_b32 behind it; with a mask it knows nothing about it folds the move into the AND (v_and_b32_dpp)
+    asm volatile("" : "+v"(keep_l), "+v"(keep_r));
     auto edge_l = [&](s16x2 v) { return __builtin_bit_cast(s16x2, __builtin_bit_cast(int, v) & keep_l); };
     auto edge_r = [&](s16x2 v) { return __builtin_bit_cast(s16x2, __builtin_bit_cast(int, v) & keep_r); };
     PkConst K;
@@ -485,7 +499,7 @@ __device__ __forceinline__ void sw_four_pk16_trace(const SwArgs &a, const uint64
     K.place[0] = u16x2{1, 1}; K.place[1] = u16x2{16, 16}; K.place[2] = u16x2{256, 256}; K.place[3] = u16x2{4096, 4096};
     s16x2 HA = zero, EA = zero, FA = zero, HB = zero, EB = zero, FB = zero;
     u16x2 first = {0, 0};
-    s16x2 best = zero;
+    u16x2 below = {1, 1};                          // 1 while the lane has not met T yet (see above)
     int cb = 0;
     do {
     const int ce = CHUNKED ? min(nb, cb + chunk) : nb;
@@ -500,47 +514,57 @@ __device__ __forceinline__ void sw_four_pk16_trace(const SwArgs &a, const uint64
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     lds_cu16 *vq0 = (lds_cu16 *)((hf ? wq[2] : wq[0]) + (SUB_LANES - ln)), *vt0 = (lds_cu16 *)((hf ? wt[2] : wt[0]) + (1 + ln));
     lds_cu16 *vq1 = (lds_cu16 *)((hf ? wq[3] : wq[1]) + (SUB_LANES - ln)), *vt1 = (lds_cu16 *)((hf ? wt[3] : wt[1]) + (1 + ln));
-    int tv0 = vt0[0], tv1 = vt1[0], qv0 = 0, qv1 = 0;
+    // the residue cursors run one step ahead of the table look-ups, as in sw_two_pk16: the reads for the next step are issued right behind the
+    // two table reads of this one, so a step waits for ONE LDS round trip (its table entries), not for two in a row.  The read-ahead of a chunk's
+    // last step lands in the 8 entries of slack that stage_sub_windows stages behind the last block (highest index read: 8 * blocks + SUB_LANES);
+    // after a restaging the cursors are primed again, here, behind the wave barrier
+    int tv0 = vt0[0], tv1 = vt1[0], qv0 = vq0[0], qv1 = vq1[0];
     for (int b = cb; b < ce; ++b) {
         u16x2 accA = {0, 0}, accB = {0, 0}, loA = {0, 0}, loB = {0, 0};
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                // ---- A step
-                qv0 = vq0[u]; qv1 = vq1[u];
+                // ---- A step: both table reads first, the next target residues behind them; the lane moves, the edge masks and E / F need neither
+                int tn0, tn1, qn0, qn1;
                 {
-                    const s16x2 sub = {tab_at(tab, qv0, tv0), tab_at(tab, qv1, tv1)};
+                    const short s0 = tab_at(tab, qv0, tv0), s1 = tab_at(tab, qv1, tv1);
+                    tn0 = vt0[u + 1]; tn1 = vt1[u + 1];
                     const s16x2 hl = edge_l(pk_shr1z(HB)), el = edge_l(pk_shr1z(EB));
                     const s16x2 e_ext = el - ext2, f_ext = FB - ext2;                 // "open from H" needs no subtraction in this form
                     const s16x2 E = pk_max(e_ext, hl), F = pk_max(f_ext, HB);
+                    const s16x2 sub = {s0, s1};
                     const s16x2 h = HA + sub;
-                    const s16x2 H = pk_max(pk_max(h, pk_max(E, F) - oe2), zero);
+                    const s16x2 hz = pk_max(h, zero);
+                    const s16x2 H = pk_max(hz, pk_max(E, F) - oe2);
                     {   // u is a compile-time constant of the unrolled loop: the first nibble of a half block simply starts the word
-                        const u16x2 code = pk_codes(K, H, h, E, F, e_ext, hl, f_ext, HB);
+                        const u16x2 code = pk_codes(K, H, hz, E, F, e_ext, hl, f_ext, HB);
                         accA = u == 0 ? code : pk_mad(code, K.place[u], accA);
                     }
-                    best = pk_max(best, H);
-                    first += pk_gt(T2, best);
+                    below = pk_min_u16(below, T2 - H);
+                    first = count_up(first, below);
                     HA = H; EA = E; FA = F;
                 }
-                // ---- B step (target cursor advances)
-                tv0 = vt0[u + 1]; tv1 = vt1[u + 1];
+                // ---- B step (target cursor advances); the next query residues are read behind its table reads
                 {
-                    const s16x2 sub = {tab_at(tab, qv0, tv0), tab_at(tab, qv1, tv1)};
+                    const short s0 = tab_at(tab, qv0, tn0), s1 = tab_at(tab, qv1, tn1);
+                    qn0 = vq0[u + 1]; qn1 = vq1[u + 1];
                     const s16x2 hu = edge_r(pk_shl1z(HA)), fu = edge_r(pk_shl1z(FA));
                     const s16x2 e_ext = EA - ext2, f_ext = fu - ext2;
                     const s16x2 E = pk_max(e_ext, HA), F = pk_max(f_ext, hu);
+                    const s16x2 sub = {s0, s1};
                     const s16x2 h = HB + sub;
-                    const s16x2 H = pk_max(pk_max(h, pk_max(E, F) - oe2), zero);
+                    const s16x2 hz = pk_max(h, zero);
+                    const s16x2 H = pk_max(hz, pk_max(E, F) - oe2);
                     {
-                        const u16x2 code = pk_codes(K, H, h, E, F, e_ext, HA, f_ext, hu);
+                        const u16x2 code = pk_codes(K, H, hz, E, F, e_ext, HA, f_ext, hu);
                         accB = u == 0 ? code : pk_mad(code, K.place[u], accB);
                     }
-                    best = pk_max(best, H);
-                    first += pk_gt(T2, best);
+                    below = pk_min_u16(below, T2 - H);
+                    first = count_up(first, below);
                     HB = H; EB = E; FB = F;
                 }
+                tv0 = tn0; tv1 = tn1; qv0 = qn0; qv1 = qn1;
             }
             vq0 += 4; vq1 += 4; vt0 += 4; vt1 += 4;
             if (half == 0) { loA = accA; loB = accB; }
