@@ -131,6 +131,14 @@ GDIFF_SIGNATURES = {
     'pep_global_diff_copy': (I, P, U64, P, P, P, P, P),
     'pep_global_diff_check': (I, P, U64, P, U64, U32, U64, P, U64),
 }
+# ... and of include/peppan_hip_cds.h (K23), for the same reason; tests/test_gffgenes_host.py holds this one to the fourth header
+CDS_SIGNATURES = {
+    'pep_cds_genes_check': (I, P, U32, U32, P, P, P, P, U32, P, U64),
+    'pep_cds_genes': (I, P, P, P, U32, U32, P, P, P, P, U32, U32, I, P, P, P),
+}
+CDS_MAX_WINDOW = 1 << 31                 # PEP_CDS_MAX_WINDOW: a window of pep_cds_genes holds fewer bytes than this
+CDS_MAX_ITEMS = 1 << 32                  # PEP_CDS_MAX_ITEMS: fewer CDS than this in one call
+CDS_ALLOW = {'s': 1, 'i': 2, 'f': 4, 'e': 8}     # PEP_CDS_ALLOW_*: the mask bit of every letter of incompleteCDS
 GDIFF_MAX_GENOMES = 16384                # PEP_GDIFF_MAX_GENOMES: distinct genomes of one pep_global_diff call
 GDIFF_MAX_ITEMS = 1 << 32                # PEP_GDIFF_MAX_ITEMS: list-pair members of one call
 GDIFF_TABLE = 10050                      # PEP_GDIFF_TABLE: entries of the logarithm table, value codes 0 .. 10049
@@ -246,7 +254,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()):
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -597,6 +605,32 @@ def gene_structure_check(seq_off, seq, win_off, win_len, flags, lp, allowed_vary
     """the host checks of pep_gene_structure alone (no context, no device, the nucleotides are not read): PepError with the library's code and text, else None"""
     args, _, keep = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
     _check_only('pep_gene_structure_check', *args)
+
+
+def _cds_tables(contig_off, contig, win_off, win_len, strand):
+    """the tables of a pep_cds_genes / pep_cds_genes_check call as the library's types; values that do not fit their column raise ValueError here"""
+    contig_off = np.ascontiguousarray(contig_off, dtype=np.uint64).reshape(-1)
+    if len(contig_off) == 0:
+        raise ValueError('cds_genes: contig_off has n_contigs + 1 entries')
+    given = [np.asarray(col).reshape(-1) for col in (contig, win_off, win_len, strand)]
+    n_cds = len(given[0])
+    if any(len(c) != n_cds for c in given):
+        raise ValueError('cds_genes: one entry per CDS in every table')
+    if n_cds >= CDS_MAX_ITEMS or len(contig_off) - 1 >= 1 << 32:              # (before any column is looked through)
+        raise ValueError('cds_genes: 2^32 CDS or contigs or more in one call')
+    cols = []
+    for name, col, dtype in zip(('contig', 'win_off', 'win_len', 'strand'), given, (np.uint32, np.uint64, np.uint32, np.uint8)):
+        if len(col) and (col.dtype.kind not in 'iub' or (col.dtype.kind == 'i' and (col < 0).any()) or int(col.max()) > np.iinfo(dtype).max):
+            raise ValueError('cds_genes: %s must be integers that fit %s' % (name, np.dtype(dtype).name))
+        cols.append(np.ascontiguousarray(col, dtype=dtype))
+    keep = [contig_off] + [_some(c) for c in cols]
+    return [_ptr(keep[0]), len(contig_off) - 1, n_cds] + [_ptr(c) for c in keep[1:]], n_cds, keep
+
+
+def cds_genes_check(contig_off, contig, win_off, win_len, strand, mask=0):
+    """the host checks of pep_cds_genes alone (no context, no device, the contigs are not read): PepError with the library's code and text, else None"""
+    args, _, keep = _cds_tables(contig_off, contig, win_off, win_len, strand)
+    _check_only('pep_cds_genes_check', *args, int(mask))
 
 
 def pack_presence(presence):
@@ -1302,6 +1336,7 @@ class Context(object):
         self._verdict_stats = [np.zeros(4), 0]          # kernel times and bytes to the host, summed over the library calls of the newest group_verdicts
         self.kimura_ms = self.nj_ms = (0., 0.)          # kernel times summed over the library calls of the newest kimura_pairs / nj_trees
         self.global_diff_ms = (0., 0., 0.)              # kernel times of the newest global_diff
+        self.cds_ms = (0., 0.)                          # kernel times of the newest cds_genes
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1859,6 +1894,25 @@ class Context(object):
         self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off), _ptr(ms))
         self.nj_ms = (self.nj_ms[0] + float(ms[0]), self.nj_ms[1] + float(ms[1]))
         return [(node[int(a):int(b)], length[int(a):int(b)]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+    # ---- K23
+    def cds_genes(self, nt, contig_off, contig, win_off, win_len, strand, min_cds=0, mask=0, table4=False):
+        """checkPseu (PEPPAN.py:992-1010) and the SHA-1 of the kept (:178, :1020) for a batch of CDS, as include/peppan_hip_cds.h states them.  nt: the contigs
+        as upper-cased ASCII bytes (bytes or uint8 array), contig c at nt[contig_off[c] .. contig_off[c+1]].  CDS p is win_len[p] bytes from the 0-based
+        win_off[p] of contig contig[p], read backward and complemented when strand[p] is 1.  min_cds: 0 .. 2^31; mask: CDS_ALLOW bits; table4: TGA is no stop.
+        -> (code uint8[n]: 0 .. 5; digest uint8[n, 20]: hashlib.sha1(text).digest() where the code is 0, zeros elsewhere).  The kernel times: self.cds_ms
+        (verdicts, digests; zeros unless set_timing(2))."""
+        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        args, n, keep_alive = _cds_tables(contig_off, contig, win_off, win_len, strand)
+        if len(nt) != int(keep_alive[0][-1]):
+            raise ValueError('cds_genes: contig_off must end at the length of nt')
+        if not 0 <= int(min_cds) <= CDS_MAX_WINDOW or not 0 <= int(mask) < 1 << 32:
+            raise ValueError('cds_genes: min_cds is 0 .. 2^31, mask 32 bits')
+        code, digest, ms = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 20), np.uint8), np.zeros(2)
+        self.cds_ms = (0., 0.)
+        self._call('pep_cds_genes', _ptr(_some(nt)), *args, int(min_cds), int(mask), 1 if table4 else 0, _ptr(code), _ptr(digest), _ptr(ms))
+        self.cds_ms = (float(ms[0]), float(ms[1]))
+        return code[:n], digest[:n]
 
     # ---- K22
     def global_diff(self, events, arena, n_genomes, table, chunk_items=0):
