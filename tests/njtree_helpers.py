@@ -3,6 +3,8 @@ bipartition sets of join records and of Newick texts, and the builders of the te
 
 The restatement is the definition the device is held to bit for bit: float64 throughout, every operation one numpy operation (numpy never fuses a
 multiplication into an addition), the row sums added left to right, the arg-min the first smallest Q in row-major order over the live slots.
+With a `trace` it also says, round by round, which pairs tied and whether a NaN or the no-usable-Q fallback was met: tests/test_njtree_host.py
+holds the tie and overflow matrices of tests/test_gpu_njtree_edges.py (edge_case) to the branches they are meant to reach.
 
     python tests/njtree_helpers.py > profiles/njtree_vs_reference.txt     how far the restatement is from what rapidnj printed for the committed fixtures"""
 import gzip
@@ -13,8 +15,18 @@ import sys
 import numpy as np
 
 
-def nj_restated(matrix):
-    """(node uint32[2 n - 3], length float64[2 n - 3]) of one square matrix, of which the entries with row < column are read"""
+def nj_restated(matrix, trace=None):
+    """(node uint32[2 n - 3], length float64[2 n - 3]) of one square matrix, of which the entries with row < column are read.  Sums that overflow are
+    legal (the header's rules for +infinity and NaN apply), so numpy's warnings are off in here.
+
+    trace: a list that receives one (m, i, j, n_min, rows_min, any_nan, fallback) per round - the live slots, the list positions joined, how many usable
+    pairs (Q below +infinity) attain the smallest Q, the set of list rows i they lie in, whether any Q of the upper triangle is NaN, and whether
+    positions 0, 1 were taken for lack of a usable Q.  It changes nothing of what is computed."""
+    with np.errstate(all='ignore'):
+        return _nj_restated(matrix, trace)
+
+
+def _nj_restated(matrix, trace):
     n = len(matrix)
     up = np.triu(np.asarray(matrix, dtype=np.float64), 1)
     D = up + up.T
@@ -34,12 +46,17 @@ def nj_restated(matrix):
         L = np.array(live)
         Dl, rl = D[np.ix_(L, L)], r[L]
         Q = (float(m - 2) * Dl - rl[:, None]) - rl[None, :]
-        with np.errstate(invalid='ignore'):
-            usable = np.triu(np.ones((m, m), bool), 1) & (Q < np.inf)
-        if usable.any():
-            i, j = divmod(int(np.argmin(np.where(usable, Q, np.inf))), m)       # the first smallest: the smaller a, then the smaller b
+        upper = np.triu(np.ones((m, m), bool), 1)
+        usable = upper & (Q < np.inf)
+        masked = np.where(usable, Q, np.inf)
+        fallback = not usable.any()
+        if not fallback:
+            i, j = divmod(int(np.argmin(masked)), m)         # the first smallest: the smaller a, then the smaller b
         else:
             i, j = 0, 1
+        if trace is not None:
+            ties = usable & (masked == masked[i, j])
+            trace.append((m, i, j, int(ties.sum()), set(np.flatnonzero(ties.any(1)).tolist()), bool((np.isnan(Q) & upper).any()), fallback))
         a, b = live[i], live[j]
         dab, ra, rb = D[a, b], r[a], r[b]
         la = 0.5 * dab + (ra - rb) / float(2 * (m - 2))
@@ -205,6 +222,74 @@ def with_duplicates(n, seed):
     pts = rng.integers(0, 4, (max(2, n // 3), 3)).astype(np.float64)
     pts = pts[rng.integers(0, len(pts), n)]
     return np.sqrt(((pts[:, None, :] - pts[None, :, :]) ** 2).sum(-1))
+
+
+def tied(n, seed, levels=3):
+    """a symmetric matrix of integers 0 .. levels - 1 with a zero diagonal: Q is a small integer, so in most rounds several pairs attain the minimum"""
+    rng = np.random.default_rng(seed)
+    up = np.triu(rng.integers(0, levels, (n, n)).astype(np.float64), 1)
+    return up + up.T
+
+
+def tied_clades(n, seed, levels=3, fan=2):
+    """integers 0 .. levels - 1 again, but an ultrametric: every leaf draws a label of levels - 1 digits below `fan`, and two leaves are as far apart as
+    digits remain from the first one they differ in.  Leaves with one label are duplicates, a join of two of them is one more, and so the smallest Q is
+    shared by several pairs until a label is down to two leaves: ties in most rounds, where independent draws (tied) tie in about 3 % of them"""
+    rng = np.random.default_rng(seed)
+    labels = rng.integers(0, fan, (n, levels - 1))
+    same = np.cumprod(labels[:, None, :] == labels[None, :, :], axis=-1).sum(-1)          # digits of the common prefix
+    return (levels - 1 - same).astype(np.float64)
+
+
+def constant(n, value):
+    """every distance off the diagonal is `value`: all Q equal in the first round; at 1e308 every row sum overflows and every Q is NaN"""
+    d = np.full((n, n), float(value))
+    np.fill_diagonal(d, 0.)
+    return d
+
+
+def planted(n, seed, a, b):
+    """euclidean(n, seed) in which a and b all but coincide"""
+    d = euclidean(n, seed)
+    d[a, b] = d[b, a] = 1e-9
+    return d
+
+
+def one_huge_row(n, seed):
+    """euclidean(n, seed) with row and column 0 at 1.5e308: r[0] overflows, so every Q of row 0 is NaN, and every other Q is -infinity"""
+    d = euclidean(n, seed)
+    d[0, 1:] = d[1:, 0] = 1.5e308
+    return d
+
+
+def chain_parts(m):
+    """the workgroups of nj_chain_argmin at m live slots; workgroup (i // 4) % parts has list row i, wavefront i % 4 of it"""
+    return min(256, -(-(m - 1) // 4))
+
+
+# the tie and overflow matrices of tests/test_gpu_njtree_edges.py, by name; tests/test_njtree_host.py proves from the trace that each reaches its branch
+TIED_SIZES = (4, 5, 32, 33, 64, 65, 66, 80, 81, 129, 255, 256, 257, 301)
+CONSTANT_SIZES = (5, 65, 81, 257)
+CGAV12_SIZES = (100, 301)
+ALL_NAN_SIZES = (4, 6, 40, 100, 257)
+HUGE_ROW_SIZES = (6, 100, 257)
+EDGE_BUILDERS = {'tied': lambda n: tied(n, 1),
+                 'clades': lambda n: tied_clades(n, 2 if n >= 1026 else 1),       # (seed 2 at 1030 leaves: the first round's ties reach list row 1024)
+                 'constant': lambda n: constant(n, 0.25),
+                 'cgav12': lambda n: cgav_like(n, 7, genes=12), 'planted': lambda n: planted(n, 1, n - 4, n - 2),
+                 'all_nan': lambda n: constant(n, 1e308), 'huge_row': lambda n: one_huge_row(n, 5)}
+_edge_cases = {}
+
+
+def edge_case(kind, n):
+    """(matrix, node, length, trace) of EDGE_BUILDERS[kind](n), restated once per process and read-only: both test modules share it"""
+    if (kind, n) not in _edge_cases:
+        matrix, trace = EDGE_BUILDERS[kind](n), []
+        node, length = nj_restated(matrix, trace)
+        for a in (matrix, node, length):
+            a.setflags(write=False)
+        _edge_cases[kind, n] = (matrix, node, length, tuple(trace))
+    return _edge_cases[kind, n]
 
 
 def non_additive(n, seed):

@@ -215,3 +215,82 @@ def test_writecgav_without_rapidnj_writes_the_tree(monkeypatch, tmp_path):
     assert H.bipartitions(branches, genomes) == H.bipartitions(H.named_branches(distances, genomes), genomes)
     assert log[-1] == 'Core gene allelic variation tree is saved in %s_CGAV.nwk' % prefix and not any('skipped' in line for line in log)
     assert os.path.exists(prefix + '_CGAV.profile') and os.path.exists(prefix + '_CGAV.dist')
+
+
+# ---- the tie and overflow matrices of tests/test_gpu_njtree_edges.py reach the branches they are for: proved from the restatement's trace alone
+
+def tie_rounds(trace):
+    """(rounds in which two usable pairs or more attain the smallest Q; of those, rounds in which they lie in rows of two wavefronts - a wavefront of
+    nj_scan_rows has the list rows of one i % 4 -; rounds in which they lie in rows of two workgroups of nj_chain_argmin)"""
+    tied = sum(1 for r in trace if r[3] >= 2)
+    waves = sum(1 for r in trace if len({i % 4 for i in r[4]}) >= 2)
+    groups = sum(1 for r in trace if len({(i // 4) % H.chain_parts(r[0]) for i in r[4]}) >= 2)
+    return tied, waves, groups
+
+
+TIE_CASES = [(kind, n) for kind, sizes in (('tied', H.TIED_SIZES), ('clades', H.TIED_SIZES), ('constant', H.CONSTANT_SIZES), ('cgav12', H.CGAV12_SIZES))
+             for n in sizes]
+
+
+@pytest.mark.parametrize('kind,n', TIE_CASES)
+def test_tie_matrices_tie_across_wavefronts_and_workgroups(kind, n):
+    """Every tie matrix: finite lengths, a tied round, above 64 leaves a round whose tied minima lie in rows of two wavefronts, at chain sizes one whose
+    tied minima lie in rows of two workgroups.  The ultrametric and the constant matrices tie in a quarter of their rounds at least (measured: all but
+    five).  Independent draws of 0..2 (H.tied) and the 12-gene profiles do not, whatever the seed or the number of levels above one - the updates halve
+    the integers and the ties are gone after a few joins: 2 - 7 tied rounds of 29 - 298 for H.tied, 14 of 97 and 54 of 298 for the profiles - so of
+    them only what they do have is asserted, and the quarter is carried by H.tied_clades at the same sizes."""
+    matrix, node, length, trace = H.edge_case(kind, n)
+    assert len(trace) == n - 3 and np.isfinite(length).all() and len(node) == 2 * n - 3
+    assert all(r[3] >= 1 and not r[5] and not r[6] and r[1] in r[4] for r in trace)
+    tied, waves, groups = tie_rounds(trace)
+    print('%s %d: %d rounds, %d tied, %d over two wavefronts, %d over two workgroups' % (kind, n, len(trace), tied, waves, groups))
+    assert tied >= 1
+    if kind in ('clades', 'constant'):
+        assert 4 * tied >= len(trace)
+    if n > 64:
+        assert waves >= 1
+    if n > 256:
+        assert groups >= 1
+
+
+def test_trace_changes_nothing():
+    for kind, n in (('tied', 33), ('clades', 66), ('all_nan', 6), ('huge_row', 6)):
+        matrix, node, length, trace = H.edge_case(kind, n)
+        again_node, again_length = H.nj_restated(matrix)
+        assert np.array_equal(node, again_node) and np.array_equal(length.view(np.uint64), again_length.view(np.uint64))
+        assert [r[0] for r in trace] == list(range(n, 3, -1)) and all(0 <= r[1] < r[2] < r[0] for r in trace)
+    assert (H.tied(9, 4) == H.tied(9, 4).T).all() and set(np.unique(H.tied(40, 4))) == {0., 1., 2.} and not H.tied(9, 4).diagonal().any()
+    assert (H.tied_clades(9, 4) == H.tied_clades(9, 4).T).all() and set(np.unique(H.tied_clades(40, 4))) == {0., 1., 2.}
+    assert np.array_equal(H.constant(3, 0.25), [[0, .25, .25], [.25, 0, .25], [.25, .25, 0]])
+    d, e = H.planted(9, 4, 2, 5), H.euclidean(9, 4)
+    assert d[2, 5] == d[5, 2] == 1e-9 and (d != e).sum() == 2
+
+
+def test_the_1030_leaf_matrices_reach_the_second_trip_of_the_chain():
+    """256 workgroups of four wavefronts have list rows 0 .. 1023 on their first trip; row 1026 is the second trip of workgroup 0's wavefront 2"""
+    n = 1030
+    assert H.chain_parts(n) == 256 and H.chain_parts(1025) == 256 and H.chain_parts(1024) == 256 and H.chain_parts(1021) == 255
+    matrix, node, length, trace = H.edge_case('planted', n)
+    assert trace[0][:4] == (n, 1026, 1028, 1) and node[:2].tolist() == [1026, 1028] and np.isfinite(length).all()
+    assert 1026 >= 4 * H.chain_parts(n)
+    for kind in ('tied', 'clades'):
+        matrix, node, length, trace = H.edge_case(kind, n)
+        tied, waves, groups = tie_rounds(trace)
+        both_trips = sum(1 for r in trace if r[3] >= 2 and max(r[4]) >= 4 * H.chain_parts(r[0]) > min(r[4]))
+        print('%s %d: %d rounds, %d tied, %d over two wavefronts, %d over two workgroups, %d over both trips' % (kind, n, len(trace), tied, waves, groups, both_trips))
+        assert np.isfinite(length).all() and tied >= 1 and waves >= 1 and groups >= 1
+        if kind == 'clades':                                  # ... and tied minima in rows of a wavefront's first and second trip
+            assert 4 * tied >= len(trace) and both_trips >= 1
+
+
+def test_overflow_matrices_take_the_fallback_and_meet_nan():
+    for n in H.ALL_NAN_SIZES:
+        matrix, node, length, trace = H.edge_case('all_nan', n)
+        assert len(trace) == n - 3 and all(r[6] and r[5] and r[1:5] == (0, 1, 0, set()) for r in trace)
+    assert H.edge_case('all_nan', 6)[1].tolist() == [0, 1, 6, 2, 7, 3, 8, 4, 5]
+    for n in H.HUGE_ROW_SIZES:
+        matrix, node, length, trace = H.edge_case('huge_row', n)
+        assert np.isfinite(matrix).all() and matrix[0, 1] == 1.5e308
+        met = [r for r in trace if r[5] and not r[6]]              # a NaN among the Q, and a usable winner: finite or -infinity by the definition of usable
+        assert len(met) >= 1 and all(r[3] >= 1 and r[1] in r[4] for r in met)
+        assert trace[0][1:3] == (1, 2) and np.isnan(length).any() and not np.isnan(length).all()
