@@ -136,6 +136,19 @@ CDS_SIGNATURES = {
     'pep_cds_genes_check': (I, P, U32, U32, P, P, P, P, U32, P, U64),
     'pep_cds_genes': (I, P, P, P, U32, U32, P, P, P, P, U32, U32, I, P, P, P),
 }
+# ... and of include/peppan_hip_outalleles.h (K24), for the same reason; tests/test_outalleles_host.py holds this one to the fifth header
+OUTALLELES_SIGNATURES = {
+    'pep_out_alleles_check': (I, P, U32, U32, P, U32, P, P, U32, P, U64),
+    'pep_out_alleles': (I, P, P, P, U32, U32, P, U32, P, P, I, U32, P, P, P, P, P),
+}
+OUTA_COLS, OUTA_PLAN_COLS = 12, 6        # PEP_OUTA_COLS, PEP_OUTA_PLAN_COLS: int32 values of a row record and of a plan record
+OUTA_GENE, OUTA_CONTIG, OUTA_FLAGS, OUTA_S, OUTA_E, OUTA_PART, OUTA_QS, OUTA_QE, OUTA_REFLEN, OUTA_CLEN, OUTA_VARY, OUTA_SVMIN = range(12)     # PEP_OUTA_GENE ..
+OUTA_MISC, OUTA_NONAME, OUTA_SECONDARY, OUTA_MINUS = 1, 2, 4, 8                  # the bits of PEP_OUTA_FLAGS
+OUTA_SKIPPED, OUTA_FRAGMENT, OUTA_INTACT, OUTA_STRUCTVAR = range(4)              # the classes of a plan record
+OUTA_BATCH = 10000                       # PEP_OUTA_BATCH: rows between two write-backs of the reference
+OUTA_MAX_CONTIG = 1 << 31                # PEP_OUTA_MAX_CONTIG
+OUTA_MAX_ITEMS = 1 << 30                 # PEP_OUTA_MAX_ITEMS: rows and genes of one call
+ERR_ALLELE_CLASS = -24                   # PEP_ERR_ALLELE_CLASS: two rows of one digest class hold different bytes
 CDS_MAX_WINDOW = 1 << 31                 # PEP_CDS_MAX_WINDOW: a window of pep_cds_genes holds fewer bytes than this
 CDS_MAX_ITEMS = 1 << 32                  # PEP_CDS_MAX_ITEMS: fewer CDS than this in one call
 CDS_ALLOW = {'s': 1, 'i': 2, 'f': 4, 'e': 8}     # PEP_CDS_ALLOW_*: the mask bit of every letter of incompleteCDS
@@ -254,7 +267,8 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()):
+    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()) + \
+            list(OUTALLELES_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -631,6 +645,38 @@ def cds_genes_check(contig_off, contig, win_off, win_len, strand, mask=0):
     """the host checks of pep_cds_genes alone (no context, no device, the contigs are not read): PepError with the library's code and text, else None"""
     args, _, keep = _cds_tables(contig_off, contig, win_off, win_len, strand)
     _check_only('pep_cds_genes_check', *args, int(mask))
+
+
+def _outalleles_tables(contig_off, seed_contig, rows, look9):
+    """the tables of a pep_out_alleles / pep_out_alleles_check call as the library's types; values that do not fit int32 raise ValueError here"""
+    contig_off = np.ascontiguousarray(contig_off, dtype=np.uint64).reshape(-1)
+    if len(contig_off) == 0:
+        raise ValueError('out_alleles: contig_off has n_contigs + 1 entries')
+    given = []
+    for name, a in (('seed_contig', seed_contig), ('rows', rows), ('look9', look9)):
+        if a is None:
+            given.append(None)
+            continue
+        a = np.asarray(a)
+        if a.size and (a.dtype.kind not in 'iu' or int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
+            raise ValueError('out_alleles: %s must be integers that fit int32' % name)
+        given.append(np.ascontiguousarray(a, dtype=np.int32))
+    seed_contig, rows, look9 = given[0].reshape(-1), given[1], given[2]
+    if rows.ndim != 2 or rows.shape[1] != OUTA_COLS:
+        raise ValueError('out_alleles: rows is a table [n_rows, %d]' % OUTA_COLS)
+    n_rows = rows.shape[0]
+    if look9 is not None and look9.shape != (n_rows,):
+        raise ValueError('out_alleles: look9 has one entry per row')
+    if n_rows + len(seed_contig) >= OUTA_MAX_ITEMS or len(contig_off) - 1 >= 1 << 32:
+        raise ValueError('out_alleles: 2^30 rows and genes, or 2^32 contigs, or more in one call')
+    keep = [contig_off, _some(seed_contig), _some(rows.reshape(-1)), look9]
+    return [_ptr(keep[0]), len(contig_off) - 1, len(seed_contig), _ptr(keep[1]), n_rows, _ptr(keep[2]), None if look9 is None else _ptr(look9)], n_rows, keep
+
+
+def out_alleles_check(contig_off, seed_contig, rows, look9=None, key_bits=0):
+    """the host checks of pep_out_alleles alone (no context, no device, the contigs are not read): PepError with the library's code and text, else None"""
+    args, _, keep = _outalleles_tables(contig_off, seed_contig, rows, look9)
+    _check_only('pep_out_alleles_check', *args, int(key_bits))
 
 
 def pack_presence(presence):
@@ -1337,6 +1383,7 @@ class Context(object):
         self.kimura_ms = self.nj_ms = (0., 0.)          # kernel times summed over the library calls of the newest kimura_pairs / nj_trees
         self.global_diff_ms = (0., 0., 0.)              # kernel times of the newest global_diff
         self.cds_ms = (0., 0.)                          # kernel times of the newest cds_genes
+        self.out_alleles_ms = (0.,) * 6                 # kernel times of the newest out_alleles: plan, digest, classes, comparison, sort, ranks
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1913,6 +1960,32 @@ class Context(object):
         self._call('pep_cds_genes', _ptr(_some(nt)), *args, int(min_cds), int(mask), 1 if table4 else 0, _ptr(code), _ptr(digest), _ptr(ms))
         self.cds_ms = (float(ms[0]), float(ms[1]))
         return code[:n], digest[:n]
+
+    # ---- K24
+    def out_alleles(self, nt, contig_off, seed_contig, rows, look9=None, plan_only=False, key_bits=0):
+        """the allele pass of write_output (PEPPAN.py:1391-1472) for a prediction table, as include/peppan_hip_outalleles.h states it.  nt: the contigs - and behind
+        them the representatives, one contig each - as ASCII bytes (bytes or uint8 array), contig c at nt[contig_off[c] .. contig_off[c+1]]; seed_contig[g]: the
+        contig that is gene g's representative, -1 for none; rows int32[n, OUTA_COLS]: the row records; look9 (optional, int32[n]): column 9 as the rows of
+        earlier batches show it to the '-' rows at the head of a batch.
+        -> (plan int32[n, OUTA_PLAN_COLS]: class, s2, e2, lp, a, len; first int32[n]; rank uint32[n]; tflag uint8[n]).  plan_only: the plan alone, nt is not read
+        (None will do) and the other three are None.  key_bits: for tests of the comparison pass alone.  The kernel times: self.out_alleles_ms (zeros unless
+        set_timing(2))."""
+        args, n, keep_alive = _outalleles_tables(contig_off, seed_contig, rows, look9)
+        if not 0 <= int(key_bits) < 1 << 32:
+            raise ValueError('out_alleles: key_bits is 0 .. 31')
+        plan, ms = np.zeros((max(n, 1), OUTA_PLAN_COLS), np.int32), np.zeros(6)
+        self.out_alleles_ms = (0.,) * 6
+        if plan_only:
+            self._call('pep_out_alleles', None, *args, 1, int(key_bits), _ptr(plan), None, None, None, _ptr(ms))
+            self.out_alleles_ms = tuple(float(v) for v in ms)
+            return plan[:n], None, None, None
+        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        if len(nt) != int(keep_alive[0][-1]):
+            raise ValueError('out_alleles: contig_off must end at the length of nt')
+        first, rank, tflag = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8)
+        self._call('pep_out_alleles', _ptr(_some(nt)), *args, 0, int(key_bits), _ptr(plan), _ptr(first), _ptr(rank), _ptr(tflag), _ptr(ms))
+        self.out_alleles_ms = tuple(float(v) for v in ms)
+        return plan[:n], first[:n], rank[:n], tflag[:n]
 
     # ---- K22
     def global_diff(self, events, arena, n_genomes, table, chunk_items=0):

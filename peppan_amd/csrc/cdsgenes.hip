@@ -9,7 +9,7 @@
 //                 wave-uniform bits are carried: codon 0 is M, codon n - 1 is X, an X before codon n - 1.  The next chunk is on its way while one is judged;
 //                 the walk ends after chunk 0 when code 3 is already fixed.  Integers only, no LDS, the code byte by a plain vector store of lane 0.
 //   cds_digest    one thread per CDS of code 0, as K13's k13_sha1: 64-byte blocks as four unaligned 16-byte loads straight from the arena - read from the
-//                 window's far end, complemented bytewise and taken in reverse word order when the strand bit is set - into sha1_block (sha1.h).
+//                 window's far end, complemented bytewise and taken in reverse word order when the strand bit is set - into sha1_block (sha1.h: sha1_window).
 // What bounds them: byte-granular reads and a short wavefront-serial chain of chunks per CDS (verdict); ~1100 integer operations per 64 bytes with the lanes
 // of a wavefront on CDS of different lengths (digest).  DESIGN.md 4.10j.
 #include "common.h"
@@ -75,63 +75,14 @@ __global__ __launch_bounds__(256) void cds_verdict(const uint8_t *__restrict__ n
     if (lane == 0) code[i] = (uint8_t)verdict;
 }
 
-// rc() of one byte: A <-> T, C <-> G, everything else N
-__device__ __forceinline__ uint32_t cds_rc_byte(uint32_t b)
-{
-    const uint32_t u = b & 0xDFu;
-    const uint32_t c = ((u >> 1) ^ (u >> 2)) & 3u;                      // (gs_code's test for A C G T)
-    return u == ((0x54474341u >> (c * 8)) & 0xFFu) ? (0x41434754u >> (c * 8)) & 0xFFu : (uint32_t)'N';
-}
-
-__device__ __forceinline__ uint32_t cds_rc_word(uint32_t r)
-{
-    return cds_rc_byte(r & 0xFFu) | cds_rc_byte((r >> 8) & 0xFFu) << 8 | cds_rc_byte((r >> 16) & 0xFFu) << 16 | cds_rc_byte(r >> 24) << 24;
-}
-
 __global__ __launch_bounds__(256) void cds_digest(const uint8_t *__restrict__ nt, const CdsItem *__restrict__ items, uint32_t n_cds, const uint8_t *__restrict__ code,
                                                   uint32_t *__restrict__ digest)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_cds || code[i] != 0) return;
     const CdsItem it = items[i];
-    const uint8_t *s = nt + it.at;
-    const uint32_t len = it.len;
-    const bool rev = it.rev != 0;
-    uint32_t h[5] = {0x67452301u, 0xEFCDAB89u, 0x98BADCFEu, 0x10325476u, 0xC3D2E1F0u};
-    uint32_t w[16];
-    uint32_t at = 0;
-    for (; at + 64u <= len; at += 64u) {
-        if (!rev) {
-            __builtin_memcpy(w, s + at, 64);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) w[k] = __builtin_bswap32(w[k]);
-        } else {
-            // text bytes at .. at + 63 are window bytes len - 1 - at down to len - 64 - at: byte j of big-endian word k is byte 3 - j of little-endian dword 15 - k
-            uint32_t r[16];
-            __builtin_memcpy(r, s + (len - at - 64u), 64);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) w[k] = cds_rc_word(r[15 - k]);
-        }
-        sha1_block(h, w);
-    }
-    // tail: remaining bytes, 0x80, zeros, 64-bit big-endian bit length (one or two blocks)
-    const uint32_t rem = len - at;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = 0;
-    for (uint32_t k = 0; k < rem; ++k) {
-        const uint32_t b = rev ? cds_rc_byte(s[len - 1u - (at + k)]) : (uint32_t)s[at + k];
-        w[k >> 2] |= b << (24 - 8 * (k & 3));
-    }
-    w[rem >> 2] |= 0x80u << (24 - 8 * (rem & 3));
-    if (rem >= 56) {
-        sha1_block(h, w);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) w[k] = 0;
-    }
-    const uint64_t bits = (uint64_t)len * 8;
-    w[14] = (uint32_t)(bits >> 32);
-    w[15] = (uint32_t)bits;
-    sha1_block(h, w);
+    uint32_t h[5];
+    sha1_window(nt + it.at, it.len, it.rev != 0, h);
 #pragma unroll
     for (int k = 0; k < 5; ++k) digest[(size_t)i * 5 + k] = h[k];
 }
