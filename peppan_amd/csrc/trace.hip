@@ -192,19 +192,39 @@ __global__ __launch_bounds__(256) void gapless_check(const uint32_t *__restrict_
 
 // One THREAD per selected pair.  The walk is a serial chain of tiny decisions; spread over a wavefront (one alignment per wave, as the
 // first version did) every decision costs an issue slot of the whole CU - vector or scalar unit alike - and 40 k alignments took
-// 0.48 ms.  One alignment per lane instead; with all 64 lanes of a wave in use there are too few waves to hide the load latency
-// of the chain (0.15 ms), so a wave carries WALK_LANES alignments and the chip runs n / WALK_LANES waves.  A lane reads the code word of 8 consecutive
-// cells of its current diagonal (4 bytes) and fetches WALK_AHEAD words down that diagonal at once, so the latency of the scattered
-// 4-byte loads is paid once per 8 * WALK_AHEAD cells of a diagonal run, not once per word.  (Keeping single loads in flight across
-// iterations does not work: rotating the word registers reads them, which makes the compiler wait for every outstanding load.)
-#define WALK_AHEAD 8
-#ifndef WALK_LANES               // (16 and 32 measured at the end of round 3 with -DWALK_LANES: no difference, tools/ab/variants.sh)
-#define WALK_LANES 64         // alignments per wavefront: few, so that many wavefronts overlap their load latencies (see above)
+// 0.48 ms.  One alignment per lane instead, WALK_LANES alignments per wavefront, fewer than one wavefront per SIMD.  A wavefront that is
+// alone on its SIMD issues an instruction every dozen cycles, and it executes what ANY of its lanes needs: the kernel's time is the number
+// of instructions its wavefronts execute (about 5 ns each, fitted from two builds) plus their round trips to memory (about 0.6 us each), and the
+// loop is shaped to keep both chains short (profiles/walk_round_trips_ab.txt: 83.7 -> 50.1 us).
+//   * A lane holds a WINDOW of the codes: the words of WALK_AHEAD blocks down from the block of its cell, of FOUR neighbouring diagonals
+//     (one unaligned 16-byte load per block: the words of neighbouring diagonals of a block are neighbouring dwords).  A straight stretch
+//     runs down one column of the window; a gap moves the lane a column per cell, so a short gap and the stretch behind it cost no request
+//     (the window starts one diagonal below the lane's, two when the lane is inside a deletion, which moves it downwards).
+//   * The window lies in LDS, 16 bytes per lane and block, because a lane indexes it by its own block and diagonal.  In registers that is a
+//     4-way select per access and 28 moves per block (built first: the wavefronts' round trips fell from 26 to 8 and their instructions
+//     rose by half, 83.7 -> 106 us; the same had been found in round 3, DESIGN_HISTORY.md).  Nobody reads another lane's words: no barrier.
+//   * The loads are a ROUND of the wavefront: an outer loop that loads, an inner loop in which every lane steps until its cell leaves its
+//     window.  A lane that is through waits (masked off) for the others, so the round trips a wavefront pays are those of its lane with the
+//     most rounds - not, as with a refill inside the stepping loop, one per trip in which any lane needs memory.
+//   * A trip of the inner loop has one shape for every lane - a gap cell, or the diagonal cells down to the end of the NEXT word, found with
+//     one 64-bit count of leading zeros - and one branch, around the store of a run that has ended.  Before, a trip was a nest of branches
+//     (refill, state switch, word-by-word fast path) of which a wavefront ran nearly all, about 170 instructions; now it is about 75.
+//   * The loads of a round are unconditional (rows above block 0 read block 0 again and are not counted in `have`): a branch around a load
+//     makes hipcc wait for each load on its own.
+// Window depth, measured with -DWALK_AHEAD: 6 / 8 / 12 / 16 blocks -> 51.6 / 50.5 / 57.0 / 60.9 us - every block is a scattered request,
+// and a window is dropped when a gap leaves it sideways.  For the same reason the window behind the current one is NOT fetched ahead: it
+// would hide part of a round trip on a straight stretch and add eight requests to every round that ends sideways or ends the alignment.
+#ifndef WALK_AHEAD
+#define WALK_AHEAD 8          // blocks per window: 64 cells of a diagonal
+#endif
+#ifndef WALK_LANES               // (16 and 32 measured at the end of round 3 with -DWALK_LANES: no difference; 32 with the window in LDS: 49.5 against 50.5 us, none either)
+#define WALK_LANES 64         // alignments per wavefront
 #endif
 __global__ __launch_bounds__(WALK_LANES) void walk(const uint32_t *__restrict__ d_n_sel, SelInfo *__restrict__ sel, const uint64_t *__restrict__ cands, const int4 *__restrict__ sw,
                                            const uint64_t *__restrict__ dir_off, const uint32_t *__restrict__ dirs, const int32_t *__restrict__ mode,
                                            const uint64_t *__restrict__ run_off, uint32_t *__restrict__ runs)
 {
+    __shared__ uint32_t win[(WALK_AHEAD + 1) * 4 * WALK_LANES];
     const uint64_t s = (uint64_t)blockIdx.x * WALK_LANES + threadIdx.x;
     if (s >= *d_n_sel) return;
     SelInfo info = sel[s];
@@ -222,81 +242,67 @@ __global__ __launch_bounds__(WALK_LANES) void walk(const uint32_t *__restrict__ 
         return;
     }
     const int dlo = key_dlo(key) + (md > 0 ? 2 * md : 0);
-    const size_t row = md < 0 ? 128 : 64;
+    const int row = md < 0 ? 128 : 64;
     const int4 cell = sw[info.cand];
     const int a0 = cell.w;
-    // word of (block b, diagonal rel): dword ((b * lanes + (rel >> 1)) * 2 + (rel & 1)) of this pair's traceback area
+    // word of (block b, diagonal rel): dword ((b * lanes + (rel >> 1)) * 2 + (rel & 1)) = b * row + rel of this pair's traceback area
     const uint32_t *dir = dirs + dir_off[info.cand] * 128;
     uint32_t *out = runs + run_off[s];
 
+    uint32_t *const wl = win + threadIdx.x * 4;               // this lane's four dwords of row 0; row k lies k * 4 * WALK_LANES dwords on
     info.iend = cell.y; info.jend = cell.z;     // (the trace pass recomputes the same score)
     int i = info.iend, j = info.jend, state = 0;
     int istart = i, jstart = j;
     uint32_t n_runs = 0, aln_len = 0, cur_op = 3, cur_len = 0;
-    int cur_rel = -1, cur_blk = -1, have = 0;
-    uint32_t w[WALK_AHEAD];                                    // words of blocks cur_blk, -1, ... of diagonal cur_rel
+    bool done = false;
+    while (!done) {
+        // ---- a round: the window around cell (i, j), which is the (m & 7)-th cell of block m >> 3 of diagonal rel
+        const int rel0 = j - i - dlo;
+        const int top = (i - a0 + (rel0 >> 1)) >> 3;
+        if ((unsigned)rel0 >= (unsigned)row || top < 0) break;                  // (no path leaves its band: nothing is read outside the rows)
+        const int base = min(max(rel0 - (state == 1 ? 2 : 1), 0), row - 4);     // never in front of the row's first dword or behind its last
+        const uint32_t *col = dir + base;
+        uint4 v[WALK_AHEAD];
 #pragma unroll
-    for (int k = 0; k < WALK_AHEAD; ++k) w[k] = 0;
-    for (;;) {
-        // cell (i, j) is the (m & 7)-th cell of block m >> 3 of diagonal rel
-        const int rel = j - i - dlo;
-        const int m = i - a0 + (rel >> 1);
-        const int blk = m >> 3;
-        if (rel != cur_rel || blk != cur_blk) {
-            const uint32_t *col = dir + rel;
-            if (rel == cur_rel && blk == cur_blk - 1 && have > 1) {
-                // the next word down the same diagonal is already here (no load in flight: a refill waits for all of its loads)
+        for (int k = 0; k < WALK_AHEAD; ++k) __builtin_memcpy(&v[k], col + (size_t)max(top - k, 0) * row, 16);
 #pragma unroll
-                for (int k = 0; k + 1 < WALK_AHEAD; ++k) w[k] = w[k + 1];
-                --have;
-            } else {
-#pragma unroll
-                for (int k = 0; k < WALK_AHEAD; ++k) w[k] = blk >= k ? col[(size_t)(blk - k) * row] : 0u;
-                have = WALK_AHEAD;
-            }
-            cur_rel = rel; cur_blk = blk;
+        for (int k = 0; k < WALK_AHEAD; ++k) {
+            uint32_t *r = wl + k * 4 * WALK_LANES;
+            r[0] = v[k].x; r[1] = v[k].y; r[2] = v[k].z; r[3] = v[k].w;
         }
-        const uint32_t word = w[0];
-        const int nidx = m & 7;
-        const uint32_t nib = (word >> (nidx * 4)) & 15u;
-        uint32_t op, cnt = 1;
-        if (state == 0) {
+        const int have = min(WALK_AHEAD, top + 1);                              // the look-ahead ends at block 0
+        // ---- every lane steps until its cell leaves its window.  One trip takes a gap cell, or the diagonal cells from (i, j) on to the end of
+        // the NEXT word (two words side by side, one count of leading zeros), without a branch but for the run that has ended
+        for (;;) {
+            const int rel = j - i - dlo, c = rel - base;
+            const int m = i - a0 + (rel >> 1);
+            const int k = top - (m >> 3), nidx = m & 7;
+            if ((unsigned)c > 3u || (unsigned)k >= (unsigned)have) break;
+            const uint32_t *p = wl + k * 4 * WALK_LANES + c;
+            const uint32_t w0 = p[0], below = p[4 * WALK_LANES];                // (row WALK_AHEAD exists: read, not used)
+            const uint32_t w1 = k + 1 < have ? below : 0u;                      // a zero nibble is no diagonal code: the run stops at the window's end
+            const uint32_t nib = (w0 >> (nidx * 4)) & 15u;
             const uint32_t src = nib & 3u;
-            if (src == 0) break;
-            if (src != 1) { state = (src == 2) ? 1 : 2; continue; }
-            // follow the diagonal inside this word: up to nidx + 1 cells, never past row 0 / column 0
-            // (a zero nibble of x = a diagonal code; the cells of the word below this one are shifted to the top and counted at once)
+            const int st = state ? state : (int)src - 1;                        // 0: a diagonal cell, 1 / 2: a cell of a gap (a gap opens in the cell that names it), -1: the start
+            // a zero nibble of y = a diagonal code; the cells below (i, j) are shifted to the top and counted at once, never past row 0 / column 0
+            const uint64_t x = (((uint64_t)w0 << 32) | w1) << ((7 - nidx) * 4);
+            const uint64_t y = (x & 0x3333333333333333ull) ^ 0x1111111111111111ull;
             const int lim = min(i, j);
-            const uint32_t x = ((word & 0x33333333u) ^ 0x11111111u) << ((7 - nidx) * 4);
-            const int run = x ? (__clz(x) >> 2) : 8;
-            int r = min(min(run, nidx + 1), lim + 1);
-            // whole words of diagonal codes further down the same diagonal, as far as they are already here: a long ungapped stretch
-            // costs a handful of instructions per 8 cells instead of a trip through the general step
-            if (r == nidx + 1)
-                while (have > 1 && cur_blk > 0 && r + 8 <= lim + 1 && ((w[1] & 0x33333333u) ^ 0x11111111u) == 0u) {
-                    r += 8;
-#pragma unroll
-                    for (int k = 0; k + 1 < WALK_AHEAD; ++k) w[k] = w[k + 1];
-                    --have; --cur_blk;
-                }
-            op = 0; cnt = (uint32_t)r;
-            istart = i - r + 1; jstart = j - r + 1;
-        } else if (state == 1) {
-            op = 2; state = (nib & 4u) ? 1 : 0;
-        } else {
-            op = 1; state = (nib & 8u) ? 2 : 0;
+            const int run = min(y ? (__clzll((long long)y) >> 2) : 16, lim + 1);
+            const uint32_t op = st <= 0 ? 0u : 3u - (uint32_t)st, cnt = st == 0 ? (uint32_t)run : (st < 0 ? 0u : 1u);
+            aln_len += cnt;
+            if (op != cur_op && cnt) {                                          // (the one branch of a trip: a run has ended)
+                if (cur_len) out[n_runs++] = (cur_len << 2) | cur_op;
+                cur_op = op; cur_len = 0;
+            }
+            cur_len += cnt;
+            istart = st == 0 ? i - run + 1 : istart; jstart = st == 0 ? j - run + 1 : jstart;
+            done = st < 0 || (st == 0 && run > lim);                            // the start code, or the last cell of the run lies on row 0 or column 0
+            i -= st == 0 ? run : (st == 2 ? 1 : 0);
+            j -= st == 0 ? run : (st == 1 ? 1 : 0);
+            state = st > 0 && ((nib >> (st + 1)) & 1u) ? st : 0;                // bit 2 / bit 3: the gap goes on
+            if (done) break;
         }
-        aln_len += cnt;
-        if (op == cur_op) cur_len += cnt;
-        else {
-            if (cur_len) out[n_runs++] = (cur_len << 2) | cur_op;
-            cur_op = op; cur_len = cnt;
-        }
-        if (op == 0) {
-            if ((int)cnt > min(i, j)) break;            // the last cell of the run lies on row 0 or column 0
-            i -= (int)cnt; j -= (int)cnt;
-        } else if (op == 2) --j;
-        else --i;
     }
     if (cur_len) out[n_runs++] = (cur_len << 2) | cur_op;
     info.istart = istart; info.jstart = jstart; info.n_runs = n_runs; info.aln_len = aln_len;
