@@ -796,9 +796,9 @@ int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out)
     int rc = pep_find_candidates(ctx, &d_cands, &n_cands, prepare_thresholds, finish_targets);
     if (rc == PEP_OK) rc = finish_targets(ctx);
     pep_timer_end(ctx, TM_SEED);
-    if (rc == PEP_OK) rc = pep_extend(ctx, d_cands, n_cands, nullptr, res, true);
+    if (rc == PEP_OK) rc = pep_extend(ctx, d_cands, n_cands, nullptr, res, true, ctx->grp_nodes != 0);
     const bool grouped = rc == PEP_OK && ctx->grp_nodes != 0;
-    if (grouped)                                  // single linkage over the table that was just emitted, same stream, same wait
+    if (grouped)                                  // single linkage over the table that was just emitted, same stream, same wait (nothing left to queue where topk_emit and pack_out did it)
         rc = ctx->ext.pending ? pep_k10_queue(ctx, ctx->ext.n_bound, reinterpret_cast<const pep_hit *>(ctx->ext.d_hits), ctx->ext.d_n_hits)
                               : pep_k10_queue(ctx, res->n_hits, res->d_hits);
     // K7's count of identical nucleotide columns for every hit of this search (pep_set_nt_match), from the table on the device: same stream, same wait

@@ -156,7 +156,7 @@ struct NuclDesc { uint32_t seq, rev; };
 // search, with the reason the earlier tenant is dead by then.  The stand-alone calls name their slots in their own files and stay below PEP_WS_HITS_OUT.
 enum PepWsSlot {
     PEP_WS_BUCKET_CNT = 0,                  // entries per index bucket of the count -> scan -> fill build, u32: seed_count / seed_fill (seeds.hip), read last by seed_fill
-    PEP_WS_UF_PARENT = PEP_WS_BUCKET_CNT,   // K10's parent of every node, u32: pack_out / uf_init, read last by uf_flatten - the bucket counts are dead when the seed stage ends, the parents are written behind emit
+    PEP_WS_UF_PARENT = PEP_WS_BUCKET_CNT,   // K10's parent of every node, u32: finalize / uf_init, read last by pack_out / uf_flatten - the bucket counts are dead when the seed stage ends, the parents are written behind walk
     PEP_WS_IDX_START = 1,                   // first entry of every bucket, per seed shape, u32: idx_finish / the scan, read last by the matchers (seed_match, seed_match_stride)
     PEP_WS_IDX_ENTRIES = 2,                 // the query index's entries, per seed shape, u64: idx_finish / seed_fill, read last by the matchers
     // 3: free in the pipeline
@@ -177,11 +177,11 @@ enum PepWsSlot {
     PEP_WS_SW_SCAN_IN = 14,                 // blocks per candidate as the look-back scan's input, u64: sw_prep
     PEP_WS_SW_ORDER = 15,                   // the candidates by decreasing length, u32: sw_order, read last by the sweeps
     // 16 - 18: free
-    PEP_WS_SEL = 19,                        // the record of every selected pair, SelInfo: select_gather .. topk, read last by emit
-    PEP_WS_SEL_RUNS_KEYS = 20,              // run slot of every selected pair u64[n + 2], then their keys u64[n + 2]: select_gather, read last by emit
-    PEP_WS_RUNS = 21,                       // the CIGAR run arena of the selected pairs, u32: walk, read last by emit
-    PEP_WS_KEEP = 22,                       // keep flag u32, hit position u32, CIGAR position u64 per selected pair: topk, read last by emit
-    PEP_WS_HITS_OUT = 23,                   // the search's hit table, pep_hit[n_hits] + CIGAR runs u32: emit.  The one slot that outlives a call: intact while ctx->dev_result is set
+    PEP_WS_SEL = 19,                        // the record of every selected pair, SelInfo: select_gather .. finalize, read last by topk_emit (the exactly sized path: emit)
+    PEP_WS_SEL_RUNS_KEYS = 20,              // run slot of every selected pair u64[n + 2], then their keys u64[n + 2]: select_gather, read last by topk_emit / emit
+    PEP_WS_RUNS = 21,                       // the CIGAR run arena of the selected pairs, u32: walk, read last by topk_emit / emit
+    PEP_WS_KEEP = 22,                       // keep flag u32, hit position u32, CIGAR position u64 per selected pair: topk, read last by emit - the exactly sized path only (topk_emit hands nothing over)
+    PEP_WS_HITS_OUT = 23,                   // the search's hit table, pep_hit[n_hits] + CIGAR runs u32: topk_emit / emit.  The one slot that outlives a call: intact while ctx->dev_result is set
                                             // (pep_fetch_result and pep_k10_components_dev read it later), so whoever writes it calls pep_drop_dev_result first and every other user of ws stays below it
     PEP_WS_COUNT
 };
@@ -295,7 +295,7 @@ struct pep_ctx {
     uint64_t set_clean_slots = 0;           // leading slots of d_set known to be EMPTY (0 while a search is using it)
     DevBuf uf_nodes;                        // K10 over a device-resident hit table: node of every target (uploaded when it changes)
     std::vector<uint32_t> uf_nodes_host;
-    struct { bool pending = false; pep_result *res = nullptr; const void *d_hits = nullptr, *d_cig = nullptr; const uint32_t *d_n_hits = nullptr; uint64_t n_bound = 0; bool parent_ready = false; } ext;
+    struct { bool pending = false; pep_result *res = nullptr; const void *d_hits = nullptr, *d_cig = nullptr; const uint32_t *d_n_hits = nullptr; uint64_t n_bound = 0; bool grouped = false; } ext;
                                             // a search whose result left through pack_out and whose host half (sizes, statistics, views) is still to be done (pep_extend_finish)
     struct { void *d_dst = nullptr; const void *pinned_src = nullptr; uint64_t n_words = 0; } upload;   // an upload out of pinned memory that rides on the next read-back kernel
     bool want_nt_match = false;              // pep_set_nt_match: the searches of this context end with K7's count of identical nucleotide columns per hit (rescore.hip: pep_k7_hits_queue)
@@ -463,7 +463,9 @@ int pep_sw_run(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, bool trace, co
                const uint32_t *d_n = nullptr, uint64_t dir_blocks_bound = 0, unsigned long long **d_hdr = nullptr);   // kernel time: phase timers TM_SW / TM_SW_TRACE
 // h_min_score: score threshold per query; nullptr = ctx->d_min_score holds them already (pep_search uploads them while the seed stage runs)
 // defer: the caller waits for the stream itself and calls pep_extend_finish afterwards (pep_search: one wait for everything)
-int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n_cands, const int32_t *h_min_score, pep_result *res, bool defer = false);
+// group: the caller ends with K10 over this table (pep_set_grouping): where the result leaves through topk_emit / pack_out those two do the unions and the
+// labels on their way (ctx->ext.grouped says so; pep_k10_queue then queues nothing)
+int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n_cands, const int32_t *h_min_score, pep_result *res, bool defer = false, bool group = false);
 int pep_extend_finish(pep_ctx *ctx);
 int pep_selftest_dpp(pep_ctx *ctx);
 // ---- what another translation unit calls of a kernel's file (an exported function is defined in the file of its kernel and declared in the public header alone)
@@ -473,6 +475,43 @@ int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, cons
                            uint64_t n_targets, uint32_t *h_label);      // pep_components_of_result over a hit table that is still on the device (unionfind.hip)
 
 static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// In-matrix cells of a band: the diagonals dlo .. dlo + 127 (d = j - i) of an Lq x Lt matrix, clipped to dl = max(dlo, -(Lq - 1)) .. dh = min(dlo + 127, Lt - 1).
+// Diagonal d holds min(Lq, Lt - d) + min(0, d) cells; their sum in closed form (a loop over the 128 diagonals of every candidate was most of sw_prep's
+// time, and a wavefront per hit in the emit stage).  0 for a band that misses the matrix.
+__device__ __forceinline__ unsigned long long pep_band_cells(int Lq, int Lt, int dlo)
+{
+    const int dl = max(dlo, -(Lq - 1)), dh = min(dlo + 127, Lt - 1);
+    if (dl > dh) return 0ull;
+    auto tri = [](long long a, long long b) { return b < a ? 0ll : (a + b) * (b - a + 1) / 2; };      // a + (a + 1) + ... + b
+    const long long k = (long long)Lt - Lq;                       // min(Lq, Lt - d) = Lq for d <= k, Lt - d beyond
+    const long long flat_hi = min((long long)dh, k), slope_lo = max((long long)dl, k + 1);
+    long long total = (flat_hi >= dl ? (flat_hi - dl + 1) * (long long)Lq : 0ll);
+    if (slope_lo <= dh) total += (long long)(dh - slope_lo + 1) * Lt - tri(slope_lo, dh);
+    total += tri(dl, min((long long)dh, -1ll));                     // + d for the negative diagonals
+    return (unsigned long long)total;
+}
+
+// K10's lock-free union-find (unionfind.hip), for every kernel that unites or flattens: a union hooks the larger root under the smaller with an
+// atomic compare-and-swap, so the final root of a component is its smallest node id whatever the execution order
+__device__ __forceinline__ uint32_t uf_root(uint32_t *parent, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p == x) return x;
+        x = p;
+    }
+}
+__device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t x, uint32_t y)
+{
+    for (;;) {
+        x = uf_root(parent, x);
+        y = uf_root(parent, y);
+        if (x == y) return;
+        if (x < y) { const uint32_t t = x; x = y; y = t; }          // x = larger root, hooked under y
+        if (atomicCAS(&parent[x], x, y) == x) return;
+    }
+}
 int pep_upload_blk2seq(pep_ctx *ctx, SeqSet &s);
 // translate.hip, for the seed stage of a self-search (seeds.hip: self_prepare): K1 leaves ctx->d_self_t[g] = the packed sequence that frame 1 of reference sequence g
 // starts with (PEP_SELF_NONE: none); pep_self_map clears ctx->d_self_delta - one word per 32-byte block of the target layout, PEP_SELF_NO_DELTA - and says whether

@@ -312,36 +312,55 @@ __global__ __launch_bounds__(WALK_LANES) void walk(const uint32_t *__restrict__ 
 // identities + filters; FIN_LANES lanes per selected pair, parallel over the columns of each M run (a whole wavefront per pair meant
 // 38 k wavefronts that each lived for a chain of dependent loads: 0.039 ms; two pairs per wavefront: 0.031 ms, four: 0.030 ms but
 // slower once alignments are long)
+// An M run is compared four residues per lane and trip: one unaligned 4-byte load per side (the packed sets carry >= 16 bytes of padding behind
+// every sequence, so the last load of a run may reach up to 3 bytes past it), the equal bytes counted as the zero bytes of the XOR, the run's last
+// 1 - 3 columns by mask.  One byte per lane and trip was a chain of 11 dependent trips for a 330-column run; this is 3.
+// A chore rides along: the union-find behind it (topk_emit unites, pack_out flattens) gets its parent array initialised (iota).
 constexpr int FIN_LANES = 32;
+__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __global__ __launch_bounds__(256) void finalize(const uint32_t *__restrict__ d_n_sel, SelInfo *__restrict__ sel, const uint64_t *__restrict__ cands,
                                                 const uint8_t *__restrict__ q_res, const uint32_t *__restrict__ q_off, const uint32_t *__restrict__ q_len,
                                                 const uint8_t *__restrict__ t_res, const uint32_t *__restrict__ t_off,
-                                                const uint64_t *__restrict__ run_off, const uint32_t *__restrict__ runs, double min_id_pct, double min_qcov_pct)
+                                                const uint64_t *__restrict__ run_off, const uint32_t *__restrict__ runs, double min_id_pct, double min_qcov_pct,
+                                                uint32_t *__restrict__ iota, uint32_t n_iota)
 {
+    for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n_iota; x += gridDim.x * 256) iota[x] = x;
     const int lane = threadIdx.x & (FIN_LANES - 1);
     const uint64_t s = (uint64_t)blockIdx.x * (256 / FIN_LANES) + threadIdx.x / FIN_LANES;
     if (s >= *d_n_sel) return;                                // (whole lane groups leave together)
     const SelInfo info = sel[s];
-    const uint64_t key = cands[info.cand];
+    const uint64_t key = cands[s];                            // (info.cand == s, select_gather: the key, the record and the run slot leave in one round trip)
     const uint32_t q = key_q(key), t = key_t(key);
     const uint8_t *qs = q_res + q_off[q], *ts = t_res + t_off[t];
     const uint32_t *rv = runs + run_off[s];
+    const double Lq = (double)q_len[q];
     int i = info.istart, j = info.jstart;
     uint32_t ident = 0;
-    for (uint32_t r = 0; r < info.n_runs; ++r) {
-        const uint32_t run = rv[info.n_runs - 1 - r];     // the walk stored them end -> start
-        const int len = (int)(run >> 2);
-        const uint32_t op = run & 3u;
-        if (op == 0) {
-            for (int x = lane; x < len; x += FIN_LANES) ident += (qs[i + x] == ts[j + x]) ? 1u : 0u;
-            i += len; j += len;
-        } else if (op == 1) i += len;
-        else j += len;
+    for (uint32_t r0 = 0; r0 < info.n_runs; r0 += FIN_LANES) {
+        // the next FIN_LANES runs with one load, a run per lane, and handed round by lane shuffles: a load per run put a memory round trip
+        // between every two runs of the pair (the walk stored them end -> start)
+        const uint32_t nr = min((uint32_t)FIN_LANES, info.n_runs - r0);
+        const uint32_t mine = (uint32_t)lane < nr ? rv[info.n_runs - 1 - (r0 + lane)] : 0u;
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t run = __shfl(mine, (int)r, FIN_LANES);
+            const int len = (int)(run >> 2);
+            const uint32_t op = run & 3u;
+            if (op == 0) {
+                for (int x = lane * 4; x < len; x += FIN_LANES * 4) {
+                    const uint32_t d = load_u32_unaligned(qs + i + x) ^ load_u32_unaligned(ts + j + x);
+                    uint32_t z = ~(((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d | 0x7f7f7f7fu);      // 0x80 in every byte of d that is zero
+                    if (len - x < 4) z &= 0x80808080u >> (8 * (4 - (len - x)));               // columns behind the run do not count
+                    ident += (uint32_t)__popc(z);
+                }
+                i += len; j += len;
+            } else if (op == 1) i += len;
+            else j += len;
+        }
     }
     for (int d = FIN_LANES / 2; d > 0; d >>= 1) ident += __shfl_xor(ident, d, 64);
     if (lane == 0) {
         const double idp = (double)ident * 100.0 / (double)info.aln_len;
-        const double qcov = (double)(info.iend - info.istart + 1) * 100.0 / (double)q_len[q];
+        const double qcov = (double)(info.iend - info.istart + 1) * 100.0 / Lq;
         sel[s].n_ident = ident;
         sel[s].pass = (idp >= min_id_pct && qcov >= min_qcov_pct) ? 1u : 0u;
     }
@@ -437,6 +456,53 @@ __global__ __launch_bounds__(256) void apply_dedupe(const uint32_t *__restrict__
 // rank inside (query, target mod n_splits): score desc, target asc, band asc.  sel is ordered by (q, t, bin).
 // t_class (optional): competition class of every target = group * n_splits + (index inside the group) % n_splits, so that a
 // batch of reference sets (genomes) searched at once ranks exactly as if each had been searched alone
+// the top-k decision of selected pair s (me = sel[s], which passed its filters): its rank among the query's passing pairs of its competition class
+__device__ __forceinline__ uint32_t topk_keeps(const SelInfo &me, uint64_t s, uint64_t n_sel, const SelInfo *__restrict__ sel, const uint64_t *__restrict__ cands, int top_k, int n_splits,
+                                               uint32_t t_base, const uint32_t *__restrict__ t_class, const uint32_t *__restrict__ t_subject)
+{
+    // (the key of selected pair x is cands[x]: sel[x].cand == x, select_gather - so a neighbour's key and record are two loads side by side, not a chain)
+    const uint64_t key = cands[s];
+    const uint32_t q = key_q(key), t = key_t(key), split = t_class ? t_class[t] : (t + t_base) % (uint32_t)n_splits;
+    uint32_t rank = 0;
+    if (t_subject) {
+        // hsp_mode 2: top_k counts subjects.  This alignment's subject is as good as its best alignment (subject_best marked it: keep = 1);
+        // its rank = the subjects of the same query and class whose best alignment stands in front of that one
+        const uint32_t sj = t_subject[t];
+        int64_t mine = (int64_t)s;
+        int32_t mine_score = me.score;
+        if (!me.keep)
+            for (int dir = -1; dir <= 1 && mine == (int64_t)s; dir += 2)
+                for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
+                    const SelInfo o = sel[x];
+                    const uint64_t ko = cands[x];
+                    if (key_q(ko) != q) break;
+                    const uint32_t to = key_t(ko);
+                    if (o.pass && o.keep && t_subject[to] == sj && (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) == split) { mine = x; mine_score = o.score; break; }
+                }
+        for (int dir = -1; dir <= 1; dir += 2) {
+            for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
+                const SelInfo o = sel[x];
+                const uint64_t ko = cands[x];
+                if (key_q(ko) != q) break;
+                const uint32_t to = key_t(ko);
+                if (!o.pass || !o.keep || t_subject[to] == sj || (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) != split) continue;
+                if (o.score > mine_score || (o.score == mine_score && x < mine)) ++rank;
+            }
+        }
+    } else
+    for (int dir = -1; dir <= 1; dir += 2) {
+        for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
+            const SelInfo o = sel[x];
+            const uint64_t ko = cands[x];
+            if (key_q(ko) != q) break;
+            const uint32_t to = key_t(ko);
+            if (!o.pass || (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) != split) continue;
+            if (o.score > me.score || (o.score == me.score && (to < t || (to == t && x < (int64_t)s)))) ++rank;
+        }
+    }
+    return rank < (uint32_t)top_k ? 1u : 0u;
+}
+
 __global__ __launch_bounds__(256) void topk(const uint32_t *__restrict__ d_n_sel, SelInfo *__restrict__ sel, const uint64_t *__restrict__ cands, int top_k, int n_splits, uint32_t t_base,
                                             const uint32_t *__restrict__ t_class, uint32_t *__restrict__ keep_flag, uint32_t *__restrict__ hit_pos, uint64_t *__restrict__ cig_pos,
                                             const unsigned long long *__restrict__ score_hdr, const unsigned long long *__restrict__ trace_hdr, unsigned long long *__restrict__ mail,
@@ -460,48 +526,7 @@ __global__ __launch_bounds__(256) void topk(const uint32_t *__restrict__ d_n_sel
     uint64_t n_runs = 0;
     if (s < n_sel) {
         const SelInfo me = sel[s];
-        if (me.pass) {
-            const uint64_t key = cands[me.cand];
-            const uint32_t q = key_q(key), t = key_t(key), split = t_class ? t_class[t] : (t + t_base) % (uint32_t)n_splits;
-            uint32_t rank = 0;
-            if (t_subject) {
-                // hsp_mode 2: top_k counts subjects.  This alignment's subject is as good as its best alignment (subject_best marked it: keep = 1);
-                // its rank = the subjects of the same query and class whose best alignment stands in front of that one
-                const uint32_t sj = t_subject[t];
-                int64_t mine = (int64_t)s;
-                int32_t mine_score = me.score;
-                if (!me.keep)
-                    for (int dir = -1; dir <= 1 && mine == (int64_t)s; dir += 2)
-                        for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
-                            const SelInfo o = sel[x];
-                            const uint64_t ko = cands[o.cand];
-                            if (key_q(ko) != q) break;
-                            const uint32_t to = key_t(ko);
-                            if (o.pass && o.keep && t_subject[to] == sj && (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) == split) { mine = x; mine_score = o.score; break; }
-                        }
-                for (int dir = -1; dir <= 1; dir += 2) {
-                    for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
-                        const SelInfo o = sel[x];
-                        const uint64_t ko = cands[o.cand];
-                        if (key_q(ko) != q) break;
-                        const uint32_t to = key_t(ko);
-                        if (!o.pass || !o.keep || t_subject[to] == sj || (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) != split) continue;
-                        if (o.score > mine_score || (o.score == mine_score && x < mine)) ++rank;
-                    }
-                }
-            } else
-            for (int dir = -1; dir <= 1; dir += 2) {
-                for (int64_t x = (int64_t)s + dir; x >= 0 && x < (int64_t)n_sel; x += dir) {
-                    const SelInfo o = sel[x];
-                    const uint64_t ko = cands[o.cand];
-                    if (key_q(ko) != q) break;
-                    const uint32_t to = key_t(ko);
-                    if (!o.pass || (t_class ? t_class[to] : (to + t_base) % (uint32_t)n_splits) != split) continue;
-                    if (o.score > me.score || (o.score == me.score && (to < t || (to == t && x < (int64_t)s)))) ++rank;
-                }
-            }
-            keep = rank < (uint32_t)top_k ? 1u : 0u;
-        }
+        if (me.pass) keep = topk_keeps(me, s, n_sel, sel, cands, top_k, n_splits, t_base, t_class, t_subject);
         n_runs = keep ? me.n_runs : 0;
     }
     uint32_t tot_k;
@@ -563,6 +588,112 @@ __global__ __launch_bounds__(256) void emit(const uint32_t *__restrict__ d_n_sel
     (void)nblk;
 }
 
+// topk and emit in ONE launch, for the result that leaves through pack_out.  After its look-back a tile knows where its kept hits go: a
+// contiguous range of the hit table and a contiguous range of the arena.  So it writes them itself instead of handing keep flag, hit slot
+// and CIGAR slot of every pair to a wavefront-per-pair launch through global memory:
+//  - the owner of a kept hit builds the 64-byte record in LDS (cells: pep_band_cells, one thread instead of a wavefront's loop over the 128
+//    diagonals); the tile writes its records out 16 bytes per lane;
+//  - the tile's runs are copied by all threads, one run of the tile's arena range per thread and trip: the hit a run belongs to is found by
+//    bisection over the tile's scanned run counts in LDS (9 steps).  Pair by pair with lanes over runs would be a chain of up to 256 dependent
+//    round trips per tile for hits of 4 - 5 runs; this way every trip has 256 independent copies in flight, and a hit with more runs than the
+//    tile has threads is nothing special.  Reversed as emit does (the walk stored them end -> start);
+//  - the owner of a kept hit unites (q + q_base, node of t) where single linkage follows (parent != nullptr; finalize has set the parents);
+//  - the last tile writes the stage's counter block, complete, to mail_copy (outside the region pack_out clears).
+// The arena range of one tile is counted in 32 bits: the path is taken only below FAST_RUN_BYTES, 2^29 runs for the whole search.
+__global__ __launch_bounds__(256) void topk_emit(const uint32_t *__restrict__ d_n_sel, const SelInfo *__restrict__ sel, const uint64_t *__restrict__ cands, int top_k, int n_splits,
+                                                 uint32_t t_base, const uint32_t *__restrict__ t_class, const uint32_t *__restrict__ t_subject,
+                                                 const uint64_t *__restrict__ run_off, const uint32_t *__restrict__ runs, const uint32_t *__restrict__ q_len,
+                                                 const uint32_t *__restrict__ t_len, pep_hit *__restrict__ hits, uint32_t *__restrict__ cigar,
+                                                 const unsigned long long *__restrict__ score_hdr, const unsigned long long *__restrict__ trace_hdr,
+                                                 const unsigned long long *__restrict__ mail, unsigned long long *__restrict__ mail_copy,
+                                                 uint32_t *parent, uint32_t q_base, const uint32_t *__restrict__ node_of_target, SelectState st)
+{
+    static_assert(sizeof(pep_hit) == 64, "four 16-byte pieces per record");
+    __shared__ uint32_t s_tile, lds32[4];
+    __shared__ uint64_t lds64[4], s_pre[2];
+    __shared__ uint4 s_rec[256 * 4];             // the records of the tile's kept hits, in hit order
+    __shared__ uint64_t s_src[256];              // kept hit k: its first run in `runs` (the walk's order)
+    __shared__ uint32_t s_first[257];            // kept hit k: its first run in the tile's arena range; [kept hits] = the tile's runs
+    const uint32_t tile = lb_take_tile(st.count.state, st.count.ticket_base, &s_tile);
+    const uint64_t n_sel = *d_n_sel;
+    const uint64_t s = (uint64_t)tile * 256 + threadIdx.x;
+    uint32_t keep = 0;
+    uint64_t n_runs = 0;
+    SelInfo me = {};
+    if (s < n_sel) {
+        me = sel[s];
+        if (me.pass) keep = topk_keeps(me, s, n_sel, sel, cands, top_k, n_splits, t_base, t_class, t_subject);
+        n_runs = keep ? me.n_runs : 0;
+    }
+    uint32_t tot_k;
+    uint64_t tot_r;
+    const uint32_t ex_k = block_excl_scan_256<uint32_t>(keep, &tot_k, lds32);
+    const uint64_t ex_r = block_excl_scan_256<uint64_t>(n_runs, &tot_r, lds64);
+    if (threadIdx.x < 64) {
+        const uint64_t p0 = lb_tile_prefix<32>(st.count.status(), tile, tot_k, st.count.epoch, (int)threadIdx.x);
+        const uint64_t p1 = lb_tile_prefix<48>(st.runs.status(), tile, tot_r, st.runs.epoch, (int)threadIdx.x);
+        if (threadIdx.x == 0) { s_pre[0] = p0; s_pre[1] = p1; }
+    }
+    __syncthreads();
+    const uint64_t hit0 = s_pre[0], run0 = s_pre[1];
+    uint32_t node_q = 0, node_t = 0;
+    if (keep) {
+        const uint64_t key = cands[s];                    // (me.cand == s, select_gather)
+        const uint32_t q = key_q(key), t = key_t(key);
+        pep_hit h;
+        h.q = q; h.t = t;
+        h.q_start = (uint32_t)me.istart + 1; h.q_end = (uint32_t)me.iend + 1;
+        h.t_start = (uint32_t)me.jstart + 1; h.t_end = (uint32_t)me.jend + 1;
+        h.score = me.score; h.n_ident = me.n_ident; h.aln_len = me.aln_len; h.nm = me.aln_len - me.n_ident;
+        h.cigar_runs = me.n_runs; h.bin = (int32_t)(key & ((1u << 18) - 1)); h.cigar_off = run0 + ex_r;
+        h.cells = pep_band_cells((int)q_len[q], (int)t_len[t], key_dlo(key));
+        uint4 piece[4];
+        __builtin_memcpy(piece, &h, sizeof(h));
+#pragma unroll
+        for (int x = 0; x < 4; ++x) s_rec[ex_k * 4 + x] = piece[x];
+        s_src[ex_k] = run_off[s];
+        s_first[ex_k] = (uint32_t)ex_r;
+        if (parent) { node_q = q + q_base; node_t = node_of_target[t]; }
+    }
+    if (threadIdx.x == 0) s_first[tot_k] = (uint32_t)tot_r;
+    __syncthreads();
+    uint4 *hdst = reinterpret_cast<uint4 *>(hits + hit0);
+    for (uint32_t x = threadIdx.x; x < tot_k * 4; x += 256) hdst[x] = s_rec[x];
+    uint32_t *cdst = cigar + run0;
+    const uint32_t n_tile_runs = (uint32_t)tot_r;
+    for (uint32_t x0 = threadIdx.x; x0 < n_tile_runs; x0 += 4 * 256) {      // four copies per thread in flight
+        uint32_t v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t x = x0 + u * 256;
+            v[u] = 0;
+            if (x < n_tile_runs) {
+                uint32_t lo = 0, hi = tot_k;                                 // s_first[lo] <= x < s_first[hi]: the last hit that starts at or in front of x
+                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_first[mid] <= x) lo = mid; else hi = mid; }
+                const uint32_t first = s_first[lo], n = s_first[lo + 1] - first;
+                v[u] = runs[s_src[lo] + (n - 1 - (x - first))];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t x = x0 + u * 256;
+            if (x < n_tile_runs) cdst[x] = v[u];
+        }
+    }
+    if (keep && parent) uf_unite(parent, node_q, node_t);
+    if (tile == gridDim.x - 1 && threadIdx.x == 255) {
+        // the counter block the host reads with its last synchronisation (HostMail): the pair counts and the run capacity as select_gather left them,
+        // the hits and their CIGAR runs, the totals of the two Smith-Waterman passes
+        mail_copy[0] = mail[0];
+        mail_copy[1] = (unsigned long long)(uint32_t)(hit0 + tot_k) | ((unsigned long long)(uint32_t)score_hdr[7] << 32);      // hits, candidates the score pass settled without a sweep
+        mail_copy[2] = run0 + tot_r;
+        mail_copy[3] = mail[3];
+        mail_copy[4] = score_hdr[0]; mail_copy[5] = score_hdr[1];
+        mail_copy[6] = trace_hdr ? trace_hdr[0] : 0ull; mail_copy[7] = trace_hdr ? trace_hdr[1] : 0ull; mail_copy[8] = trace_hdr ? trace_hdr[5] : 0ull;
+        mail_copy[9] = score_hdr[6];                                         // cells of the settled candidates
+    }
+}
+
 // The result on its way to the host WITHOUT the host knowing its size: the counter block (72 bytes: hits, CIGAR runs, statistics), the
 // hit records and the CIGAR arena are written into the context's pinned staging area by this kernel - header (PACK_HEADER bytes), hits,
 // arena back to back - so that the search needs no synchronisation between its candidate count and its end.  A staging area that is too
@@ -570,13 +701,14 @@ __global__ __launch_bounds__(256) void emit(const uint32_t *__restrict__ d_n_sel
 // and copies the classic way.
 constexpr size_t PACK_HEADER = 128;
 // Two chores ride along (a launch of their own costs 4 - 5 us each): the counters of the NEXT search are cleared (zero_words: the region every
-// search needs zeroed - this is its last reader), and the union-find that follows gets its parent array initialised (iota).
+// search needs zeroed - this is its last reader), and single linkage ends here: every union of topk_emit is complete when this launch begins, so
+// the label of every node (its root) goes straight into the pinned label array (the body of uf_flatten; n_nodes = 0: no grouping).
 __global__ __launch_bounds__(256) void pack_out(const unsigned long long *__restrict__ mail, const pep_hit *__restrict__ hits, const uint32_t *__restrict__ cigar,
                                                 unsigned char *__restrict__ pinned, unsigned long long cap, uint32_t *__restrict__ zero_words, uint32_t n_zero_words,
-                                                uint32_t *__restrict__ iota, uint32_t n_iota)
+                                                uint32_t *parent, uint32_t *__restrict__ label, uint32_t n_nodes)
 {
     for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n_zero_words; x += gridDim.x * 256) zero_words[x] = 0u;
-    for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n_iota; x += gridDim.x * 256) iota[x] = x;
+    for (uint32_t x = blockIdx.x * 256 + threadIdx.x; x < n_nodes; x += gridDim.x * 256) label[x] = uf_root(parent, x);
     const uint32_t n_hits = reinterpret_cast<const uint32_t *>(mail)[2];
     const unsigned long long n_cig = mail[2];
     const bool fits = PACK_HEADER + (unsigned long long)n_hits * sizeof(pep_hit) + n_cig * 4 <= cap;
@@ -652,7 +784,7 @@ int pep_extend_finish(pep_ctx *ctx)
     return PEP_OK;
 }
 
-int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t *h_min_score, pep_result *res, bool defer)
+int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t *h_min_score, pep_result *res, bool defer, bool group)
 {
     const pep_search_params &P = ctx->params;
     pep_drop_dev_result(ctx);                     // PEP_WS_HITS_OUT is about to be rewritten
@@ -689,7 +821,7 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
     const uint32_t *d_n_sel = counters + 1;
     HostMail h_mail;
     std::memset(&h_mail, 0, sizeof(h_mail));
-    ctx->ext.pending = false;
+    ctx->ext.pending = ctx->ext.grouped = false;
     const unsigned gb = (unsigned)ceil_div(n, 256);
     // selection, compaction and the run slots of the selected pairs in one launch (select_gather); the arrays of the selected pairs are laid
     // out for n entries (every candidate selected) whatever the count turns out to be
@@ -737,11 +869,23 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
         PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_RUNS], (total_runs + 1) * 4));
         runs = ctx->ws[PEP_WS_RUNS].as<uint32_t>();
         const unsigned gfin = (unsigned)ceil_div(n_b, 256 / FIN_LANES);
+        // the result leaves through topk_emit and pack_out: no look at the sizes, no synchronisation behind the selection
+        const bool packed = fast && !ctx->device_results && pin_reserve(ctx, ctx->pin_stage, PACK_HEADER) == PEP_OK;
+        // ... and single linkage (pep_set_grouping) rides along: parents in finalize, unions in topk_emit, labels in pack_out.  Only with a node map
+        // that covers this search's queries and targets - pep_k10_queue refuses the others, and nothing may be united out of bounds before it does
+        uint32_t *parent = nullptr, *labels = nullptr;
+        if (packed && group && ctx->grp_nodes && ctx->uf_nodes_host.size() >= ctx->t.n && (uint64_t)ctx->q.n + ctx->grp_q_base <= ctx->grp_nodes &&
+            pin_reserve(ctx, ctx->pin_labels, (size_t)ctx->grp_nodes * 4) == PEP_OK) {
+            PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)ctx->grp_nodes * 4));
+            parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>();
+            labels = reinterpret_cast<uint32_t *>(ctx->pin_labels.p);
+        }
+        const uint32_t n_nodes = parent ? ctx->grp_nodes : 0u;
         hipLaunchKernelGGL(walk, dim3((unsigned)ceil_div(n_b, WALK_LANES)), dim3(WALK_LANES), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, sw2, ctx->ws[PEP_WS_SW_DIR_OFF].as<const uint64_t>(),
                            ctx->ws[PEP_WS_TRACE_DIRS].as<const uint32_t>(), ctx->d_trace_mode.as<const int32_t>(), (const uint64_t *)run_off, runs);
         hipLaunchKernelGGL(finalize, dim3(gfin), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, ctx->q.res.as<const uint8_t>(),
                            ctx->q.off.as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.res.as<const uint8_t>(),
-                           ctx->t.off.as<const uint32_t>(), (const uint64_t *)run_off, (const uint32_t *)runs, P.min_id_pct, P.min_qcov_pct);
+                           ctx->t.off.as<const uint32_t>(), (const uint64_t *)run_off, (const uint32_t *)runs, P.min_id_pct, P.min_qcov_pct, parent, n_nodes);
         const uint32_t *t_subject = nullptr;
         if (P.hsp_mode == 1) {
             hipLaunchKernelGGL(dedupe_bands, dim3((unsigned)ceil_div(n_b, 256)), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys);
@@ -760,38 +904,29 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
             hipLaunchKernelGGL(subject_best, dim3((unsigned)ceil_div(n_b, 256)), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, P.n_splits, (uint32_t)(P.t_index_base % P.n_splits),
                                ctx->t_class_ready ? ctx->d_t_class.as<const uint32_t>() : (const uint32_t *)nullptr, t_subject);
         }
-        // top-k, then compaction of hits and CIGAR runs
-        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_KEEP], ((size_t)n_b + 2) * (4 + 4 + 8)));
-        keep_flag = ctx->ws[PEP_WS_KEEP].as<uint32_t>(); hit_pos = keep_flag + n_b + 2;
-        cig_pos = reinterpret_cast<uint64_t *>(hit_pos + n_b + 2);
-        {
-            SelectState ts;
-            const uint64_t tiles = ceil_div(n_b, 256);
-            PEP_TRY(begin_select(ctx, PEP_LB_TOPK_HITS, PEP_LB_TOPK_RUNS, tiles, &ts));
-            hipLaunchKernelGGL(topk, dim3((unsigned)tiles), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, P.top_k, P.n_splits,
-                               (uint32_t)(P.t_index_base % P.n_splits), ctx->t_class_ready ? ctx->d_t_class.as<const uint32_t>() : (const uint32_t *)nullptr, keep_flag, hit_pos, cig_pos,
-                               (const unsigned long long *)score_hdr, (const unsigned long long *)trace_hdr, mail, ts, t_subject);
-        }
-        if (fast && !ctx->device_results && pin_reserve(ctx, ctx->pin_stage, PACK_HEADER) == PEP_OK) {
-            // the result leaves through pack_out: output buffers from the same upper bounds, no look at the sizes, no synchronisation here
+        const uint32_t t_base = (uint32_t)(P.t_index_base % P.n_splits);
+        const uint32_t *t_class = ctx->t_class_ready ? ctx->d_t_class.as<const uint32_t>() : (const uint32_t *)nullptr;
+        SelectState ts;
+        const uint64_t tiles = ceil_div(n_b, 256);
+        if (packed) {
+            // top-k, compaction and the table itself in one launch; output buffers from the same upper bounds as everything behind the selection
             const size_t hb_bound = (size_t)n_b * sizeof(pep_hit);
             PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_HITS_OUT], hb_bound + (run_bound + 1) * 4));
             pep_hit *d_hits = ctx->ws[PEP_WS_HITS_OUT].as<pep_hit>();
             uint32_t *d_cig = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ctx->ws[PEP_WS_HITS_OUT].p) + hb_bound);
             PEP_TRY(dev_reserve(ctx, ctx->d_mail_copy, 128));
             unsigned long long *mail_copy = ctx->d_mail_copy.as<unsigned long long>();
-            uint32_t *parent = nullptr;
-            if (ctx->grp_nodes) { PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)ctx->grp_nodes * 4)); parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>(); }      // (K10 follows: pep_k10_queue)
-            hipLaunchKernelGGL(emit, dim3((unsigned)ceil_div(n_b, 4)), dim3(256), 0, st, d_n_sel, (const SelInfo *)sel, (const uint64_t *)sel_keys, (const uint32_t *)keep_flag,
-                               (const uint32_t *)hit_pos, (const uint64_t *)cig_pos, (const uint64_t *)run_off, (const uint32_t *)runs,
-                               ctx->ws[PEP_WS_SW_NBLK].as<const uint32_t>(), ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig,
-                               (const unsigned long long *)mail, mail_copy);
+            PEP_TRY(begin_select(ctx, PEP_LB_TOPK_HITS, PEP_LB_TOPK_RUNS, tiles, &ts));
+            hipLaunchKernelGGL(topk_emit, dim3((unsigned)tiles), dim3(256), 0, st, d_n_sel, (const SelInfo *)sel, (const uint64_t *)sel_keys, P.top_k, P.n_splits, t_base, t_class, t_subject,
+                               (const uint64_t *)run_off, (const uint32_t *)runs, ctx->q.len.as<const uint32_t>(), ctx->t.len.as<const uint32_t>(), d_hits, d_cig,
+                               (const unsigned long long *)score_hdr, (const unsigned long long *)trace_hdr, (const unsigned long long *)mail, mail_copy,
+                               parent, ctx->grp_q_base, ctx->uf_nodes.as<const uint32_t>(), ts);
             hipLaunchKernelGGL(pack_out, dim3(1024), dim3(256), 0, st, (const unsigned long long *)mail_copy, (const pep_hit *)d_hits, (const uint32_t *)d_cig,
-                               ctx->pin_stage.p, (unsigned long long)ctx->pin_stage.cap, ctx->d_zero.as<uint32_t>(), (uint32_t)(PEP_ZERO_TOTAL / 4), parent, ctx->grp_nodes);
+                               ctx->pin_stage.p, (unsigned long long)ctx->pin_stage.cap, ctx->d_zero.as<uint32_t>(), (uint32_t)(PEP_ZERO_TOTAL / 4), parent, labels, n_nodes);
             PEP_HIP(ctx, hipGetLastError());
             ctx->ext.pending = true; ctx->ext.res = res; ctx->ext.d_hits = d_hits; ctx->ext.d_cig = d_cig;
             ctx->ext.d_n_hits = reinterpret_cast<const uint32_t *>(mail_copy) + 2; ctx->ext.n_bound = n_b;
-            ctx->ext.parent_ready = parent != nullptr;
+            ctx->ext.grouped = parent != nullptr;       // parents, unions and labels are queued: nothing is left for pep_k10_queue
             for (bool &f : ctx->zero_ok) f = true;   // as of this point of the stream every counter block is zero again (pack_out): whatever is queued
             ctx->zero_clean = true;                  // behind it - the next search, K9's alignment stage - needs no fill
             pep_timer_end(ctx, TM_TRACE);
@@ -799,6 +934,13 @@ int pep_extend(pep_ctx *ctx, const uint64_t *d_cands, uint64_t n, const int32_t 
             PEP_HIP(ctx, pep_stream_wait(ctx));
             return pep_extend_finish(ctx);
         }
+        // the exactly sized table: top-k and the two compactions, the sizes to the host, then emit into buffers of that size
+        PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_KEEP], ((size_t)n_b + 2) * (4 + 4 + 8)));
+        keep_flag = ctx->ws[PEP_WS_KEEP].as<uint32_t>(); hit_pos = keep_flag + n_b + 2;
+        cig_pos = reinterpret_cast<uint64_t *>(hit_pos + n_b + 2);
+        PEP_TRY(begin_select(ctx, PEP_LB_TOPK_HITS, PEP_LB_TOPK_RUNS, tiles, &ts));
+        hipLaunchKernelGGL(topk, dim3((unsigned)tiles), dim3(256), 0, st, d_n_sel, sel, (const uint64_t *)sel_keys, P.top_k, P.n_splits, t_base, t_class, keep_flag, hit_pos, cig_pos,
+                           (const unsigned long long *)score_hdr, (const unsigned long long *)trace_hdr, mail, ts, t_subject);
         PEP_TRY(pep_read_back(ctx, &h_mail, mail, sizeof(h_mail)));
         PEP_TRY(pep_sync_reads(ctx));
         n_hits = h_mail.n_hits; n_cig = h_mail.n_cig;

@@ -8,15 +8,7 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t uf_root(uint32_t *parent, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
+// (uf_root, uf_unite: common.h - the search's own kernels unite and flatten with them too)
 __global__ __launch_bounds__(256) void uf_init(uint32_t *parent, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -27,14 +19,7 @@ __global__ __launch_bounds__(256) void uf_union(uint32_t *parent, const uint32_t
 {
     const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= m) return;
-    uint32_t x = a[e], y = b[e];
-    for (;;) {
-        x = uf_root(parent, x);
-        y = uf_root(parent, y);
-        if (x == y) return;
-        if (x < y) { const uint32_t t = x; x = y; y = t; }          // x = larger root, hooked under y
-        if (atomicCAS(&parent[x], x, y) == x) return;
-    }
+    uf_unite(parent, a[e], b[e]);
 }
 
 // the same over the edges of a hit table that is still on the device: (hit.q + q_base, node_of_target[hit.t])
@@ -44,14 +29,7 @@ __global__ __launch_bounds__(256) void uf_union_hits(uint32_t *parent, const pep
     if (d_m) m = *d_m;                       // (the grid is sized from an upper bound then)
     const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= m) return;
-    uint32_t x = hits[e].q + q_base, y = node_of_target[hits[e].t];
-    for (;;) {
-        x = uf_root(parent, x);
-        y = uf_root(parent, y);
-        if (x == y) return;
-        if (x < y) { const uint32_t t = x; x = y; y = t; }
-        if (atomicCAS(&parent[x], x, y) == x) return;
-    }
+    uf_unite(parent, hits[e].q + q_base, node_of_target[hits[e].t]);
 }
 
 __global__ __launch_bounds__(256) void uf_flatten(uint32_t *parent, uint32_t *__restrict__ label, uint32_t n)
@@ -130,20 +108,21 @@ int pep_k10_components_dev(pep_ctx *ctx, uint32_t n_nodes, uint64_t n_hits, cons
     return PEP_OK;
 }
 
-// K10 as the tail of a search (pep_set_grouping): queued behind `emit` on the search's stream, BEFORE the search's final synchronisation -
+// K10 as the tail of a search (pep_set_grouping): queued behind the emit stage on the search's stream, BEFORE the search's final synchronisation -
 // no second call, no second wait, and uf_flatten writes the labels straight into pinned host memory (no blit behind it).  The labels are
-// in ctx->pin_labels once the stream has been waited for.
+// in ctx->pin_labels once the stream has been waited for.  A search whose result left through topk_emit / pack_out has done all of it already
+// (ctx->ext.grouped: parents in finalize, unions in topk_emit, labels in pack_out): nothing is queued then.
 int pep_k10_queue(pep_ctx *ctx, uint64_t n_hits, const pep_hit *d_hits, const uint32_t *d_n_hits)
 {
     const uint32_t n_nodes = ctx->grp_nodes;
     if (n_nodes == 0) return PEP_OK;
     if (ctx->uf_nodes_host.size() < ctx->t.n) return pep_fail(ctx, PEP_ERR_STATE, "pep_set_grouping: fewer node entries than the search has targets");
     if ((uint64_t)ctx->q.n + ctx->grp_q_base > n_nodes) return pep_fail(ctx, PEP_ERR_STATE, "pep_set_grouping: query nodes beyond n_nodes");
+    if (ctx->ext.pending && ctx->ext.grouped) return PEP_OK;
     PEP_TRY(dev_reserve(ctx, ctx->ws[PEP_WS_UF_PARENT], (size_t)n_nodes * 4));
     PEP_TRY(pin_reserve(ctx, ctx->pin_labels, (size_t)n_nodes * 4));
     uint32_t *parent = ctx->ws[PEP_WS_UF_PARENT].as<uint32_t>();
-    if (!(ctx->ext.pending && ctx->ext.parent_ready))          // (pack_out has initialised the parents on its way)
-        hipLaunchKernelGGL(uf_init, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, n_nodes);
+    hipLaunchKernelGGL(uf_init, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, n_nodes);
     if (n_hits) hipLaunchKernelGGL(uf_union_hits, dim3((unsigned)ceil_div(n_hits, 256)), dim3(256), 0, ctx->stream, parent, d_hits, n_hits, ctx->grp_q_base, ctx->uf_nodes.as<const uint32_t>(), d_n_hits);
     hipLaunchKernelGGL(uf_flatten, dim3((unsigned)ceil_div(n_nodes, 256)), dim3(256), 0, ctx->stream, parent, reinterpret_cast<uint32_t *>(ctx->pin_labels.p), n_nodes);
     PEP_HIP(ctx, hipGetLastError());
