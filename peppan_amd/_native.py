@@ -141,6 +141,14 @@ OUTALLELES_SIGNATURES = {
     'pep_out_alleles_check': (I, P, U32, U32, P, U32, P, P, U32, P, U64),
     'pep_out_alleles': (I, P, P, P, U32, U32, P, U32, P, P, I, U32, P, P, P, P, P),
 }
+# ... and of include/peppan_hip_treecut.h (K25), for the same reason; tests/test_treecut_host.py holds this one to the sixth header
+TREECUT_SIGNATURES = {
+    'pep_tree_cut': (I, P, P, U32, P, P, P, P, P, P, P, P, P, P, U32, P, P, P, P, P),
+    'pep_tree_cut_check': (I, P, U32, P, P, P, P, P, U32, P, U64),
+}
+CUT_AUTO, CUT_BLOCK, CUT_CHAIN = 0, 1, 2   # PEP_CUT_AUTO ..: the path of pep_tree_cut
+CUT_ROUND = 8                            # PEP_CUT_ROUND: iterations of a launch chain between two reads of its `done` flag
+CUT_DEFAULT_CAP = 3000                   # PEP_CUT_DEFAULT_CAP: the reference's iterations per component
 OUTA_COLS, OUTA_PLAN_COLS = 12, 6        # PEP_OUTA_COLS, PEP_OUTA_PLAN_COLS: int32 values of a row record and of a plan record
 OUTA_GENE, OUTA_CONTIG, OUTA_FLAGS, OUTA_S, OUTA_E, OUTA_PART, OUTA_QS, OUTA_QE, OUTA_REFLEN, OUTA_CLEN, OUTA_VARY, OUTA_SVMIN = range(12)     # PEP_OUTA_GENE ..
 OUTA_MISC, OUTA_NONAME, OUTA_SECONDARY, OUTA_MINUS = 1, 2, 4, 8                  # the bits of PEP_OUTA_FLAGS
@@ -268,7 +276,7 @@ def load_library():
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
     for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()) + \
-            list(OUTALLELES_SIGNATURES.items()):
+            list(OUTALLELES_SIGNATURES.items()) + list(TREECUT_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -738,6 +746,35 @@ def nj_trees_check(n_leaves, dist_off, out_off):
     if len(dist_off) != len(n) + 1 or len(out_off) != len(n) + 1:
         raise ValueError('nj_trees: dist_off and out_off need one entry more than n_leaves')
     _check_only('pep_nj_trees_check', _ptr(_some(n)), len(n), _ptr(dist_off), _ptr(out_off))
+
+
+def _tree_cut_tables(n_leaves, sets):
+    """the offsets tables of a pep_tree_cut / pep_tree_cut_check call laid out densely, and the bit sets as one array: sets[t] is uint64[B, words]"""
+    n = np.ascontiguousarray(n_leaves, dtype=np.uint32).reshape(-1)
+    if len(sets) != len(n):
+        raise ValueError('tree_cuts: one array of bit sets per tree')
+    sets = [np.ascontiguousarray(s, dtype=np.uint64) for s in sets]
+    for t, s in enumerate(sets):
+        if s.ndim != 2 or s.shape[1] != (int(n[t]) + 63) // 64:
+            raise ValueError('tree_cuts: the bit sets of tree %d are %s, not [branches, %d words]' % (t, s.shape, (int(n[t]) + 63) // 64))
+    n64 = n.astype(np.int64)
+    leaf_off = np.concatenate([[0], np.cumsum(n64)]).astype(np.uint64)
+    mat_off = np.concatenate([[0], np.cumsum(n64 * n64)]).astype(np.uint64)
+    branch_off = np.concatenate([[0], np.cumsum([len(s) for s in sets])]).astype(np.uint64)
+    set_off = np.concatenate([[0], np.cumsum([s.size for s in sets])]).astype(np.uint64)
+    flat = np.concatenate([s.reshape(-1) for s in sets]) if sets else np.zeros(0, np.uint64)
+    return n, leaf_off, mat_off, branch_off, set_off, _some(flat)
+
+
+def tree_cut_check(n_leaves, leaf_off, mat_off, branch_off, set_off, sets, path=0):
+    """the host checks of pep_tree_cut that read no matrix (no context, no device) on the caller's own tables: PepError with the library's code and text, else
+    None.  Every offsets table has one entry more than n_leaves; sets: the uint64 words of all bit sets; None for a table hands the library a null pointer"""
+    n = np.ascontiguousarray(n_leaves, dtype=np.uint32).reshape(-1)
+    tabs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (leaf_off, mat_off, branch_off, set_off, sets)]
+    for a in tabs[:4]:
+        if a is not None and len(a) != len(n) + 1:
+            raise ValueError('tree_cuts: every offsets table needs one entry more than n_leaves')
+    _check_only('pep_tree_cut_check', _ptr(_some(n)), len(n), *[None if a is None else _ptr(_some(a)) for a in tabs], int(path))
 
 
 def _gdiff_tables(events, arena):
@@ -1941,6 +1978,60 @@ class Context(object):
         self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off), _ptr(ms))
         self.nj_ms = (self.nj_ms[0] + float(ms[0]), self.nj_ms[1] + float(ms[1]))
         return [(node[int(a):int(b)], length[int(a):int(b)]) for a, b in zip(out_off[:-1], out_off[1:])]
+
+    # ---- K25
+    def tree_cuts(self, sets, lengths, w0, w1, strong, cap=CUT_DEFAULT_CAP, path=CUT_AUTO):
+        """the tree cutting of filt_per_group (PEPPAN.py:424-482) for a batch of trees, as include/peppan_hip_treecut.h states it.  Per tree: sets uint64[B, words],
+        the leaves on one side of every branch as bits; lengths float64[B]; w0, w1 float64[n, n], incompatible[:, :, 0] and [:, :, 1] compacted to the leaves;
+        strong bool[n]; cap: the iterations per component, one number or one per tree; path: CUT_AUTO, CUT_BLOCK, CUT_CHAIN.
+        -> per tree (part int32[n]: the leaf's component in the reference's output order, -1 for a dropped leaf; n_parts; n_cuts; n_ties; log_where
+        int32[n_cuts, 2]: component and lowest inducing branch of every cut; log_val float64[n_cuts, 4]: s0, s1, m, key).  Batches beyond the library's
+        PEP_NJ_MAX_BYTES of one matrix go to it in several calls.  The kernel times, summed over the library calls: self.cut_ms (the one-workgroup path with
+        the preparation, launch chains; zeros unless set_timing(2))."""
+        w0 = [np.ascontiguousarray(m, dtype=np.float64) for m in w0]
+        w1 = [np.ascontiguousarray(m, dtype=np.float64) for m in w1]
+        n_trees = len(w0)
+        if not (len(sets) == len(lengths) == len(w1) == len(strong) == n_trees):
+            raise ValueError('tree_cuts: one entry per tree in every list')
+        for t in range(n_trees):
+            if w0[t].ndim != 2 or w0[t].shape[0] != w0[t].shape[1] or w1[t].shape != w0[t].shape:
+                raise ValueError('tree_cuts: the matrices of tree %d are %s and %s, not two squares of one size' % (t, w0[t].shape, w1[t].shape))
+        caps = np.broadcast_to(np.asarray(cap, dtype=np.int64), (n_trees,))
+        if n_trees and (caps.min() < 0 or caps.max() >= 1 << 32):
+            raise ValueError('tree_cuts: cap is 0 .. 2^32 - 1')
+        sizes = [m.size * 8 for m in w0]
+        self.cut_ms = (0., 0.)
+        results, lo = [], 0
+        while lo < n_trees:
+            hi, total = lo + 1, sizes[lo]                             # (a matrix beyond the budget goes alone: the library refuses it in its words)
+            while hi < n_trees and total + sizes[hi] <= NJ_MAX_BYTES:
+                total += sizes[hi]
+                hi += 1
+            results += self._tree_cuts_call(sets[lo:hi], lengths[lo:hi], w0[lo:hi], w1[lo:hi], strong[lo:hi], caps[lo:hi], path)
+            lo = hi
+        return results
+
+    def _tree_cuts_call(self, sets, lengths, w0, w1, strong, caps, path):
+        n, leaf_off, mat_off, branch_off, set_off, flat = _tree_cut_tables([len(m) for m in w0], sets)
+        _check_only('pep_tree_cut_check', _ptr(n), len(n), _ptr(leaf_off), _ptr(mat_off), _ptr(branch_off), _ptr(set_off), _ptr(flat), int(path))
+        lengths = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in lengths]
+        strong = [np.ascontiguousarray(x).astype(bool).astype(np.uint8).reshape(-1) for x in strong]
+        for t in range(len(n)):
+            if len(lengths[t]) != int(branch_off[t + 1] - branch_off[t]) or len(strong[t]) != int(n[t]):
+                raise ValueError('tree_cuts: tree %d needs one length per branch and one strong flag per leaf' % t)
+        length, w0, w1, strong = (np.concatenate([x.reshape(-1) for x in xs]) for xs in (lengths, w0, w1, strong))
+        caps = np.ascontiguousarray(caps, dtype=np.uint32)
+        n_leaf = int(leaf_off[-1])
+        part, counts = np.full(n_leaf, -1, np.int32), np.zeros((len(n), 4), np.int32)
+        log_where, log_val, ms = np.zeros((n_leaf, 2), np.int32), np.zeros((n_leaf, 4), np.float64), np.zeros(4)
+        self._call('pep_tree_cut', _ptr(n), len(n), _ptr(leaf_off), _ptr(mat_off), _ptr(branch_off), _ptr(set_off), _ptr(flat), _ptr(length), _ptr(w0), _ptr(w1),
+                   _ptr(strong), _ptr(caps), int(path), _ptr(part), _ptr(counts), _ptr(log_where), _ptr(log_val), _ptr(ms))
+        self.cut_ms = (self.cut_ms[0] + float(ms[0]), self.cut_ms[1] + float(ms[1]))
+        out = []
+        for t, (a, b) in enumerate(zip(leaf_off[:-1], leaf_off[1:])):
+            a, cuts = int(a), int(counts[t, 1])
+            out.append((part[a:int(b)], int(counts[t, 0]), cuts, int(counts[t, 2]), log_where[a:a + cuts], log_val[a:a + cuts]))
+        return out
 
     # ---- K23
     def cds_genes(self, nt, contig_off, contig, win_off, win_len, strand, min_cds=0, mask=0, table4=False):

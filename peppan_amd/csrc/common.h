@@ -321,6 +321,7 @@ struct pep_ctx {
     uint64_t k22_n_keys = 0;                 // the keys the newest pep_global_diff left on the device, waiting for pep_global_diff_copy
     DevBuf k22[13];                          // grow-only, pep_global_diff: events, arena, the per-key tables, a chunk's sort buffers, the value lists and the sums (the slots: globaldiff.hip)
     DevBuf k23[4];                           // grow-only, pep_cds_genes: the contig arena, the item records, the codes and the digests (the slots: cdsgenes.hip)
+    DevBuf k25[15];                          // grow-only, pep_tree_cut: the matrices, the bit sets, the tree records, the scores, the outputs and the state of a launch chain (the slots: treecut.hip)
     // stats of the last search
     pep_stats stats;
     ~pep_ctx();                 // what only the context can do before its members release themselves: its device current, the results that point into it cut loose

@@ -17,7 +17,7 @@ Deviation from rapidnj, on purpose: a pair of rows with no shared column, or so 
 value from rapidnj (0.478556 where it was probed) and a tree is built on it; here such a pair is undefined, kimura_distances marks it, and gene_trees
 gives the group no tree - the caller then does what PEPPAN.py:419-421 do when the tree fails and keeps the group whole.
 
-Not here: cutting the tree (PEPPAN.py:424-482, ete3) and FastTree."""
+Cutting the tree (PEPPAN.py:424-482, ete3 there) is K25: treecut.py, orthofilter.cut_groups.  Not here: FastTree."""
 import collections
 
 import numpy as np

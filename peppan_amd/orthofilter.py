@@ -5,12 +5,16 @@
     group_verdicts              PEPPAN.py:335-392: what filt_per_group decides from those differences, decided on the GPU (K16); per-pair data
                                 comes back only for the groups that go on to the tree test
     group_trees                 PEPPAN.py:393-417: the neighbour-joining tree text of those groups (K21, njtree.py)
+    cut_groups                  PEPPAN.py:424-482: the trees cut at their incompatible branches (K25, treecut.py), the list of matrices of every group
+    filt_per_groups             all of filt_per_group for a whole `to_run` list: the drop-in for the imap_unordered of :626
     gd_table, distances_from_diff, incompatible_of   the host halves of it (the exp() per genome pair; :371-380; :400-406)
 
 Both counts are sums over columns, so the rows never leave the base-5 packing of the .seq store (mapbsn.encodeSeq): K15
 (csrc/allelediff.hip, Context.allele_diff) turns the packed bytes into bit planes and counts with population counts.  The float layer
 of filt_per_group up to the decision to build a tree is K16 (csrc/divergence.hip, Context.group_verdicts); the tree text is K21 (njtree.py);
-the cutting of the tree is not here: see DESIGN.md section 8.  There is no CPU fallback.
+the cutting of the tree is K25 (treecut.py), which needs no ete3.  Not here: `--orthology ml` (FastTree), and the reference's choice where two
+different branches tie exactly in both sort keys of :458, which depends on ete3's rooting - such ties are counted, see DESIGN.md section 8.
+There is no CPU fallback.
 The drop-ins and group_differences share one cached context per process and device; close() releases it.
 """
 import collections
@@ -22,7 +26,7 @@ from . import _native as N
 from .mapbsn import MapBsn
 
 __all__ = ['compare_seq', 'compare_seqX', 'group_differences', 'iter_group_differences', 'pack_rows', 'close',
-           'group_verdicts', 'group_trees', 'gd_table', 'distances_from_diff', 'incompatible_of', 'GdTable', 'GroupVerdict']
+           'group_verdicts', 'group_trees', 'cut_groups', 'mats_of_cut', 'filt_per_groups', 'gd_table', 'distances_from_diff', 'incompatible_of', 'GdTable', 'GroupVerdict']
 
 _CODE = np.full(256, 255, dtype=np.uint8)
 _CODE[[0, 65, 67, 71, 84]] = (0, 1, 2, 3, 4)
@@ -261,7 +265,7 @@ def group_verdicts(seq_store, to_run_groups, global_differences, params, detail=
     params: self_id and allowed_sigma.  -> one GroupVerdict per group.  The packed rows go from the store to ONE Context.group_verdicts
     batch; the device decides every verdict, and per-pair data comes back only for verdict 2 (when detail): diff float64[n, n, 2] as :370
     leaves it, groups as :383-392 leave them, distances (:371-380, by distances_from_diff on the host) and incompatible / needs_tree
-    (:400-406).  The tree and its cutting (:409-482) stay with the caller."""
+    (:400-406).  The tree and its cutting (:409-482) are group_trees and cut_groups; filt_per_groups runs all three."""
     gd = global_differences if isinstance(global_differences, GdTable) else gd_table(global_differences, params['self_id'], params['allowed_sigma'])
     mats = [np.asarray(t[0]) for t in to_run_groups]
     packed, row_off, row_len, groups = _read_groups(seq_store, mats, [t[2] for t in to_run_groups])
@@ -283,3 +287,59 @@ def group_verdicts(seq_store, to_run_groups, global_differences, params, detail=
             v.incompatible, v.needs_tree = incompatible_of(v.distances, v.groups)
         out.append(v)
     return out
+
+
+def mats_of_cut(mat, groups, leaves, part, n_parts):
+    """PEPPAN.py:474-482: the matrices of one group from the partition of its tree's leaves.  groups: as :383-392 leave them (g[0] the leader); leaves: the
+    leader rows in the order of `part`; part[i]: the component of leaves[i] in the order of the reference's queue, -1 for a dropped leaf.  Component by
+    component the rows of its leaders' groups, sorted; `mat` itself for a component that holds every leaf."""
+    members = {int(g[0]): g for g in groups}
+    mats = []
+    for q in range(int(n_parts)):
+        tips = [int(a) for a, p in zip(leaves, part) if p == q]
+        if len(tips) < len(groups):
+            mats.append(mat[sorted(nn for a in tips for nn in members.get(a, []))])
+        else:
+            mats.append(mat)
+    return mats
+
+
+def cut_groups(to_run_groups, verdicts, texts, params, cap=3000, path=0, device=None, detail=False):
+    """PEPPAN.py:424-482 behind group_trees for a whole `to_run` list in ONE K25 batch (treecut.cut_trees, which see): per group the list of matrices
+    filt_per_group returns.  verdicts: group_verdicts' (detail=True); texts: group_trees'; params: clust_identity.  A group without a tree text - verdict 0
+    or 1, no incompatible pair of leaders, or a tree that failed - gives [mat] (:368, :407, :419-421, :484).  detail=True: (that list, per group the
+    treecut.CutResult or None)."""
+    from .treecut import cut_trees
+    if not (len(to_run_groups) == len(verdicts) == len(texts)):
+        raise ValueError('cut_groups: one verdict and one text (or None) per group')
+    wanted = [k for k, text in enumerate(texts) if text is not None]
+    bound = (params['clust_identity'] - 0.02) * 10000
+    leaders = [[int(g[0]) for g in verdicts[k].groups] for k in wanted]
+    strong = [np.asarray(to_run_groups[k][0])[lead, 4].astype(np.float64) >= bound for k, lead in zip(wanted, leaders)]
+    cuts = cut_trees([texts[k] for k in wanted], [verdicts[k].incompatible for k in wanted], leaders, strong, cap, path, device)
+    out, found = [[t[0]] for t in to_run_groups], [None] * len(to_run_groups)
+    for k, c in zip(wanted, cuts):
+        out[k] = mats_of_cut(to_run_groups[k][0], verdicts[k].groups, c.leaves, c.part, c.n_parts)
+        found[k] = c
+    return (out, found) if detail else out
+
+
+def filt_per_groups(seq_store, to_run, global_differences, params, device=None):
+    """The drop-in for `pool.imap_unordered(filt_per_group, to_run)` (PEPPAN.py:626) with `--orthology nj`: group_verdicts, group_trees, cut_groups.
+
+    seq_store, to_run, global_differences: as for group_verdicts (to_run: per group (mat, inparalog, ref_len, ...)); params: self_id, allowed_sigma,
+    clust_identity and orthology.  -> (per group, in the order given, the list of matrices filt_per_group returns; n_ties: how often two different
+    branches tied exactly in both sort keys of :458, where the reference's choice depends on ete3's rooting and this project's own rule decided).
+    orthology 'ml' sends every tree of fewer than 500 tags to FastTree (:415), which is not restated: NotImplementedError when such a group is met."""
+    orthology = params.get('orthology', 'nj')
+    if orthology not in ('nj', 'ml', 'sbh'):
+        raise ValueError('filt_per_groups: orthology is nj, ml or sbh, not %r' % (orthology,))
+    verdicts = group_verdicts(seq_store, to_run, global_differences, params, detail=True, device=device)
+    if orthology == 'ml':                                # (sbh never reaches filt_per_group: filt_genes is not run for it)
+        for k, v in enumerate(verdicts):
+            if v.verdict == 2 and v.needs_tree and len(v.groups) < 500:
+                raise NotImplementedError('filt_per_groups: group %d has %d tags, and --orthology ml builds the tree of fewer than 500 tags with FastTree '
+                                          '(PEPPAN.py:415), which is not restated; only rapidnj (nj) is' % (k, len(v.groups)))
+    texts, _ = group_trees(seq_store, to_run, verdicts, device)
+    out, found = cut_groups(to_run, verdicts, texts, params, device=device, detail=True)
+    return out, sum(c.n_ties for c in found if c is not None)

@@ -1,0 +1,322 @@
+"""What the K25 tests share: the numpy restatement of the tree cutting as include/peppan_hip_treecut.h defines it, the builders of the test trees and
+matrices, and the named edge cases.
+
+The restatement is the definition the device is held to bit for bit: float64 throughout, every operation one numpy operation, the three sums in the
+header's order - per row 64 lane sums over the columns l, l + 64, .., the shuffle tree of offsets 32 .. 1, then the rows in ascending order from 0.0.
+It also reports what the fixtures are pinned by: how close a candidate's ic0 came to 1, how close the runner-up came to the winner, and how often two
+branches induced one restricted bipartition."""
+import gzip
+import json
+import os
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, 'golden', 'g28_treecut.json.gz')
+_LANES = np.arange(64)
+
+
+def pair_sum(X, rows, cols):
+    """the header's sum of X over rows x cols (rows: ascending indices, cols: a mask)"""
+    n = X.shape[0]
+    K = (n + 63) // 64
+    Y = np.zeros((len(rows), K * 64))
+    Y[:, :n] = np.where(cols[None, :], X[rows], 0.0)       # (0.0 + x and p + 0.0 leave the bits of a sum of non-negative terms alone: a column outside is skipped)
+    Y = Y.reshape(len(rows), K, 64)
+    p = np.zeros((len(rows), 64))
+    for k in range(K):
+        p = p + Y[:, k, :]
+    for off in (32, 16, 8, 4, 2, 1):
+        p = p + p[:, _LANES ^ off]
+    s = np.float64(0.0)
+    for r in p[:, 0]:
+        s = s + r
+    return s
+
+
+def cut_restated(sides, lengths, W0, W1, strong, cap=3000, report=None):
+    """sides bool[B, n]: the leaves on one side of every branch; lengths float64[B]; W0, W1 float64[n, n]; strong bool[n] -> dict(part int32[n], n_parts,
+    n_cuts, n_ties, log_where int32[n_cuts, 2], log_val float64[n_cuts, 4]).  report: a dict that receives ic0_margin (the smallest |ic0 - 1| / 1 of any
+    candidate), gap (the smallest relative distance of a runner-up's (key, ic0) from the winner's), merged (cuts whose winner was induced by more than one
+    branch) and scored (iterations that scored candidates)."""
+    with np.errstate(all='ignore'):
+        return _cut_restated(np.asarray(sides, bool), np.asarray(lengths, np.float64), np.asarray(W0, np.float64), np.asarray(W1, np.float64),
+                             np.asarray(strong, bool), int(cap), report)
+
+
+def _cut_restated(sides, lengths, W0, W1, strong, cap, report):
+    B, n = sides.shape
+    G = W0 > W1
+    M = np.where(G, W1, 0.0)
+    part = np.zeros(n, np.int32)
+    nq = 1
+    n_ties = 0
+    where, val = [], []
+    ic0_margin, gap, merged, scored = np.inf, np.inf, 0, 0
+    q = 0
+    while q < nq:
+        for _ in range(cap):
+            T = part == q
+            idx = np.flatnonzero(T)
+            if not G[np.ix_(idx, idx)].any():
+                break
+            t0 = idx[0]
+            cands = {}
+            for e in range(B):
+                F = (T & ~sides[e]) if sides[e, t0] else (T & sides[e])
+                if not F.any():
+                    continue
+                key_of = F.tobytes()
+                if key_of in cands:
+                    c = cands[key_of]
+                    c['len'] = c['len'] + lengths[e]
+                    c['n'] += 1
+                    continue
+                rows, cols = np.flatnonzero(F), T & ~F
+                s0, s1, m = pair_sum(W0, rows, cols), pair_sum(W1, rows, cols), pair_sum(M, rows, cols)
+                ic0 = s0 / (s1 if s1 > 1.0 else np.float64(1.0))
+                cands[key_of] = dict(e=e, F=F, len=np.float64(0.0) + lengths[e], n=1, s0=s0, s1=s1, m=m, ic0=ic0, key=ic0 * np.sqrt(m), minf=int(rows[0]))
+            scored += 1
+            for c in cands.values():
+                ic0_margin = min(ic0_margin, abs(float(c['ic0']) - 1.0))
+            good = [c for c in cands.values() if c['ic0'] > 1.0 and c['key'] == c['key']]
+            if not good:
+                break
+            top = max((c['key'], c['ic0']) for c in good)
+            final = [c for c in good if (c['key'], c['ic0']) == top]
+            for c in good:
+                if (c['key'], c['ic0']) != top:
+                    rel = abs(top[0] - c['key']) / abs(top[0]) if c['key'] != top[0] else abs(top[1] - c['ic0']) / abs(top[1])
+                    gap = min(gap, float(rel))
+            n_ties += len(final) - 1
+            win = min(final, key=lambda c: (-c['len'], c['minf'], c['e']))
+            merged += int(win['n'] > 1)
+            F = win['F']
+            if strong[F].any():
+                part[F] = nq
+                nq += 1
+            else:
+                part[F] = -1
+            where.append((q, win['e']))
+            val.append((win['s0'], win['s1'], win['m'], win['key']))
+        q += 1
+    if report is not None:
+        report.update(ic0_margin=ic0_margin, gap=gap, merged=merged, scored=scored)
+    return dict(part=part, n_parts=nq, n_cuts=len(where), n_ties=n_ties, log_where=np.array(where, np.int32).reshape(-1, 2),
+                log_val=np.array(val, np.float64).reshape(-1, 4))
+
+
+def sets_of(sides):
+    """bool[B, n] -> uint64[B, words], leaf l as bit l % 64 of word l / 64"""
+    sides = np.asarray(sides, bool)
+    B, n = sides.shape
+    words = (n + 63) // 64
+    full = np.zeros((B, words * 64), bool)
+    full[:, :n] = sides
+    return (full.reshape(B, words, 64).astype(np.uint64) << np.arange(64, dtype=np.uint64)).sum(axis=2, dtype=np.uint64)
+
+
+def sides_of(sets, n):
+    """the inverse of sets_of"""
+    sets = np.asarray(sets, np.uint64)
+    bits = (sets[:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+    return bits.reshape(len(sets), -1)[:, :n].astype(bool)
+
+
+def same_result(got, want):
+    """a device result (part, n_parts, n_cuts, n_ties, log_where, log_val) against the restatement's dict, the doubles bit for bit -> the first difference
+    as text, or None"""
+    part, n_parts, n_cuts, n_ties, where, val = got
+    if (n_parts, n_cuts, n_ties) != (want['n_parts'], want['n_cuts'], want['n_ties']):
+        return 'counts %r, restated %r' % ((n_parts, n_cuts, n_ties), (want['n_parts'], want['n_cuts'], want['n_ties']))
+    if not np.array_equal(part, want['part']):
+        return 'part %r, restated %r' % (part.tolist(), want['part'].tolist())
+    if not np.array_equal(where, want['log_where']):
+        return 'cut log %r, restated %r' % (where.tolist(), want['log_where'].tolist())
+    if val.tobytes() != want['log_val'].tobytes():
+        return 'cut log doubles %r, restated %r' % (val.tolist(), want['log_val'].tolist())
+    return None
+
+
+# ---- builders
+
+def tree_of_clusters(rng, clusters, n, flip=True):
+    """an unrooted binary tree over leaves 0 .. n - 1 in which every cluster (a list of leaves) is a clade: joined at random within the clusters, then
+    between them -> (sides bool[B, n], lengths as printed with %.5g); B = 2 n - 3 (2 for n = 2), and 2 n - 2 with two clusters: the branch between them is
+    then given twice, as the two children of a root are.  flip: every other side is given as its complement"""
+    if len(clusters) == 1:
+        clusters = [[a] for a in clusters[0]]
+    def leaf(a):
+        m = np.zeros(n, bool)
+        m[a] = True
+        return m
+
+    sides = []
+
+    def join(nodes, down_to):
+        nodes = list(nodes)
+        while len(nodes) > down_to:
+            i, j = sorted(rng.choice(len(nodes), 2, replace=False).tolist())
+            b, a = nodes.pop(j), nodes.pop(i)
+            sides.extend([a, b])
+            nodes.append(a | b)
+        return nodes
+
+    tops = []
+    for c in clusters:
+        tops += join([leaf(a) for a in c], 1)
+    rest = join(tops, 3 if n > 2 else 2)
+    sides.extend(rest)
+    sides = np.array(sides)
+    assert len(sides) == (2 if n == 2 else 2 * n - 2 if len(clusters) == 2 else 2 * n - 3)
+    if flip:
+        sides[::2] = ~sides[::2]
+    lengths = np.array([float('%.5g' % x) for x in rng.random(len(sides)) * 0.3])
+    return sides, lengths
+
+
+def dyadic_matrices(rng, clusters, n, within=(0, 3), between=(40, 90), bound=32, noise=0):
+    """W0, W1 as multiples of 2^-10 (every sum of them exact in any order): W1 = bound everywhere, W0 low within a cluster and high between clusters;
+    `noise` random pairs within clusters are lifted beyond the bound as well.  Symmetric, zero diagonals."""
+    label = np.zeros(n, np.int64)
+    for k, c in enumerate(clusters):
+        label[list(c)] = k
+    same = label[:, None] == label[None, :]
+    lo = rng.integers(within[0] * 1024, within[1] * 1024 + 1, (n, n)) / 1024.0
+    hi = rng.integers(between[0] * 1024, between[1] * 1024 + 1, (n, n)) / 1024.0
+    W0 = np.where(same, lo, hi)
+    for _ in range(noise):
+        a, b = rng.integers(0, n, 2)
+        if a != b and same[a, b]:
+            W0[a, b] = bound + 1 + rng.integers(0, 1024) / 1024.0
+    W0 = np.triu(W0, 1)
+    W0 = W0 + W0.T
+    W1 = np.full((n, n), float(bound))
+    np.fill_diagonal(W1, 0.0)
+    return W0, W1
+
+
+def float_matrices(rng, clusters, n):
+    """the same shape of problem in general doubles"""
+    W0, W1 = dyadic_matrices(rng, clusters, n)
+    f = np.triu(rng.random((n, n)) * 0.5 + 0.75, 1)
+    g = np.triu(rng.random((n, n)) * 0.5 + 0.75, 1)
+    return W0 * (f + f.T), W1 * (g + g.T)
+
+
+def split_evenly(n, k):
+    return [list(range(n))[i::k] for i in range(k)]
+
+
+def edge_cases():
+    """name -> dict(sides, lengths, W0, W1, strong, cap): the smallest shapes at which K25 can go wrong (tests/test_gpu_treecut.py runs them on both
+    paths; tests/test_treecut_host.py holds each to the branch it is meant to reach)"""
+    rng = np.random.default_rng(2525)
+    cases = {}
+
+    def add(name, n, clusters, strong=None, cap=3000, mats=dyadic_matrices, flip=True, **kw):
+        sides, lengths = tree_of_clusters(rng, clusters, n, flip)
+        W0, W1 = mats(rng, clusters, n, **kw)
+        cases[name] = dict(sides=sides, lengths=lengths, W0=W0, W1=W1, strong=np.ones(n, bool) if strong is None else np.asarray(strong, bool), cap=cap)
+        return cases[name]
+
+    for n in (2, 3, 4):
+        add('n%d' % n, n, [[a] for a in range(n)])
+    for n in (64, 65, 256, 257):
+        add('n%d' % n, n, split_evenly(n, 3), noise=4)
+        add('n%d_float' % n, n, split_evenly(n, 3), mats=float_matrices)
+    add('compatible', 9, [list(range(9))])
+    # one pair beyond its bound, but every branch between the two has far more bound than difference across it
+    c = add('no_candidate', 4, [[0, 1], [2, 3]], flip=False)
+    c['W0'][:] = 0.0
+    c['W1'][:] = 100.0
+    np.fill_diagonal(c['W1'], 0.0)
+    c['W0'][0, 1] = c['W0'][1, 0] = 2.0
+    c['W1'][0, 1] = c['W1'][1, 0] = 1.0
+    # the side as given holds leaf 0 and is the one the reference would detach: the part with leaf 0 keeps the place all the same
+    c = add('swap', 6, [[0, 1, 2], [3, 4, 5]], flip=False)
+    c['sides'] = ~c['sides']
+    add('dropped', 8, [[0, 1, 2, 3, 4], [5, 6, 7]], strong=[1, 1, 1, 1, 1, 0, 0, 0])
+    add('dropped_first', 8, [[0, 1, 2], [3, 4, 5, 6, 7]], strong=[0, 0, 0, 1, 1, 1, 1, 1])
+    add('queue', 16, split_evenly(16, 4))
+    add('queue_cap1', 16, split_evenly(16, 4), cap=1)
+    add('queue_cap2', 16, split_evenly(16, 4), cap=2)
+    add('queue_cap0', 16, split_evenly(16, 4), cap=0)
+    add('merged', 12, [[0, 1, 2, 3], [4, 5, 6, 7], [8, 9, 10, 11]], noise=2)
+    # ic0 > 1 with m == 0: the pairs beyond their bound have a bound of zero
+    c = add('key_zero', 3, [[0], [1], [2]])
+    c['W1'][:] = 0.0
+    add('float_small', 11, split_evenly(11, 3), mats=float_matrices)
+    add('singletons', 5, [[a] for a in range(5)])
+    # exact ties between different bipartitions: every pair alike, so the splits of one size score alike; the lengths decide, then - all lengths alike - the leaves
+    for name in ('ties', 'ties_one_length'):
+        c = add(name, 6, [[a] for a in range(6)])
+        c['W0'][:] = 50.0
+        np.fill_diagonal(c['W0'], 0.0)
+        if name == 'ties_one_length':
+            c['lengths'][:] = 0.125
+    return cases
+
+
+_RESTATED = {}
+
+
+def restated_edge_cases():
+    """(cases, name -> (restatement's result, its report)), computed once per process"""
+    if not _RESTATED:
+        cases = edge_cases()
+        done = {}
+        for name, c in cases.items():
+            report = {}
+            done[name] = (cut_restated(report=report, **c), report)
+        _RESTATED.update(cases=cases, done=done)
+    return _RESTATED['cases'], _RESTATED['done']
+
+
+def load_golden():
+    with gzip.open(GOLDEN, 'rb') as f:
+        return json.loads(f.read().decode())
+
+
+def golden_mat(case, k):
+    """the table of golden case k as the generator built it (column 1 genome, 4 identity, 5 locus id, 6 row), the genome ids moved to a range of the
+    case's own and the loci to member k + 1 of a shared store"""
+    mat = np.zeros((case['n'], 7), dtype=np.int64)
+    mat[:, 1] = np.array(case['genomes']) + k * 100000
+    mat[:, 4], mat[:, 5], mat[:, 6] = case['identity'], (k + 1) * 1000 + np.arange(case['n']), np.arange(case['n'])
+    return mat
+
+
+def golden_rows(case):
+    import base64
+    return [np.frombuffer(base64.b64decode(r), dtype=np.uint8) for r in case['rows']]
+
+
+def golden_by_params(golden):
+    """(self_id, allowed_sigma) -> the indices of the cases that share them: one filt_per_groups call each"""
+    out = {}
+    for k, c in enumerate(golden['cases']):
+        out.setdefault((c['self_id'], c['allowed_sigma']), []).append(k)
+    return out
+
+
+def golden_store(golden, folder):
+    """every golden case in ONE .seq store -> (its path, to_run: per case (mat, inparalog, ref_len), per parameter pair the global_differences of its cases,
+    per parameter pair the params)"""
+    from peppan_amd.mapbsn import MapBsn
+    path = os.path.join(folder, 'genes.seq.npz')
+    to_run, gds, params = [], {}, {}
+    with MapBsn(path, 'w') as store:
+        for k, c in enumerate(golden['cases']):
+            rows = golden_rows(c)
+            member = np.empty(len(rows), dtype=object)
+            for i, r in enumerate(rows):
+                member[i] = r
+            store.save(k + 1, member)
+            to_run.append((golden_mat(c, k), c['inparalog'], c['ref_len']))
+            key = (c['self_id'], c['allowed_sigma'])
+            gd = gds.setdefault(key, {})
+            for a, b, m, s in c['global_differences']:
+                gd[(a + k * 100000, b + k * 100000)] = (m, s)
+            params[key] = dict(self_id=c['self_id'], allowed_sigma=c['allowed_sigma'], clust_identity=c['clust_identity'], orthology='nj')
+    return path, to_run, gds, params
