@@ -191,7 +191,8 @@ enum PepWsSlot {
 // and they begin one after the other on the context's stream.
 enum PepLookback {
     PEP_LB_SCAN_U32 = 0,                    // scan_onepass<uint32_t> (pep_scan_u32): scan_lookback<uint32_t>; K1's layout_and_pack and reference side (translate.hip): k1_offsets,
-                                            // k1_ref_desc.  32 value bits.  Co-tenants: all three write 32-bit words and are begun one after another on the context's stream
+                                            // k1_ref_desc, k1_ref_layout (four status arrays, one per total).  32 value bits.  Co-tenants: all write 32-bit words and are begun one
+                                            // after another on the context's stream
     PEP_LB_SCAN_U64,                        // scan_onepass<uint64_t> (pep_scan_u64): scan_lookback<uint64_t>; the traceback pass of pep_sw_run (sw.hip): sw_prep.  48 value bits.
                                             // Co-tenants for the same reason
     PEP_LB_SELECT_COUNT,                    // the alignment stage (trace.hip): select_gather, selected pairs in front of a tile.  32 value bits.  Its ticket numbers the tiles of both select slots
@@ -258,6 +259,10 @@ struct pep_ctx {
     // records (+ frame -> record), the stop mask itself, tiles of chunk slots
     DevBuf d_k1_seg, d_k1_long, d_k1_spec, d_k1_tiles;
     uint32_t k1_n_seg = 0, k1_n_long = 0, k1_n_tiles = 0;
+    // ... and of a set without long frames (genes: k1_ref_layout / k1_pack_ref): its frames of more than 1000 characters, whose stops k1_ref_chunks looks for, and the
+    // chunk slots of its sequences too long for one wavefront's staging area
+    DevBuf d_k1_cut, d_k1_big;
+    uint32_t k1_n_cut = 0, k1_n_big = 0;
     // what pep_use_nt_as_residues makes of the nucleotide sets apart from the residues themselves (translate.hip: pep_nucl_sets), kept per pair of uploads
     struct NuclSide {
         uint32_t n = 0, max_len = 0;

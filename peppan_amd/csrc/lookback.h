@@ -53,7 +53,9 @@ __device__ __forceinline__ uint32_t lb_take_tile(uint64_t *state, uint32_t ticke
 
 // exclusive prefix of tile `tile` whose own total is `tot`.  To be called by the 64 threads of the block's FIRST wavefront (lane = threadIdx.x);
 // the result is valid in every one of them.  VB: value bits (32 with a 30-bit epoch, 48 with a 14-bit epoch); S: the type the totals are added in.
-template <int VB, class S = uint64_t>
+// MAX: the tiles' values are combined by maximum instead of by sum ("the largest value of any tile in front of this one").
+// (A kernel that needs several prefixes at once - K1's reference layout - gives every one a status array of its own, n_tickets words apart, and a wavefront of its own.)
+template <int VB, class S = uint64_t, bool MAX = false>
 __device__ __forceinline__ S lb_tile_prefix(uint64_t *status, uint32_t tile, uint64_t tot, uint64_t epoch, int lane)
 {
     S prefix = 0;
@@ -67,12 +69,12 @@ __device__ __forceinline__ S lb_tile_prefix(uint64_t *status, uint32_t tile, uin
             const int stop = is_prefix ? __ffsll((unsigned long long)is_prefix) - 1 : 63;      // lanes 0 .. stop contribute
             S part = lane <= stop ? (S)lb_value<VB>(w) : (S)0;
 #pragma unroll
-            for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-            prefix += part;
+            for (int d = 32; d > 0; d >>= 1) { const S o = __shfl_xor(part, d, 64); part = MAX ? (o > part ? o : part) : part + o; }
+            prefix = MAX ? (part > prefix ? part : prefix) : prefix + part;
             if (is_prefix) break;
         }
     }
-    if (lane == 0) lb_publish(&status[tile], lb_word<VB, LB_PREFIX>(epoch, prefix + tot));
+    if (lane == 0) lb_publish(&status[tile], lb_word<VB, LB_PREFIX>(epoch, MAX ? ((S)tot > prefix ? (S)tot : prefix) : prefix + (S)tot));
     return prefix;
 }
 

@@ -336,12 +336,19 @@ __global__ __launch_bounds__(256) void k1_ref_chunks_mask(const uint64_t *__rest
 }
 
 // one wavefront per (reference sequence, frame): chunk boundaries.  chunk_base[w] = first slot of this frame's chunk list.
+// `list` (n_list entries): the frames to walk - the ones of more than 1000 characters of a set without long frames, whose other frames need no look at
+// their nucleotides (k1_ref_layout); nullptr: every frame of the set.
 __global__ __launch_bounds__(256) void k1_ref_chunks(const uint8_t *__restrict__ nt, const uint64_t *__restrict__ off, uint32_t n, int n_frames, int tab,
                                                      const uint64_t *__restrict__ chunk_base, uint32_t *__restrict__ chunk_cnt,
-                                                     uint32_t *__restrict__ chunk_off, uint32_t *__restrict__ chunk_len, int64_t long_from)
+                                                     uint32_t *__restrict__ chunk_off, uint32_t *__restrict__ chunk_len, int64_t long_from,
+                                                     const uint32_t *__restrict__ list, uint32_t n_list)
 {
     const int lane = threadIdx.x & 63;
-    const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (list) {
+        if (w >= n_list) return;
+        w = list[w];
+    }
     if (w >= (uint64_t)n * n_frames) return;
     const uint32_t g = (uint32_t)(w / n_frames);
     const int f = (int)(w % n_frames) + 1;
@@ -365,7 +372,65 @@ __global__ __launch_bounds__(256) void k1_ref_chunks(const uint8_t *__restrict__
     if (lane == 0) chunk_cnt[w] = cnt;
 }
 
-// One wavefront per packed sequence: lanes stride over its residues (adjacent lanes read adjacent codons - 192 contiguous
+// ---- packing: what every pack kernel does with a lane's share of a trip of 512 residues
+constexpr int K1_WINDOW_DW = 392;                // staging area of one window of 1536 (+ 2) nucleotide bytes at any alignment, dwords
+
+// the lane's 24 characters in reading order, four to a register: seven dwords from LDS (stage[di ..]: source order), shifted down by the staged bytes' misalignment;
+// the reverse strand reads in descending source order
+__device__ __forceinline__ void lane_chars(const uint32_t *stage, int di, uint32_t shift, bool fwd, uint32_t *ch)
+{
+    uint32_t raw[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) raw[k] = stage[di + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ch[k] = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], shift);
+    if (!fwd) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t lo_w = __builtin_bswap32(ch[5 - k]), hi_w = __builtin_bswap32(ch[k]);
+            ch[k] = lo_w; ch[5 - k] = hi_w;
+        }
+    }
+}
+
+// ... -> its eight residue bytes: the first n_valid characters lie inside the sequence, the first n_res residues inside the packed sequence (padding behind them)
+__device__ __forceinline__ uint2 translate24(const uint32_t *ch, bool fwd, int n_valid, int n_res, const uint32_t *codon)
+{
+    uint32_t word[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                                 // twelve characters = four codons
+        uint32_t pk[3], bad[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nt4(ch[3 * h + k], !fwd, pk[k], bad[k]);
+        const uint32_t codes = (pk[0] << 16) | (pk[1] << 8) | pk[2];
+        uint32_t bad12 = (bad[0] << 8) | (bad[1] << 4) | bad[2];
+        const int nv = min(max(n_valid - 12 * h, 0), 12);
+        bad12 |= (1u << (12 - nv)) - 1u;                          // characters behind the sequence's end
+        uint32_t w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t c = codon[(codes >> (18 - 6 * k)) & 63u];
+            if ((bad12 >> (9 - 3 * k)) & 7u) c = 23u;
+            if (4 * h + k >= n_res) c = PEP_PAD_CODE;
+            w |= c << (8 * k);
+        }
+        word[h] = w;
+    }
+    return make_uint2(word[0], word[1]);
+}
+
+// (sequence, start) per 32-byte block that holds residues of packed sequence s: [start, next - 16) - the gap in front of `next` is at least 16 bytes of
+// padding, so a block never holds residues of two sequences; the block that `next` starts in the middle of belongs to the next sequence
+__device__ __forceinline__ void fill_blk2seq(uint2 *__restrict__ blk2seq, uint32_t s, uint32_t start, uint32_t next, int lane)
+{
+    for (uint32_t b = (start >> 5) + lane, last = ((next & 31u) == 16u) ? ((next - 16u) >> 5) - 1u : (next - 17u) >> 5; b <= last && last != ~0u; b += 64) blk2seq[b] = make_uint2(s, start);
+}
+
+__device__ __forceinline__ void pack_windows(const uint8_t *__restrict__ src, int L, PackDesc d, uint32_t s, uint32_t start, uint32_t next, uint32_t *stage,
+                                             const uint32_t *codon, int lane, uint8_t *__restrict__ res, uint2 *__restrict__ blk2seq);
+
+// One wavefront per packed sequence - the query side's genes, and every set that holds long frames (contigs; gene sets on the reference side: k1_pack_ref,
+// a wavefront per gene): lanes stride over its residues (adjacent lanes read adjacent codons - 192 contiguous
 // nucleotide bytes per step - and store 64 contiguous residue bytes), then over the padding up to the next sequence, and fill
 // the block -> sequence map of the blocks it owns.  The number of packed sequences lives on the device (*n_ptr): the grid is
 // sized from a host upper bound and the surplus waves leave at once, so the host never waits for the chunk count.
@@ -397,17 +462,21 @@ __global__ __launch_bounds__(256) void k1_pack(const uint8_t *__restrict__ nt, c
         return;
     }
     if (s >= n_packed) return;
-    const uint8_t *src = nt + so.off;
-    const int L = (int)so.L;
+    __shared__ uint32_t stage_all[4][K1_WINDOW_DW];
+    pack_windows(nt + so.off, (int)so.L, d, s, start, next, stage_all[threadIdx.x >> 6], codon, lane, res, blk2seq);
+}
+
+// packed sequence s = residues d.aa_off .. d.aa_off + d.len of frame d.frame of src[0..L), bytes [start, next) of the layout, by one wavefront.
+// Chunks of 512 residues: the wavefront copies the 1536 nucleotide bytes behind them into LDS with aligned dword loads (coalesced:
+// 256 contiguous bytes per instruction), then every lane translates eight residues out of LDS and stores 8 bytes.  Reading the
+// bytes straight from global memory (three byte loads per residue, 24 bytes apart from lane to lane) made every instruction touch
+// 24 cache lines: both sides of K1 ran at the same 230 G residues/s whatever their size.
+// A lane's 24 characters are handled four to a register (nt4): character by character the kernel spent 850 vector instructions per
+// chunk - at four cycles per wave64 instruction that, not memory, was its time.
+__device__ __forceinline__ void pack_windows(const uint8_t *__restrict__ src, int L, PackDesc d, uint32_t s, uint32_t start, uint32_t next, uint32_t *stage,
+                                             const uint32_t *codon, int lane, uint8_t *__restrict__ res, uint2 *__restrict__ blk2seq)
+{
     if (s == 0) for (uint32_t x = lane; x < start; x += 64) res[x] = (uint8_t)PEP_PAD_CODE;          // leading pad
-    // Chunks of 512 residues: the wavefront copies the 1536 nucleotide bytes behind them into LDS with aligned dword loads (coalesced:
-    // 256 contiguous bytes per instruction), then every lane translates eight residues out of LDS and stores 8 bytes.  Reading the
-    // bytes straight from global memory (three byte loads per residue, 24 bytes apart from lane to lane) made every instruction touch
-    // 24 cache lines: both sides of K1 ran at the same 230 G residues/s whatever their size.
-    // A lane's 24 characters are handled four to a register (nt4): character by character the kernel spent 850 vector instructions per
-    // chunk - at four cycles per wave64 instruction that, not memory, was its time.
-    __shared__ uint32_t stage_all[4][392];
-    uint32_t *stage = stage_all[threadIdx.x >> 6];
     const int frame = (int)d.frame;
     const bool fwd = frame <= 3;
     const int fo = fwd ? frame - 1 : frame - 4;
@@ -431,48 +500,99 @@ __global__ __launch_bounds__(256) void k1_pack(const uint8_t *__restrict__ nt, c
         const uint32_t x0 = c0 + 8 * lane;
         if (x0 < next - start) {
             // the lane's 24 characters in source order: seven dwords from LDS, shifted down by the window's misalignment
-            const int di = fwd ? 6 * lane : 378 - 6 * lane;
-            uint32_t raw[7], ch[6];
-#pragma unroll
-            for (int k = 0; k < 7; ++k) raw[k] = stage[di + k];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ch[k] = __builtin_amdgcn_alignbyte(raw[k + 1], raw[k], (uint32_t)shift);
-            if (!fwd) {                                                   // reading direction = descending source order
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const uint32_t lo_w = __builtin_bswap32(ch[5 - k]), hi_w = __builtin_bswap32(ch[k]);
-                    ch[k] = lo_w; ch[5 - k] = hi_w;
-                }
-            }
+            uint32_t ch[6];
+            lane_chars(stage, fwd ? 6 * lane : 378 - 6 * lane, (uint32_t)shift, fwd, ch);
             const int n_valid = min(max(L - (P0 + 24 * lane), 0), 24);          // characters of the lane that lie inside the sequence
             const int n_res = (int)min(max((int64_t)d.len - (int64_t)x0, (int64_t)0), (int64_t)8);
-            uint32_t word[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {                                 // twelve characters = four codons
-                uint32_t pk[3], bad[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) nt4(ch[3 * h + k], !fwd, pk[k], bad[k]);
-                const uint32_t codes = (pk[0] << 16) | (pk[1] << 8) | pk[2];
-                uint32_t bad12 = (bad[0] << 8) | (bad[1] << 4) | bad[2];
-                const int nv = min(max(n_valid - 12 * h, 0), 12);
-                bad12 |= (1u << (12 - nv)) - 1u;                          // characters behind the sequence's end
-                uint32_t w = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t c = codon[(codes >> (18 - 6 * k)) & 63u];
-                    if ((bad12 >> (9 - 3 * k)) & 7u) c = 23u;
-                    if (4 * h + k >= n_res) c = PEP_PAD_CODE;
-                    w |= c << (8 * k);
-                }
-                word[h] = w;
-            }
-            *reinterpret_cast<uint2 *>(res + start + x0) = make_uint2(word[0], word[1]);
+            *reinterpret_cast<uint2 *>(res + start + x0) = translate24(ch, fwd, n_valid, n_res, codon);
         }
         __builtin_amdgcn_wave_barrier();                                 // the next chunk overwrites the staging area
     }
-    // (sequence, start) per 32-byte block that holds residues of this sequence: [start, next - 16) - the gap in front of `next` is at least 16 bytes of
-    // padding, so a block never holds residues of two sequences; the block that `next` starts in the middle of belongs to the next sequence
-    for (uint32_t b = (start >> 5) + lane, last = ((next & 31u) == 16u) ? ((next - 16u) >> 5) - 1u : (next - 17u) >> 5; b <= last && last != ~0u; b += 64) blk2seq[b] = make_uint2(s, start);
+    fill_blk2seq(blk2seq, s, start, next, lane);
+}
+
+// ---- the reference side of a set WITHOUT long frames (genes: PEPPAN's hot call) in two launches, k1_ref_layout and k1_pack_ref.
+// The six frames of a 1 002-nt gene were six wavefronts of k1_pack in six blocks, each with its own descriptor, source and offset loads and its own copy of the
+// same 1 000 bytes into LDS: 60 000 wavefronts at 10 000 genes.  Here a wavefront stages its gene ONCE - all of it, K1_GENE_NT bytes at the most - and translates
+// every packed sequence of the gene, forward frames and mirrored reverse frames alike, out of that copy.  Sequences beyond K1_GENE_NT keep a wavefront per packed
+// sequence (pack_windows), in a second range of blocks of the same launch over a host-built list of their chunk slots: one wavefront must never pack a sequence of
+// tens of kilobases alone (round 4's contig bug was that, 4 - 8 ms).
+// K1_GENE_NT: the staging areas of a block's four wavefronts and the codon tables take 19 840 bytes of LDS, so that eight blocks - 32 wavefronts, all a CU holds - fit
+// its 160 KiB; 4 608 nucleotides are three windows of 512 codons.
+constexpr int K1_GENE_NT = 4608;
+constexpr int K1_GENE_GUARD = 8;                 // dwords in front of the staged bytes: a lane of a reverse frame whose first characters lie inside the sequence reads up to 23 bytes in front of it
+constexpr int K1_GENE_DW = 1176;                 // ... and seven dwords from its first byte, which may be the sequence's last
+static_assert(K1_GENE_GUARD * 4 + 3 + K1_GENE_NT - 1 + 28 <= K1_GENE_DW * 4, "a lane with a character inside the sequence reads inside the staging area");
+static_assert(K1_GENE_DW >= K1_WINDOW_DW && 8 * (4 * K1_GENE_DW * 4 + 4 * 64 * 4) <= 160 * 1024, "eight blocks per CU; the window path of the long sequences fits too");
+struct K1Big { uint32_t g, k; };                 // chunk slot k (counted over all frames) of reference sequence g, a sequence beyond K1_GENE_NT
+
+__global__ __launch_bounds__(256) void k1_pack_ref(const uint8_t *__restrict__ nt, const uint64_t *__restrict__ off, uint32_t n, int n_frames, int tab,
+                                                   const uint32_t *__restrict__ first_w, const PackDesc *__restrict__ desc, const uint32_t *__restrict__ pk_off,
+                                                   uint32_t gene_blocks, const K1Big *__restrict__ big, uint32_t n_big, uint8_t *__restrict__ res, uint2 *__restrict__ blk2seq)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ uint32_t codon_all[4][64];
+    __shared__ uint32_t stage_all[4][K1_GENE_DW];
+    uint32_t *codon = codon_all[wave], *stage = stage_all[wave];
+    codon[lane] = c_codon[tab][lane];
+    if (blockIdx.x >= gene_blocks) {
+        // a long sequence's chunk slot: the packed sequence behind it, if the frames of the sequence have that many
+        const uint32_t x = (blockIdx.x - gene_blocks) * 4 + wave;
+        if (x >= n_big) return;
+        const K1Big b = big[x];
+        const uint32_t s = first_w[(uint64_t)b.g * n_frames] + b.k;
+        if (s >= first_w[(uint64_t)(b.g + 1) * n_frames]) return;
+        const uint64_t o = off[b.g];
+        pack_windows(nt + o, (int)(off[b.g + 1] - o), desc[s], s, pk_off[s], pk_off[s + 1], stage, codon, lane, res, blk2seq);
+        return;
+    }
+    const uint32_t g = blockIdx.x * 4 + wave;
+    if (g >= n) return;
+    // everything the wavefront needs before it can fetch is here in one round trip: where the gene lies, which packed sequences are its own
+    const uint64_t o = off[g];
+    const int L = (int)(off[g + 1] - o);
+    const uint32_t s0 = first_w[(uint64_t)g * n_frames], s1 = first_w[(uint64_t)(g + 1) * n_frames];       // (first_w[n * n_frames] = the number of packed sequences)
+    if (g == 0 && first_w[(uint64_t)n * n_frames] == 0) {                // nothing but the two end pads
+        for (uint32_t x = lane; x < pk_off[0]; x += 64) res[x] = (uint8_t)PEP_PAD_CODE;
+        return;
+    }
+    if (L > K1_GENE_NT || s1 == s0) return;
+    const uint32_t cnt = s1 - s0;                                        // <= 12: a frame of 1 536 characters makes two chunks at the most
+    const uintptr_t A = reinterpret_cast<uintptr_t>(nt + o);
+    const int shift0 = (int)(A & 3u);
+    const uint32_t *al = reinterpret_cast<const uint32_t *>(A - shift0);
+    const int n_dw = (L + shift0 + 3) >> 2;                              // the buffer is padded by 64 bytes behind the last sequence
+    for (int x = lane; x < n_dw; x += 64) stage[K1_GENE_GUARD + x] = al[x];
+    PackDesc dl = PackDesc{0u, 1u, 0u, 0u};
+    if ((uint32_t)lane < cnt) dl = desc[s0 + lane];                      // one coalesced read each for the descriptors and the offsets (cnt + 1 of them)
+    const uint32_t pkl = (uint32_t)lane <= cnt ? pk_off[s0 + lane] : 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const int frame = __builtin_amdgcn_readlane((int)dl.frame, (int)k);
+        const uint32_t aa_off = (uint32_t)__builtin_amdgcn_readlane((int)dl.aa_off, (int)k), len = (uint32_t)__builtin_amdgcn_readlane((int)dl.len, (int)k);
+        const uint32_t start = (uint32_t)__builtin_amdgcn_readlane((int)pkl, (int)k), next = (uint32_t)__builtin_amdgcn_readlane((int)pkl, (int)k + 1);
+        const uint32_t s = s0 + k;
+        if (s == 0) for (uint32_t x = lane; x < start; x += 64) res[x] = (uint8_t)PEP_PAD_CODE;          // leading pad
+        const bool fwd = frame <= 3;
+        const int fo = fwd ? frame - 1 : frame - 4;
+        for (uint32_t c0 = 0; c0 < next - start; c0 += 512) {
+            const uint32_t x0 = c0 + 8 * lane;
+            if (x0 >= next - start) continue;
+            const int P0 = fo + 3 * (int)(aa_off + c0);                  // first nucleotide position (in reading direction) of the trip
+            const int lo = fwd ? P0 : L - 1 - (P0 + 1535);               // the source bytes [lo, lo + 1536) hold positions P0 .. P0 + 1535, as in pack_windows
+            const int B = lo + shift0 + 4 * K1_GENE_GUARD;               // the byte of the staging area the window starts at (in front of it where a reverse frame runs out)
+            // a lane with a character inside the sequence reads inside the area (the static_assert above); the others are held there and read what nobody uses
+            const int di = min(max((B >> 2) + (fwd ? 6 * lane : 378 - 6 * lane), 0), K1_GENE_DW - 7);
+            uint32_t ch[6];
+            lane_chars(stage, di, (uint32_t)(B & 3), fwd, ch);
+            const int n_valid = min(max(L - (P0 + 24 * lane), 0), 24);
+            const int n_res = (int)min(max((int64_t)len - (int64_t)x0, (int64_t)0), (int64_t)8);
+            *reinterpret_cast<uint2 *>(res + start + x0) = translate24(ch, fwd, n_valid, n_res, codon);
+        }
+        fill_blk2seq(blk2seq, s, start, next, lane);
+    }
 }
 
 // ---- nucleotide sets as residue sets (the blastn-equivalent tool, uberBlast.py:294, 482-509): base codes A0 C1 G2 T3, anything else 4;
@@ -646,6 +766,87 @@ __global__ __launch_bounds__(256) void k1_offsets(const uint32_t *__restrict__ n
     if (i == cap) { sum->n = n; sum->total = (unsigned long long)at + 2ull * PEP_END_PAD; }
 }
 
+// The reference layout of a set without long frames in ONE launch, a thread per (sequence, frame) - what k1_ref_chunks over every frame, k1_ref_desc and k1_offsets
+// did in three, with a look-back scan in two of them.  A frame of at most 1000 characters is one chunk (none when it is empty), whatever its text: chunk_end
+// returns at once, the appended 'X' at index 1000 ends the search where it starts.  Only the frames beyond that have had their stops looked for (k1_ref_chunks over
+// the host's list of them, in front of this launch); their chunks are read from chunk_cnt / chunk_off / chunk_len.
+// Four totals run through the tiles, each with a status array of its own (n_tiles words apart) and a wavefront of the block to look back for it: packed sequences,
+// padded bytes, residues, and - by maximum - the longest packed sequence.  The last tile therefore holds the set's summary and writes it, to the device and into the
+// host's pinned memory: no accumulator has to be cleared in front of the launch, no atomic is needed.
+// Writes: descriptors, source records, len, pk_off (entries n .. cap = the layout's size), first_w (entry nw = the number of packed sequences), first_t, the summaries.
+__global__ __launch_bounds__(256) void k1_ref_layout(const uint64_t *__restrict__ nt_off, uint64_t nw, int n_frames, const uint64_t *__restrict__ chunk_base,
+                                                     const uint32_t *__restrict__ chunk_cnt, const uint32_t *__restrict__ chunk_off, const uint32_t *__restrict__ chunk_len,
+                                                     uint32_t cap, PackDesc *__restrict__ desc, K1Src *__restrict__ src_of, uint32_t *__restrict__ len_out, uint32_t *__restrict__ pk_off,
+                                                     uint32_t *__restrict__ first_t, uint32_t *__restrict__ first_w, K1Summary *__restrict__ sum, K1Summary *__restrict__ pin_sum,
+                                                     LbLaunch sc, uint32_t n_tiles)
+{
+    __shared__ uint32_t s_tile, red_r[4], red_m[4];
+    __shared__ uint64_t lds[4], s_pre[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t tile = lb_take_tile(sc.state, sc.ticket_base, &s_tile);
+    const uint64_t w = (uint64_t)tile * 256 + threadIdx.x;
+    uint32_t cnt = 0, bytes = 0, resid = 0, longest = 0, g = 0, f = 0, na = 0;
+    uint64_t o = 0, base = 0;
+    int64_t L = 0;
+    bool cut = false;                            // a frame of more than 1000 characters: its chunks come from k1_ref_chunks
+    if (w < nw) {
+        g = (uint32_t)(w / n_frames); f = (uint32_t)(w % n_frames) + 1;
+        o = nt_off[g];
+        L = (int64_t)(nt_off[g + 1] - o);
+        na = (uint32_t)frame_len(L, (int)f);
+        cut = na > 1000u;
+        if (cut) {
+            cnt = chunk_cnt[w]; base = chunk_base[w];
+            for (uint32_t c = 0; c < cnt; ++c) { const uint32_t l = chunk_len[base + c]; bytes += padded_len(l); resid += l; longest = max(longest, l); }
+        } else if (na) { cnt = 1; bytes = padded_len(na); resid = longest = na; }
+    }
+    // the tile's totals: packed sequences and padded bytes by one scan (a tile holds fewer than 2^32 of either), residues and the longest by reduction
+    uint64_t tot2;
+    const uint64_t ex2 = block_excl_scan_256<uint64_t>(((uint64_t)cnt << 32) | bytes, &tot2, lds);
+    uint32_t r = resid, m = longest;
+    for (int d = 32; d > 0; d >>= 1) { r += __shfl_xor(r, d, 64); m = max(m, (uint32_t)__shfl_xor((int)m, d, 64)); }
+    if (lane == 0) { red_r[wave] = r; red_m[wave] = m; }
+    __syncthreads();
+    const uint32_t tot_r = red_r[0] + red_r[1] + red_r[2] + red_r[3], tot_m = max(max(red_m[0], red_m[1]), max(red_m[2], red_m[3]));
+    {
+        uint64_t *st = sc.status() + (uint64_t)wave * n_tiles;
+        const uint64_t mine = wave == 0 ? tot2 >> 32 : wave == 1 ? (tot2 & 0xFFFFFFFFull) : wave == 2 ? (uint64_t)tot_r : (uint64_t)tot_m;
+        const uint64_t p = wave == 3 ? lb_tile_prefix<32, uint64_t, true>(st, tile, mine, sc.epoch, lane) : lb_tile_prefix<32>(st, tile, mine, sc.epoch, lane);
+        if (lane == 0) s_pre[wave] = p;
+    }
+    __syncthreads();
+    const uint32_t at = (uint32_t)s_pre[0] + (uint32_t)(ex2 >> 32);              // packed sequences in front of this frame
+    uint32_t pos = PEP_END_PAD + (uint32_t)s_pre[1] + (uint32_t)ex2;            // where its first one starts
+    if (w < nw) {
+        first_w[w] = at;
+        if (f == 1u) first_t[g] = cnt ? at : PEP_SELF_NONE;          // the packed sequence frame 1 of reference sequence g starts with (seeds.hip: self_prepare)
+        const K1Src so{o, (uint32_t)L, 0u};
+        if (!cut) {
+            if (cnt) { desc[at] = PackDesc{g, f, 0u, na}; src_of[at] = so; len_out[at] = na; pk_off[at] = pos; }
+        } else {
+            for (uint32_t c = 0; c < cnt; ++c) {
+                const uint32_t l = chunk_len[base + c];
+                desc[at + c] = PackDesc{g, f, chunk_off[base + c], l};
+                src_of[at + c] = so;
+                len_out[at + c] = l;
+                pk_off[at + c] = pos;
+                pos += padded_len(l);
+            }
+        }
+    }
+    if (tile == n_tiles - 1) {
+        const uint32_t n_all = (uint32_t)s_pre[0] + (uint32_t)(tot2 >> 32);
+        const uint32_t total = (uint32_t)s_pre[1] + (uint32_t)tot2 + 2u * PEP_END_PAD;
+        for (uint64_t i = (uint64_t)n_all + threadIdx.x; i <= cap; i += 256) pk_off[i] = total;          // the sentinels of the owner search
+        if (threadIdx.x == 0) {
+            first_w[nw] = n_all;
+            const K1Summary S{(unsigned long long)((uint32_t)s_pre[2] + tot_r), (unsigned long long)total, n_all, max((uint32_t)s_pre[3], tot_m), {0u, 0u}};
+            *sum = S;
+            *pin_sum = S;
+        }
+    }
+}
+
 int reserve_packed(pep_ctx *ctx, SeqSet &out, uint32_t cap, uint64_t upper)
 {
     if (upper > PEP_MAX_RESIDUES + (uint64_t)cap * 32) return pep_fail(ctx, PEP_ERR_LIMIT, "packed protein set exceeds 2^29 bytes");
@@ -689,9 +890,10 @@ int k1_take(pep_ctx *ctx, hipEvent_t ev, const void *pinned, SeqSet &out)
 enum {
     K1Q_PADDED = 3,                         // padded length per query, u32: k1_query_frames, read last by k1_offsets
     K1Q_COUNT = 5,                          // number of queries, u32: k1_query_frames, read last by k1_pack
-    K1R_CHUNK_CNT = 1, K1R_CHUNK_OFF, K1R_CHUNK_LEN,    // chunks per frame u32; first residue and length per chunk slot u32: k1_ref_chunks(_mask), read last by k1_ref_desc(_fill)
-    K1R_FIRST = 5,                          // first packed sequence per frame, the number of targets behind them, u32: k1_ref_desc, read last by k1_pack
-    K1R_PADDED,                             // padded length per target, u32: k1_ref_desc(_fill), read last by k1_offsets
+    K1R_CHUNK_CNT = 1, K1R_CHUNK_OFF, K1R_CHUNK_LEN,    // chunks per frame u32; first residue and length per chunk slot u32: k1_ref_chunks(_mask), read last by k1_ref_desc(_fill) / k1_ref_layout
+                                            // (a set of genes: only the entries of its frames of more than 1000 characters are written, and read)
+    K1R_FIRST = 5,                          // first packed sequence per frame, the number of targets behind them, u32: k1_ref_desc / k1_ref_layout, read last by k1_pack / k1_pack_ref
+    K1R_PADDED,                             // padded length per target, u32: k1_ref_desc(_fill), read last by k1_offsets (sets with long frames only: k1_ref_layout keeps the padded lengths to itself)
     K1_SLOTS
 };
 static_assert(K1Q_COUNT < K1_SLOTS && K1_SLOTS <= PEP_WS_HITS_OUT, "leaves the device-resident hit table alone");
@@ -821,6 +1023,31 @@ int pep_k1_ref_queue(pep_ctx *ctx, int frames, int gtable)
             PEP_HIP(ctx, hipMemcpy(ctx->d_k1_tiles.p, tiles.data(), tiles.size() * sizeof(K1Seg), hipMemcpyHostToDevice));
         }
         ctx->k1_n_tiles = (uint32_t)tiles.size();
+        ctx->k1_n_cut = ctx->k1_n_big = 0;
+        if (longs.empty()) {
+            // a set of genes: the frames of more than 1000 characters (k1_ref_chunks walks these alone) and the chunk slots of the sequences that one wavefront does not stage whole
+            std::vector<uint32_t> cut;
+            std::vector<K1Big> big;
+            for (uint32_t g = 0; g < n; ++g) {
+                const uint64_t L = nt.h_off[g + 1] - nt.h_off[g];
+                for (int f = 1; f <= nf; ++f) {
+                    const uint64_t shift = (uint64_t)(f <= 3 ? f - 1 : f - 4);
+                    if (L > shift && (L - shift + 2) / 3 > 1000) cut.push_back(g * (uint32_t)nf + (uint32_t)(f - 1));
+                }
+                if (L > (uint64_t)K1_GENE_NT)
+                    for (uint32_t k = 0, slots_g = (uint32_t)(base[(uint64_t)(g + 1) * nf] - base[(uint64_t)g * nf]); k < slots_g; ++k) big.push_back(K1Big{g, k});
+            }
+            if (!cut.empty()) {
+                PEP_TRY(dev_reserve(ctx, ctx->d_k1_cut, cut.size() * 4));
+                PEP_HIP(ctx, hipMemcpy(ctx->d_k1_cut.p, cut.data(), cut.size() * 4, hipMemcpyHostToDevice));
+            }
+            if (!big.empty()) {
+                PEP_TRY(dev_reserve(ctx, ctx->d_k1_big, big.size() * sizeof(K1Big)));
+                PEP_HIP(ctx, hipMemcpy(ctx->d_k1_big.p, big.data(), big.size() * sizeof(K1Big), hipMemcpyHostToDevice));
+            }
+            ctx->k1_n_cut = (uint32_t)cut.size();
+            ctx->k1_n_big = (uint32_t)big.size();
+        }
         ctx->k1_base_frames = nf;
     }
     const uint64_t slots = ctx->k1_base[nw], upper = ctx->k1_upper;
@@ -839,9 +1066,27 @@ int pep_k1_ref_queue(pep_ctx *ctx, int frames, int gtable)
     PEP_TRY(dev_reserve(ctx, ctx->d_self_t, ((size_t)n + 1) * 4));
     ctx->self_first_n = n;
     const uint64_t *d_base = ctx->d_k1_base.as<const uint64_t>();
-    if (nw) {
+    if (nw && ctx->k1_n_long == 0) {
+        // a set of genes: the stops of the few frames that can have more than one chunk, the layout, the residues gene by gene (the kernels' comments)
+        if (ctx->k1_n_cut)
+            hipLaunchKernelGGL(k1_ref_chunks, dim3((unsigned)ceil_div(ctx->k1_n_cut, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, nf, tab,
+                               d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>(), INT64_MAX,
+                               ctx->d_k1_cut.as<const uint32_t>(), ctx->k1_n_cut);
+        LbLaunch sc;
+        const uint64_t tiles = ceil_div(nw + 1, 256);
+        PEP_TRY(pep_lookback_begin(ctx, PEP_LB_SCAN_U32, tiles, 4, 32, &sc));
+        hipLaunchKernelGGL(k1_ref_layout, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, nt.off.as<const uint64_t>(), nw, nf, d_base, W[K1R_CHUNK_CNT].as<const uint32_t>(),
+                           W[K1R_CHUNK_OFF].as<const uint32_t>(), W[K1R_CHUNK_LEN].as<const uint32_t>(), (uint32_t)slots, D.as<PackDesc>(), k1_src_of(D.as<const PackDesc>(), (uint32_t)slots),
+                           ctx->t.len.as<uint32_t>(), ctx->t.off.as<uint32_t>(), ctx->d_self_t.as<uint32_t>(), W[K1R_FIRST].as<uint32_t>(),
+                           reinterpret_cast<K1Summary *>(D.as<PackDesc>() + slots), pin_sum, sc, (uint32_t)tiles);
+        const uint32_t gene_blocks = (uint32_t)ceil_div(n, 4);
+        hipLaunchKernelGGL(k1_pack_ref, dim3(gene_blocks + (unsigned)ceil_div(ctx->k1_n_big, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, nf, tab,
+                           W[K1R_FIRST].as<const uint32_t>(), D.as<const PackDesc>(), ctx->t.off.as<const uint32_t>(), gene_blocks, ctx->d_k1_big.as<const K1Big>(), ctx->k1_n_big,
+                           ctx->t.res.as<uint8_t>(), ctx->t.blk2seq.as<uint2>());
+        PEP_HIP(ctx, hipGetLastError());
+    } else if (nw) {
         hipLaunchKernelGGL(k1_ref_chunks, dim3((unsigned)ceil_div(nw, 4)), dim3(256), 0, ctx->stream, nt.nt.as<const uint8_t>(), nt.off.as<const uint64_t>(), n, nf, tab,
-                           d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>(), ctx->k1_n_long ? K1_LONG : INT64_MAX);
+                           d_base, W[K1R_CHUNK_CNT].as<uint32_t>(), W[K1R_CHUNK_OFF].as<uint32_t>(), W[K1R_CHUNK_LEN].as<uint32_t>(), K1_LONG, (const uint32_t *)nullptr, 0u);
         if (ctx->k1_n_long) {
             // the frames of contigs: their stops as a bit mask (all frames side by side), then the chunk chain of every frame out of register windows of that mask
             const K1Long *d_longs = ctx->d_k1_long.as<const K1Long>();
