@@ -524,6 +524,7 @@ int pep_upload_blk2seq(pep_ctx *ctx, SeqSet &s);
 // the current sets came out of K1 at all (*on = 0: not applicable, nothing queued).
 #define PEP_SELF_NONE 0xFFFFFFFFu
 #define PEP_SELF_NO_DELTA ((int32_t)0x80808080)
+#define PEP_SELF_SAFE 1          // bit 0 of a distance word (the starts are 16-aligned, so a distance has four free low bits; PEP_SELF_NO_DELTA has it clear): see JoinArgs::self_delta
 int pep_self_map(pep_ctx *ctx, int *on);
 int pep_upload_codes(pep_ctx *ctx, PepSide side, const uint8_t *codes, const uint64_t *off, uint32_t n, uint32_t max_n);
 int pep_upload_sub(pep_ctx *ctx);

@@ -343,6 +343,10 @@ struct JoinArgs {
                                  // atomics of one word at a tenth of what it sustains) or 1
     const int32_t *self_delta;   // self-search (pep_self_map): per 32-byte block of the targets, target position - query position of the hits that are a gene against itself on
                                  // diagonal 0 (PEP_SELF_NO_DELTA: none); nullptr = off.  Such hits are counted and dropped: self_prepare has settled their candidate.
+                                 // Bit 0 (PEP_SELF_SAFE) rides in the same word - the distance is the word with that bit cleared, a multiple of 16 - and says: every seed
+                                 // window that starts in this block and is valid on the target's side lies wholly inside the repeated stretch, so its key IS the query's
+                                 // key at position - distance and that entry IS in the index.  A matcher may then take a bucket of exactly one entry for that entry
+                                 // without reading it.  Without the bit the comparison of the keys decides, as before.
 };
 
 __device__ __forceinline__ void set_insert(const JoinArgs &a, uint64_t k)
@@ -480,6 +484,10 @@ __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
                     uint32_t ends[2]; __builtin_memcpy(ends, a.start + b, 8); e0 = ends[0]; e1 = ends[1];
                 }
                 if (a.debug == 2) { n_hit += e1 - e0; e1 = e0; }
+                // a safe self position (JoinArgs::self_delta) whose bucket holds ONE entry: that entry is the query's own - the diagonal-0 self hit, counted and
+                // dropped below anyway.  It is not read: one dependent round trip less at about half of the self positions.  (An index left with empty buckets by
+                // a partition build that overflowed never shows a bucket of one here that is not real: its buckets hold none or a whole coarse bucket.)
+                else if ((sd & PEP_SELF_SAFE) && e1 - e0 == 1u && a.debug == 0) { ++n_hit; e1 = e0; }
             }
         }
         // two entries per trip (one unaligned 16-byte load): a bucket that holds the key usually holds one to four entries - the members of a
@@ -494,7 +502,7 @@ __global__ __launch_bounds__(256) void seed_match(SeedShape sh, JoinArgs a)
                 if (e + k >= e1 || (ent >> POS_BITS) != key) continue;
                 ++n_hit;
                 if (a.debug == 3) continue;
-                if ((int32_t)((uint32_t)p - (uint32_t)(ent & POS_MASK)) == sd) continue;      // a gene against itself on diagonal 0: settled by self_prepare
+                if ((int32_t)((uint32_t)p - (uint32_t)(ent & POS_MASK)) == (sd & ~PEP_SELF_SAFE)) continue;      // a gene against itself on diagonal 0: settled by self_prepare
                 const uint64_t hit = ((ent & POS_MASK) << 32) | p;
                 const uint32_t idx = atomicAdd(&nbuf, 1u);
                 if (idx < HIT_BUF) buf[idx] = hit;
@@ -616,6 +624,15 @@ __global__ __launch_bounds__(256) void seed_match_stride(JoinArgs a)
             }
         }
         const uint32_t tl = d0, tr = (d4 >> 16) | (d5 << 16);           // target bytes p - 4 .. p - 1 and p + 14 .. p + 17
+        // a gene against itself on diagonal 0 (self_prepare: the target repeats the query base for base, with the same length, and has settled the candidate):
+        // the bases next to the word are the same on both sides - or padding on both -, so the target's side alone says how many NW-mers the probe owns
+        auto self_owned = [&]() -> uint32_t {
+            const uint32_t vl = tl & 0xFCFCFCFCu, vr = tr & 0xFCFCFCFCu;
+            const int Ls = min(NS - 1, (int)(__clz((int)vl) >> 3)), Rs = vr ? min(NS - 1, (__ffs((int)vr) - 1) >> 3) : NS - 1;
+            return Ls >= NS - 1 - Rs ? (uint32_t)(Ls - (NS - 1 - Rs) + 1) : 0u;
+        };
+        // (as in seed_match: the one entry of a safe self position's bucket is the query's own word - counted from the target's side, never read)
+        if ((sd & PEP_SELF_SAFE) && e1 - e0 == 1u) { n_hit += self_owned(); e1 = e0; }
         for (uint32_t e = e0; e < e1; e += STRIDE_ENTRY_TRIP) {
             uint64_t pair[STRIDE_ENTRY_TRIP];
             __builtin_memcpy(pair, a.entries + e, 8 * STRIDE_ENTRY_TRIP);
@@ -624,14 +641,7 @@ __global__ __launch_bounds__(256) void seed_match_stride(JoinArgs a)
                 const uint64_t ent = pair[k2];
                 if (e + k2 >= e1 || (ent >> POS_BITS) != key) continue;
                 const uint32_t qpos = (uint32_t)(ent & POS_MASK);
-                if ((int32_t)(p - qpos) == sd) {
-                    // a gene against itself on diagonal 0 (self_prepare: the target repeats the query base for base, with the same length, and has settled the candidate):
-                    // the bases next to the word are the same on both sides - or padding on both -, so the target's side alone says how many there are; counted, not emitted
-                    const uint32_t vl = tl & 0xFCFCFCFCu, vr = tr & 0xFCFCFCFCu;
-                    const int Ls = min(NS - 1, (int)(__clz((int)vl) >> 3)), Rs = vr ? min(NS - 1, (__ffs((int)vr) - 1) >> 3) : NS - 1;
-                    if (Ls >= NS - 1 - Rs) n_hit += (uint32_t)(Ls - (NS - 1 - Rs) + 1);
-                    continue;
-                }
+                if ((int32_t)(p - qpos) == (sd & ~PEP_SELF_SAFE)) { n_hit += self_owned(); continue; }      // the self entry: counted, not emitted
                 uint32_t ql, qr;                                        // query bytes qpos - 4 .. qpos - 1 and qpos + 14 .. qpos + 17 (>= 16 bytes of padding around every sequence)
                 __builtin_memcpy(&ql, a.q_res + qpos - 4, 4);
                 __builtin_memcpy(&qr, a.q_res + qpos + NK, 4);
@@ -896,6 +906,8 @@ __global__ __launch_bounds__(256) void seed_runs_extend(JoinArgs a)
 //  2. If so, the 32-byte blocks of the target layout inside [ts, ts + ql) get delta = ts - qs: seed_match counts and DROPS the hits of those blocks whose query
 //     position is the target position - delta - the gene against itself on diagonal 0, 57 % of the raw hits of the 10 000-gene search.  (The block that holds
 //     ts begins in the padding in front of the target; a block that reaches beyond ts + ql is left out: behind the query's end lies another query.)
+//     Where no window of those blocks can hold a key the query does not hold, the distance carries PEP_SELF_SAFE and the matchers skip the entries read of a
+//     bucket of one (47.6 % and 48.1 % of the self positions of the 10 000-gene search, tools/self_singletons.py).
 //  3. Their candidate is settled here.  The candidate set is a SET, and (q, t, bin of diagonal 0) is in it iff ONE seed hit of that bin passes the ungapped
 //     pre-filter (oracle: find_candidates / ungapped_score).  The hits on diagonal 0 follow from the sequence alone: every position of the query that starts a
 //     seed of one of the shapes is a hit against the target that repeats it (same residues, same key, in the index by construction), and its extension is the
@@ -922,7 +934,24 @@ __global__ __launch_bounds__(256) void self_prepare(SeedShapeSet shs, int n_shap
         else for (uint32_t y = x; y < ql; ++y) same = same && a.q_res[qs + y] == a.t_res[ts + y];
     }
     if (!__all(same)) return;
-    for (uint32_t b = (ts >> 5) + (uint32_t)lane, b1 = (ts + ql) >> 5; b < b1; b += 64u) delta[b] = (int32_t)(ts - qs);
+    // The safe mark (JoinArgs::self_delta): every window that starts in a marked block and is valid on the target's side lies inside [ts, ts + ql).  In front of ts
+    // lies padding.  Behind ts + ql lies padding when the target ends there; when it goes on, the windows that run over the end are looked at one by one - a spaced
+    // shape steps over single residues, so a stop codon behind the stretch does not end them all - and ONE that is made of seeding letters leaves the target unmarked:
+    // its key is not the query's, and a bucket of one entry may hold a stranger's.
+    const uint32_t b1 = (ts + ql) >> 5;
+    bool safe = true;
+    if (tl != ql)
+        for (int s = 0; s < n_shapes; ++s) {
+            const SeedShape &sh = shs.s[s];
+            const uint32_t reach = (uint32_t)sh.offs[sh.weight - 1];                  // a window that starts at p ends at p + reach
+            for (uint32_t p = ts + ql - min(ql, reach) + (uint32_t)lane; p < (b1 << 5); p += 64u) {
+                bool seeds = true;
+                for (int i = 0; i < sh.weight; ++i) seeds = seeds && p + (uint32_t)sh.offs[i] < a.t_total && reduce_letter(sh, a.t_res[p + sh.offs[i]]) != 15u;
+                safe = safe && !seeds;
+            }
+        }
+    const int32_t mark = (int32_t)(ts - qs) | (__all(safe) ? PEP_SELF_SAFE : 0);
+    for (uint32_t b = (ts >> 5) + (uint32_t)lane; b < b1; b += 64u) delta[b] = mark;
     if (a.ungapped_min <= 0) return;                            // (no pre-filter: every hit nominates; the caller does not drop hits then)
     constexpr int STAGE1_LEN = 16;
     const int thr = a.ungapped_min, early = max(a.ungapped_min, a.stage1_min);
