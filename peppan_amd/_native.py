@@ -146,6 +146,21 @@ TREECUT_SIGNATURES = {
     'pep_tree_cut': (I, P, P, U32, P, P, P, P, P, P, P, P, P, P, U32, P, P, P, P, P),
     'pep_tree_cut_check': (I, P, U32, P, P, P, P, P, U32, P, U64),
 }
+# ... and of include/peppan_hip_batchprep.h (K26), for the same reason; tests/test_batchprep_host.py holds this one to the seventh header
+BATCHPREP_SIGNATURES = {
+    'pep_batch_screen': (I, P, U32, P, P, P, P, U64, F64, P, P, P, P, P),
+    'pep_batch_screen_check': (I, U32, P, P, P, U64, P, U64),
+    'pep_batch_unsure_walk': (I, U32, P, P, P, P, P, U64, P, P, U64),
+    'pep_batch_unsure_walk_check': (I, U32, P, P, P, P, P, U64, P, U64),
+    'pep_batch_prune': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64, F64, F64, U32, P, P, P, P, P, P),
+    'pep_batch_prune_check': (I, U32, U32, P, P, P, P, P, P, P, P, U64, U32, P, U64),
+}
+PREP_NJ, PREP_SBH = 0, 1                 # PEP_PREP_NJ, PEP_PREP_SBH: the mode of pep_batch_prune
+PREP_AUTO, PREP_LDS, PREP_WS = 0, 1, 2   # PEP_PREP_AUTO ..: its path
+PREP_LDS_ROWS = 4096                     # PEP_PREP_LDS_ROWS: rows of a gene whose working arrays stay in LDS
+PREP_MAX_ROWS = 65536                    # PEP_PREP_MAX_ROWS: rows of one gene
+PREP_MAX_CFL_BYTES = 1 << 31             # PEP_PREP_MAX_CFL_BYTES: conflict values of one call
+PREP_MAX_LOCI = 1 << 40                  # PEP_PREP_MAX_LOCI
 CUT_AUTO, CUT_BLOCK, CUT_CHAIN = 0, 1, 2   # PEP_CUT_AUTO ..: the path of pep_tree_cut
 CUT_ROUND = 8                            # PEP_CUT_ROUND: iterations of a launch chain between two reads of its `done` flag
 CUT_DEFAULT_CAP = 3000                   # PEP_CUT_DEFAULT_CAP: the reference's iterations per component
@@ -276,7 +291,7 @@ def load_library():
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
     for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()) + \
-            list(OUTALLELES_SIGNATURES.items()) + list(TREECUT_SIGNATURES.items()):
+            list(OUTALLELES_SIGNATURES.items()) + list(TREECUT_SIGNATURES.items()) + list(BATCHPREP_SIGNATURES.items()):
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -764,6 +779,55 @@ def _tree_cut_tables(n_leaves, sets):
     set_off = np.concatenate([[0], np.cumsum([s.size for s in sets])]).astype(np.uint64)
     flat = np.concatenate([s.reshape(-1) for s in sets]) if sets else np.zeros(0, np.uint64)
     return n, leaf_off, mat_off, branch_off, set_off, _some(flat)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+
+
+def _prep_offsets(what, gene_off, cols, cfl_off=None, cfl=None):
+    """the tables of a K26 call as the library takes them; ValueError where an array is shorter than its offsets table says (the library cannot see lengths)"""
+    gene_off = _u64(gene_off)
+    if len(gene_off) < 1:
+        raise ValueError('%s: gene_off needs one entry more than there are genes' % what)
+    n_rows = int(gene_off[-1])
+    cols = [_i64(c) for c in cols]
+    if any(len(c) != n_rows for c in cols):
+        raise ValueError('%s: every column needs gene_off[-1] = %d entries' % (what, n_rows))
+    if cfl_off is None:
+        return gene_off, cols
+    cfl_off, cfl = _u64(cfl_off), _i64(cfl)
+    if len(cfl_off) != n_rows + 1 or int(cfl_off[-1]) != len(cfl):
+        raise ValueError('%s: cfl_off needs one entry per row and one more, and must end at the length of cfl' % what)
+    return gene_off, cols, cfl_off, cfl
+
+
+def batch_screen_check(gene_off, col3, locus, n_loci):
+    """every check of Context.batch_screen, without a context or a device: PepError with the library's code and text, else None"""
+    gene_off, (col3, locus) = _prep_offsets('batch_screen', gene_off, (col3, locus))
+    _check_only('pep_batch_screen_check', len(gene_off) - 1, _ptr(gene_off), _ptr(_some(col3)), _ptr(_some(locus)), int(n_loci))
+
+
+def batch_unsure_walk(gene_off, col3, locus, cfl_off, cfl, n_loci, check_only=False):
+    """pep_batch_unsure_walk (host C++, no context): stage B of include/peppan_hip_batchprep.h (PEPPAN.py:579-593) over the genes in the order given ->
+    (col3 as the walk leaves it, popped uint8[n_genes]); check_only: pep_batch_unsure_walk_check, None"""
+    gene_off, (col3, locus), cfl_off, cfl = _prep_offsets('batch_unsure_walk', gene_off, (col3, locus), cfl_off, cfl)
+    n = len(gene_off) - 1
+    if check_only:
+        return _check_only('pep_batch_unsure_walk_check', n, _ptr(gene_off), _ptr(_some(col3)), _ptr(_some(locus)), _ptr(cfl_off), _ptr(_some(cfl)), int(n_loci))
+    col3, popped = col3.copy() if len(col3) else np.zeros(1, np.int64), np.zeros(max(n, 1), np.uint8)
+    _check_only('pep_batch_unsure_walk', n, _ptr(gene_off), _ptr(col3), _ptr(_some(locus)), _ptr(cfl_off), _ptr(_some(cfl)), int(n_loci), _ptr(popped))
+    return col3[:int(gene_off[-1])], popped[:n]
+
+
+def batch_prune_check(mode, gene_off, genome, col2, col3, col4, locus, cfl_off, cfl, n_loci, path=0):
+    """every check of Context.batch_prune, without a context or a device"""
+    gene_off, cols, cfl_off, cfl = _prep_offsets('batch_prune', gene_off, (genome, col2, col3, col4, locus), cfl_off, cfl)
+    _check_only('pep_batch_prune_check', int(mode), len(gene_off) - 1, _ptr(gene_off), *[_ptr(_some(c)) for c in cols], _ptr(cfl_off), _ptr(_some(cfl)), int(n_loci), int(path))
 
 
 def tree_cut_check(n_leaves, leaf_off, mat_off, branch_off, set_off, sets, path=0):
@@ -2032,6 +2096,34 @@ class Context(object):
             a, cuts = int(a), int(counts[t, 1])
             out.append((part[a:int(b)], int(counts[t, 0]), cuts, int(counts[t, 2]), log_where[a:a + cuts], log_val[a:a + cuts]))
         return out
+
+    # ---- K26
+    def batch_screen(self, gene_off, col3, locus, used_state, threshold):
+        """stage A of include/peppan_hip_batchprep.h (PEPPAN.py:548-562) for a batch of genes: column 3 and the locus ids of their tables one behind the other,
+        used_state uint8[n_loci] (0 absent, 1 present and <= 0, 2 present and > 0), threshold = (clust_identity - 0.02) * 10000 -> (column 3 rewritten, column 4,
+        present_iden int64[n_genes], excluded uint8[n_genes]).  The kernel time: self.prep_ms (zero unless set_timing(2))."""
+        gene_off, (col3, locus) = _prep_offsets('batch_screen', gene_off, (col3, locus))
+        used_state = np.ascontiguousarray(used_state, dtype=np.uint8).reshape(-1)
+        n, n_rows = len(gene_off) - 1, int(gene_off[-1])
+        out3, out4 = np.zeros(max(n_rows, 1), np.int64), np.zeros(max(n_rows, 1), np.int64)
+        present, excluded, ms = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8), np.zeros(2)
+        self._call('pep_batch_screen', n, _ptr(gene_off), _ptr(_some(col3)), _ptr(_some(locus)), _ptr(_some(used_state)), len(used_state), float(threshold),
+                   _ptr(out3), _ptr(out4), _ptr(present), _ptr(excluded), _ptr(ms))
+        self.prep_ms = float(ms[0])
+        return out3[:n_rows], out4[:n_rows], present[:n], excluded[:n]
+
+    def batch_prune(self, mode, gene_off, genome, col2, col3, col4, locus, cfl_off, cfl, n_loci, clust_identity, final_threshold, path=PREP_AUTO):
+        """stage C of include/peppan_hip_batchprep.h (PEPPAN.py:596-624, :641-656) for a batch of genes: columns 1 - 5 of their tables one behind the other, the
+        conflict lists as CSR over the rows, final_threshold = 10000 * clust_identity -> (out_off uint64[n_genes + 1], rows int32: per gene the source rows left
+        in final order, inparalog uint8[n_genes], final uint8[n_genes], n_ties).  mode: PREP_NJ, PREP_SBH; path: PREP_AUTO, PREP_LDS, PREP_WS."""
+        gene_off, cols, cfl_off, cfl = _prep_offsets('batch_prune', gene_off, (genome, col2, col3, col4, locus), cfl_off, cfl)
+        n, n_rows = len(gene_off) - 1, int(gene_off[-1])
+        out_off, rows = np.zeros(n + 1, np.uint64), np.zeros(max(n_rows, 1), np.int32)
+        inparalog, final, n_ties, ms = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(1, np.uint64), np.zeros(2)
+        self._call('pep_batch_prune', int(mode), n, _ptr(gene_off), *[_ptr(_some(c)) for c in cols], _ptr(cfl_off), _ptr(_some(cfl)), int(n_loci),
+                   float(clust_identity), float(final_threshold), int(path), _ptr(out_off), _ptr(rows), _ptr(inparalog), _ptr(final), _ptr(n_ties), _ptr(ms))
+        self.prep_ms = float(ms[0])
+        return out_off, rows[:int(out_off[-1])], inparalog[:n], final[:n], int(n_ties[0])
 
     # ---- K23
     def cds_genes(self, nt, contig_off, contig, win_off, win_len, strand, min_cds=0, mask=0, table4=False):
