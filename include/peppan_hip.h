@@ -50,6 +50,14 @@
  *                                       k + 1 genomes of every random genome order                      PEPPAN_parser.py:74-80
  *   pep_profile_pairs (+ _check)        the pair loop of getDistance: per pair of allelic profiles the genes both carry and the
  *                                       genes where both carry the same allele                          PEPPAN_parser.py:172-179
+ *   pep_kimura_pairs, pep_nj_trees (+ _check)   the two rapidnj calls: `rapidnj -i fa -t d` per paralogous group of filt_per_group and
+ *                                       `rapidnj -i pd` behind writeCGAV                                 PEPPAN.py:19, 409-417, PEPPAN_parser.py:168
+ *   pep_global_diff_walk (+ _size, _copy, _free; host C++) / pep_global_diff (+ _copy, _check)   get_global_difference: the dictionary walk over the
+ *                                       selected rows / the cross products per genome pair and their two means   PEPPAN.py:1611-1666
+ *   pep_cds_genes (+ _check)            the per-gene work of the GFF front end: iter_readGFF, checkPseu, addGenes   PEPPAN.py:117-182, 992-1010, 1013-1021
+ *   pep_out_alleles (+ _check)          the allele pass of write_output: windows, allele bytes, allele numbers   PEPPAN.py:1391-1472
+ *   pep_tree_cut (+ _check)             the tree cutting of filt_per_group, which the reference does with ete3   PEPPAN.py:424-482
+ *   pep_batch_screen / pep_batch_unsure_walk (host C++) / pep_batch_prune (+ _check each)   the front half of every round of filt_genes   PEPPAN.py:546-656
  */
 #ifndef PEPPAN_HIP_H
 #define PEPPAN_HIP_H
@@ -62,9 +70,10 @@ extern "C" {
  * pep_verdict_result_free, pep_group_verdicts_times; and, additively again, K7's codon grid: pep_rescore_codons, pep_rescore_codons_check.
  * 18 gained pep_live_resources; and, additively, the K17 entry points: pep_gene_ingroups, pep_gene_ingroups_check, pep_gene_ingroups_times.
  * 19 took in the sections of K18, K19 and K20, which had headers and version numbers of their own (pep_synteny_version, pep_genestruct_version and
- * pep_parser_version are gone), and replaced the six pep_*_times read-outs of K15 - K20 by pep_call_times. */
-#define PEP_ABI_VERSION 19
-/* K21 (neighbour-joining trees), additive under ABI 19, is declared in a header of its own for now: include/peppan_hip_tree.h */
+ * pep_parser_version are gone), and replaced the six pep_*_times read-outs of K15 - K20 by pep_call_times.
+ * 20 took in the sections of K21 - K26, which had headers of their own, and replaced the trailing `ms` out-array parameter of their eight device entry
+ * points by pep_call_times selectors (PEP_CALL_KIMURA_PAIRS .. PEP_CALL_BATCH_PRUNE); struct pep_call_times grew from four to PEP_CALL_MS times. */
+#define PEP_ABI_VERSION 20
 
 #define PEP_OK 0
 #define PEP_ERR_HIP (-1)       /* a HIP runtime call failed */
@@ -232,9 +241,10 @@ int pep_set_result_mode(pep_ctx *ctx, int on_device);
  * leaves the GPU idle for about 6 us between the two kernels it separates.  level 0 (the default): none, the fields stay 0;
  * 1: the Smith-Waterman score pass only (ms_sw); 2: every phase (sixteen events per search).  ms_k1 (pep_translate) follows the same switch. */
 int pep_set_timing(pep_ctx *ctx, int level);
-/* The times of the context's newest call of one of K15 - K20: ms[] are kernel times on the context's stream, measured when pep_set_timing is 2 (else 0) unless
+/* The times of the context's newest call of one of K15 - K26: ms[] are kernel times on the context's stream, measured when pep_set_timing is 2 (else 0) unless
  * the kernel's section says otherwise, and the byte counts are what the call moved each way.  What each slot holds is stated in the kernel's section below; a slot
- * or a byte count a kernel does not use reads 0.  A call resets its own record when it starts (K20's two calls share one: see there) and touches no other.  PEP_ERR_ARG: a null ctx or out, a `which`
+ * or a byte count a kernel does not use reads 0.  The byte counts of K21 - K26 (selectors 6 - 13) are not counted: they read 0.  A call resets its own record when
+ * it starts (K20's two calls share one: see there) and touches no other, so a call that its checks refuse leaves zeros.  PEP_ERR_ARG: a null ctx or out, a `which`
  * outside [0, PEP_CALL_COUNT).  (The struct goes by its tag: the function has its name.) */
 #define PEP_CALL_ALLELE_DIFF 0        /* pep_allele_diff */
 #define PEP_CALL_GROUP_VERDICTS 1     /* pep_group_verdicts (+ pep_verdict_detail_copy) */
@@ -242,8 +252,17 @@ int pep_set_timing(pep_ctx *ctx, int level);
 #define PEP_CALL_SYNTENY_PAIRS 3      /* pep_synteny_pairs (+ pep_synteny_pairs_copy) */
 #define PEP_CALL_GENE_STRUCTURE 4     /* pep_gene_structure */
 #define PEP_CALL_PARSER 5             /* pep_rarefaction_curves and pep_profile_pairs */
-#define PEP_CALL_COUNT 6
-struct pep_call_times { double ms[4]; uint64_t bytes_to_device, bytes_to_host; };
+#define PEP_CALL_KIMURA_PAIRS 6       /* pep_kimura_pairs */
+#define PEP_CALL_NJ_TREES 7           /* pep_nj_trees */
+#define PEP_CALL_GLOBAL_DIFF 8        /* pep_global_diff */
+#define PEP_CALL_CDS_GENES 9          /* pep_cds_genes */
+#define PEP_CALL_OUT_ALLELES 10       /* pep_out_alleles */
+#define PEP_CALL_TREE_CUT 11          /* pep_tree_cut */
+#define PEP_CALL_BATCH_SCREEN 12      /* pep_batch_screen */
+#define PEP_CALL_BATCH_PRUNE 13       /* pep_batch_prune */
+#define PEP_CALL_COUNT 14
+#define PEP_CALL_MS 8                 /* (pep_out_alleles has six stages) */
+struct pep_call_times { double ms[PEP_CALL_MS]; uint64_t bytes_to_device, bytes_to_host; };
 int pep_call_times(const pep_ctx *ctx, int which, struct pep_call_times *out);
 /* K2..K8: seeds, candidates, banded Smith-Waterman, traceback, filters, top-k.  Hits ordered by (q, t). */
 int pep_search(pep_ctx *ctx, const pep_search_params *params, pep_result **out);
@@ -563,6 +582,434 @@ int pep_profile_pairs_check(uint32_t n, uint64_t n_genes, char *msg, uint64_t ms
 
 /* pep_call_times(PEP_CALL_PARSER): ms[0] of the newest pep_rarefaction_curves and ms[1] of the newest pep_profile_pairs of the context: their kernel
  * times when pep_set_timing is 2 (else 0) - each call resets its own slot only -, and the bytes the newer of the two calls sent to the device and to the host */
+
+/* ---- K21: neighbour-joining trees, the two rapidnj calls of the reference (PEPPAN.py:19, 409-417: `rapidnj -i fa -t d` per paralogous group of
+ * filt_per_group; PEPPAN_parser.py:168: `rapidnj -i pd` behind writeCGAV).
+ * trees of up to this many leaves are joined by one workgroup each (all of them in one launch per size class); larger ones by a chain of launches, two per join */
+#define PEP_NJ_BLOCK_LEAVES 256
+/* leaves of one tree */
+#define PEP_NJ_MAX_LEAVES 8192
+/* bytes of distance matrices of one pep_nj_trees call (8 * dist_off[n_trees]); bytes of pair counts of one pep_kimura_pairs call */
+#define PEP_NJ_MAX_BYTES (1ull << 30)
+
+/* K21a: the three pair counts of Kimura's distance, which `rapidnj -i fa` computes from the FASTA the reference writes (PEPPAN.py:19, 409-417).  Rows and
+ * groups exactly as for pep_allele_diff: base-5 packed rows, row_off[n_rows + 1], row_len[n_rows], grp_off[n_groups + 1], grp_rows = row indices, the rows
+ * of a group of one row_len.  For every pair a < b of group g, in the row-major order of pep_allele_diff's packed triangle, three int32 at
+ * out[out_off[g] + 3 * pair]: the columns where both codes are 1..4 (comparable), among those the columns A <-> G or C <-> T (transitions: codes 1 <-> 3,
+ * 2 <-> 4), and the other mismatching comparable columns (transversions).  Raw counts, without pep_allele_diff's + 1 / + 2; the logarithm is host work
+ * (peppan_amd/njtree.py: kimura_distances).  out_off[g] and out_cap count int32 values.  Empty batches, empty groups and groups of one row are legal.
+ * PEP_ERR_ARG: what pep_allele_diff names for rows and groups, an output that runs past out_cap or overlaps another group's.  PEP_ERR_LIMIT: more than
+ * PEP_NJ_MAX_BYTES of counts, or what pep_allele_diff names for the bit planes; the message says how much was asked for.
+ * pep_call_times(PEP_CALL_KIMURA_PAIRS): of the newest call, ms[0], ms[1] the kernel times - bit planes, pairs - when pep_set_timing is 2, zeros otherwise. */
+int pep_kimura_pairs(pep_ctx *ctx, const uint8_t *packed, const uint64_t *row_off, const uint32_t *row_len, uint64_t n_rows, uint32_t n_groups,
+                     const uint64_t *grp_off, const uint32_t *grp_rows, int32_t *out, const uint64_t *out_off, uint64_t out_cap);
+
+/* K21b: neighbour joining over a batch of distance matrices (what rapidnj does for PEPPAN.py:416 and PEPPAN_parser.py:168).  Matrix t is row-major
+ * double[n][n], n = n_leaves[t], at dist + dist_off[t]; only entries with row < column are read.  dist_off and out_off have n_trees + 1 entries, the last
+ * one the length of the array (of dist in doubles; of node and length in entries): dist_off[t] + n * n <= dist_off[t + 1] and out_off[t] + 2 n - 3 <=
+ * out_off[t + 1] (n = 2: + 2), so no two trees overlap and none runs past its array.  Entries of node / length between two trees are zeroed.
+ *
+ * The arithmetic, every operation one correctly rounded double operation (nothing is contracted into a fused multiply-add): slots 0 .. n - 1 hold the
+ * leaves, node[slot] the node id (leaves 0 .. n - 1, join s creates node n + s).  r[k] = D[k,0] + D[k,1] + .. from 0.0, left to right, the diagonal as 0.
+ * With m live slots, m > 3: over live a < b, Q = ((m - 2) * D[a,b] - r[a]) - r[b]; the smallest Q below +infinity wins (a NaN never), ties go to the smaller
+ * a, then the smaller b; when no Q is below +infinity, the first two live slots.  la = 0.5 * D[a,b] + (r[a] - r[b]) / (2 * (m - 2)), lb = D[a,b] - la.  For every other
+ * live k: du = ((D[a,k] + D[b,k]) - D[a,b]) * 0.5, r[k] = ((r[k] - D[a,k]) - D[b,k]) + du, D[a,k] = D[k,a] = du.  Then r[a] = 0.5 * ((r[a] + r[b]) - m * D[a,b]),
+ * slot a becomes node n + s, slot b is retired.  At m = 3, live a < b < c: la = 0.5 * ((D[a,b] + D[a,c]) - D[b,c]), lb = D[a,b] - la, lc = D[a,c] - la.
+ * n = 2: both leaves get D[0,1].
+ * Output of tree t at out_off[t], 2 n - 3 entries of node[] and length[]: for s = 0 .. n - 4 the two joined node ids (slot a's first) and la, lb; then the
+ * last three node ids in slot order with la, lb, lc; n = 2: two entries.  One exception, so that the text of a three-leaf tree is rapidnj's character for
+ * character: n = 3 gives leaves 1, 0, 2 with lb, la, lc, the order rapidnj prints them in (('B':..,'A':..,'C':..);).
+ * PEP_ERR_ARG: a null table, n < 2, offsets that overlap or run past their arrays, a distance of the read triangle that is not finite (the message names
+ * tree, row and column).  PEP_ERR_LIMIT: n > PEP_NJ_MAX_LEAVES, more than PEP_NJ_MAX_BYTES of matrices; the message says how much was asked for.
+ * n_trees == 0 is legal.
+ * pep_call_times(PEP_CALL_NJ_TREES): of the newest call, ms[0] the time of the one-workgroup-per-tree kernels, ms[1] of the launch chains, when pep_set_timing
+ * is 2, zeros otherwise. */
+int pep_nj_trees(pep_ctx *ctx, const double *dist, const uint64_t *dist_off, const uint32_t *n_leaves, uint32_t n_trees, uint32_t *node, double *length,
+                 const uint64_t *out_off);
+/* every check of pep_nj_trees that does not read a distance, without a context or a device: its code, its text in msg[msg_cap] (cut to fit) */
+int pep_nj_trees_check(const uint32_t *n_leaves, uint32_t n_trees, const uint64_t *dist_off, const uint64_t *out_off, char *msg, uint64_t msg_cap);
+
+/* ---- K22: the genome-pair identity statistics of the reference's get_global_difference (PEPPAN.py:1611-1666), the (mean, sigma) table that K16
+ * (orthofilter.gd_table) and K17 (ingroups.initializing) read.
+ *
+ * The function is cut in two.  The ORDER-DEPENDENT part (:1632-1659 without its two inner loops) is a dictionary walk over the selected rows that only
+ * decides which two member lists meet at each row; it costs the sum of the list lengths and is host C++ (pep_global_diff_walk), like pep_similar_scan.
+ * The QUADRATIC part - the cross product of the two lists of every row, grouped by genome pair, and the two means per pair - is the device's
+ * (pep_global_diff).  The host tail (:1663-1665: two clamps, np.sqrt, np.exp) stays numpy (peppan_amd/globaldiff.py).
+ * distinct genomes of one call: the keys live in a dense triangular table of G (G + 1) / 2 entries */
+#define PEP_GDIFF_MAX_GENOMES 16384
+/* items (list-pair members, the sum of a_len * b_len over the events) of one call: at most this many */
+#define PEP_GDIFF_MAX_ITEMS (1ull << 32)
+/* entries of the logarithm table: a value code is 0 .. PEP_GDIFF_TABLE - 1 (1.005 - code / 10000 stays positive) */
+#define PEP_GDIFF_TABLE 10050
+/* items of one chunk when chunk_items is 0, and the most a caller may ask for (the chunk's keys are sorted by pep_sort_u64) */
+#define PEP_GDIFF_CHUNK_ITEMS (1u << 24)
+#define PEP_GDIFF_MAX_CHUNK_ITEMS (1u << 26)
+/* bytes of device workspace of one call, as computed from its sizes before anything is reserved */
+#define PEP_GDIFF_MAX_BYTES (1ull << 34)
+
+/* The host walk (no context, no device).
+ * clu / bsn: the selected rows (r, q, value) of the .clu.npy and the .bsn.npy table as int64[n][3], in file order, bsn already without its rows of
+ * value <= 0 (:1626).  genes / genome_of: the gene -> genome map, gene ids strictly ascending, the int32 genome of each.  Genome ids are signed (-1 is
+ * a legal genome and a legal key member); they are replaced by their ranks 0 .. G - 1 in ascending order over genome_of, which keeps the order of
+ * tuple(sorted(...)).
+ *
+ * The dictionary semantics of :1632-1659, literally.  A dictionary gene -> list, empty at the start.  A list is a span (off, len, cap) of the arena, an
+ * append-only array of genome ranks; `the list [g]` below is a new span of one entry at the arena's end.
+ *   clu row (r, q, i):  rr = the list of key r if the dictionary has one, else the list [r] (the key r itself, not a root).  qq = the list of key q,
+ *       which is REMOVED from the dictionary, else the list [q].  (r == q: rr and qq are the same list when it has one; else two lists [r].)  The event
+ *       (rr.off, rr.len, qq.off, qq.len, i, 0).  Then the dictionary's entry of r becomes rr + qq: with need = rr.len + qq.len, if need > rr.cap: when rr ends where
+ *       the arena ends the arena grows to make rr.cap = need, else rr moves - cap = 2 * need new entries (zeros) at the arena's end, its len
+ *       entries copied; then qq's len entries are copied behind rr's and rr.len = need.  Nothing that an earlier event names is ever overwritten.
+ *   bsn row (r, q, i):  rr and qq as above (q's entry removed); the event (.., i, 1); nothing is written back.
+ * An event names two prefixes of lists; drop_same = 0 for clu rows (same-genome pairs count), 1 for bsn rows (:1654).
+ * PEP_ERR_ARG: a null table; gene ids not strictly ascending; a gene of a row that is not in the map (the message names the gene); a value outside
+ * 0 .. PEP_GDIFF_TABLE - 1 (the message names the row: the reference would take the logarithm of a number that is not positive); an arena beyond 2^32 - 1.
+ * The message goes to msg (msg_cap bytes, 0-terminated).  *out: a handle to the result, to be freed by pep_global_diff_walk_free on every path that got one. */
+typedef struct pep_gdiff_walk pep_gdiff_walk;
+int pep_global_diff_walk(const int64_t *clu, uint64_t n_clu, const int64_t *bsn, uint64_t n_bsn, const int64_t *genes, const int32_t *genome_of,
+                         uint64_t n_genes, pep_gdiff_walk **out, char *msg, uint64_t msg_cap);
+/* events (one per row: n_clu + n_bsn), entries of the arena, distinct genomes G */
+int pep_global_diff_walk_size(const pep_gdiff_walk *walk, uint64_t *n_events, uint64_t *arena_len, uint32_t *n_genomes);
+/* events: int64[n_events][6] = (a_off, a_len, b_off, b_len, value, drop_same); arena: int32[arena_len] genome ranks; genomes: int32[G], the genome id of every rank */
+int pep_global_diff_walk_copy(const pep_gdiff_walk *walk, int64_t *events, int32_t *arena, int32_t *genomes);
+void pep_global_diff_walk_free(pep_gdiff_walk *walk);
+
+/* K22.  events and arena as the walk leaves them (a caller may bring its own), n_genomes = G, table = double[PEP_GDIFF_TABLE], for the reference
+ * np.log(1.005 - np.arange(10050) / 10000.) made by numpy on the host: element i is bit for bit the reference's logarithm of a value i.
+ *
+ * Item (a, b) of event e, 0 <= a < a_len, 0 <= b < b_len: key = (min, max) of arena[a_off + a] and arena[b_off + b]; value code = the event's value;
+ * sequence number = base(e) + a * b_len + b, base the exclusive sum of a_len * b_len over the events.  An item of two equal ranks in a drop_same event
+ * does not exist (its sequence number stays unused).  For every key with at least one item, with x_0 .. x_(n-1) = table[code] of its items in the order
+ * of their events (all items of one event have one code, so their order inside the event does not matter):
+ *   S(x) = numpy's sum of a float64 array as np.mean computes it: s = 0.0; for every buffer of 8192 elements (the last one shorter), left to right,
+ *          s = s + P(buffer).  P(v, n) is numpy's pairwise sum: n < 8: r = 0.0, r = r + v[i] left to right.  n <= 128: eight accumulators r[j] = v[j],
+ *          r[j] = r[j] + v[i + j] for i = 8, 16, .. while i + 8 <= n; r = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); then r = r + v[i] for the
+ *          rest.  n > 128: P(v, h) + P(v + h, n - h) with h = n / 2 - (n / 2) % 8.
+ *   m = S(x) / n,   v = S((x - m) * (x - m)) / n.
+ * Every operation is one correctly rounded IEEE double operation; nothing is contracted into a fused multiply-add.
+ * The call leaves the keys on the device: *n_keys is their number; pep_global_diff_copy fetches them, ordered by the smallest sequence number of each
+ * key - the insertion order of the reference's dictionary, also where two keys first appear inside one event.
+ *
+ * chunk_items: the lists are filled chunk by chunk - chunks of this many sequence numbers, cut in event order, an event larger than a chunk split by
+ * item range; 0 = PEP_GDIFF_CHUNK_ITEMS.  The result does not depend on it.
+ * PEP_ERR_ARG: a null table, an event that runs past the arena or has an empty list, a value code outside the table, a drop_same other than 0 / 1, a
+ * rank outside 0 .. G - 1 (the message names event or entry), chunk_items above PEP_GDIFF_MAX_CHUNK_ITEMS.  PEP_ERR_LIMIT, with the amount asked for in
+ * the message: G > PEP_GDIFF_MAX_GENOMES, more than PEP_GDIFF_MAX_ITEMS items, more than PEP_GDIFF_MAX_BYTES of workspace (keys counted as
+ * min(G (G + 1) / 2, items)).  No events, or no genomes, is legal and gives no keys.
+ * pep_call_times(PEP_CALL_GLOBAL_DIFF): of the newest call, ms[0] counting and offsets, ms[1] the chunks (emit, sort, copy), ms[2] the sums, when
+ * pep_set_timing is 2, zeros otherwise. */
+int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, const int32_t *arena, uint64_t arena_len, uint32_t n_genomes,
+                    const double *table, uint64_t chunk_items, uint64_t *n_keys);
+/* the keys of the newest pep_global_diff of this context, n_keys of them: the two ranks (g1 <= g2), the number of items, m and v.  PEP_ERR_ARG: n_keys is
+ * not what that call reported. */
+int pep_global_diff_copy(pep_ctx *ctx, uint64_t n_keys, int32_t *g1, int32_t *g2, uint64_t *n, double *mean, double *var);
+/* every check of pep_global_diff, without a context or a device: its code, its text in msg[msg_cap] (cut to fit) */
+int pep_global_diff_check(const int64_t *events, uint64_t n_events, const int32_t *arena, uint64_t arena_len, uint32_t n_genomes, uint64_t chunk_items,
+                          char *msg, uint64_t msg_cap);
+
+/* ---- K23: the verdict and the digest of every annotated CDS, the per-gene work of the reference's GFF front end - iter_readGFF (PEPPAN.py:117-182),
+ * checkPseu (:992-1010) and addGenes (:1013-1021) - which builds the gene dictionary that writeGenes and every later stage start from.
+ * The host (peppan_amd/gffgenes.py) reads the files, resolves names and makes the gene texts; the device judges and digests.
+ *
+ * The inputs.  nt: the contigs of a batch of files, one after another, contig c at nt[contig_off[c] .. contig_off[c + 1]): ASCII, ALREADY UPPER-CASED by
+ * the caller (:167).  CDS i is ONE window of ONE contig: win_len[i] bytes from the 0-based win_off[i] of contig contig[i] - the reference keeps the first
+ * line of a gene name and ignores every later one (the elif of :158 compares a bare sequence id with a prefixed one and is never true), so :170-172 cut
+ * exactly one slice.  strand[i] = 1: the window is read backward and complemented as rc() does (modules/configure.py:152-154): A <-> T, C <-> G, every
+ * other byte - N and '-' included - becomes N.  strand[i] = 0: the bytes as they stand.  Call the text so read s, L = win_len[i].
+ *
+ * The verdict, checkPseu (:992-1010).  The rules in this order, each but the first waived by its bit of `mask`:
+ *   1  L < min_cds                                                             (:993)
+ *   2  L % 3 != 0, unless PEP_CDS_ALLOW_FRAMESHIFT                             (:997)
+ *   The translation is frame 1 with marked starts (:1000; transeq, modules/configure.py:160-194), n = ceil(L / 3) codons, the last one padded with
+ *   characters outside the alphabet when L % 3 != 0 (:186-187).  A codon holding a '-' is '-' (:190) - also beside another odd character, also when the
+ *   '-' sits in a padded last codon; else a codon with a character outside ACGT is X (:191); else M for ATG GTG TTG (:172, and table[14]), X for TAA TAG
+ *   and - unless table4 - TGA (:168-170), anything else otherwise.
+ *   3  codon 0 is not M, unless PEP_CDS_ALLOW_NO_START                         (:1001)
+ *   4  codon n - 1 is not X, unless PEP_CDS_ALLOW_NO_STOP                      (:1004)
+ *   5  an X among codons 0 .. n - 2, unless PEP_CDS_ALLOW_INNER_STOP           (:1007)
+ *   0  otherwise.
+ * With one codon, codon 0 is codon n - 1.  L = 0 with min_cds = 0 has no codon: the reference raises there (iter_readGFF turns that into its code 6, addGenes
+ * lets it escape); the library answers as if no codon were M or X, and its Python callers never send such a window.  Codes 1 and 2 are decided before a
+ * byte is read.  Nothing outside the window is read.
+ *
+ * The digest (:178, :1020).  digest[20 i ..]: SHA-1 of s, the 20 bytes of hashlib.sha1(s).digest(), for every CDS of code 0; twenty zero bytes for the
+ * others.  It is computed straight from nt: no copy of s is made anywhere.
+ * a window holds fewer bytes than this */
+#define PEP_CDS_MAX_WINDOW (1u << 31)
+/* CDS of one call: fewer than this (n_cds is 32 bits wide; the Python binding refuses more) */
+#define PEP_CDS_MAX_ITEMS (1ull << 32)
+/* the bits of `mask`, one per letter of the reference's incompleteCDS parameter: s, i, f, e */
+#define PEP_CDS_ALLOW_NO_START 1
+#define PEP_CDS_ALLOW_INNER_STOP 2
+#define PEP_CDS_ALLOW_FRAMESHIFT 4
+#define PEP_CDS_ALLOW_NO_STOP 8
+
+/* every check of pep_cds_genes, without a context or a device (nt is not read): its code, its text in msg[msg_cap] (cut to fit).
+ * PEP_ERR_ARG: a null table; contig_off that does not start at 0 or decreases (offsets are 64 bits wide); a contig index outside 0 .. n_contigs - 1; a
+ * window that leaves its contig; a strand byte that is not 0 or 1; a mask with bits beyond the four.  PEP_ERR_LIMIT: a window of PEP_CDS_MAX_WINDOW bytes
+ * or more.  The message names the CDS.  n_cds = 0 is legal. */
+int pep_cds_genes_check(const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_cds, const uint32_t *contig, const uint64_t *win_off,
+                        const uint32_t *win_len, const uint8_t *strand, uint32_t mask, char *msg, uint64_t msg_cap);
+
+/* K23: code[n_cds] (0 .. 5) and digest[20 n_cds] as stated above.  Two launches on the context's stream - the verdicts, one wavefront per CDS; the digests of
+ * the CDS of code 0, one thread per CDS - with nothing in between; on an error nothing is written.
+ * pep_call_times(PEP_CALL_CDS_GENES): of the newest call, ms[0], ms[1] the kernel time of each launch - verdicts, digests - when pep_set_timing is 2, zeros otherwise. */
+int pep_cds_genes(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_cds, const uint32_t *contig,
+                  const uint64_t *win_off, const uint32_t *win_len, const uint8_t *strand, uint32_t min_cds, uint32_t mask, int table4,
+                  uint8_t *code, uint8_t *digest);
+
+/* ---- K24: the allele pass of the reference's write_output (PEPPAN.py:1391-1472) for a whole prediction table - which window determineGeneStructure is to
+ * look at for every prediction, which bytes are its allele, and which number that allele gets in its gene.
+ * The host (peppan_amd/outalleles.py) resolves names to indices, evaluates the reference's float expressions in float64 and formats the texts; the
+ * device sees integers and bytes only.
+ *
+ * The inputs.  nt: contigs one after another, contig c at nt[contig_off[c] .. contig_off[c + 1]), ASCII as the reference holds them.  The
+ * representative of a gene that has one (clust_ref) is appended as a contig of its own: seed_contig[g] names it, -1 = gene g has no seed.  Row i of the
+ * prediction table, in the table's order, is the PEP_OUTA_COLS int32 values rows[PEP_OUTA_COLS i ..]:
+ *   PEP_OUTA_GENE    index of column 0 among the distinct names (0 .. n_genes - 1; not read for a skipped row)
+ *   PEP_OUTA_CONTIG  index of column 5 (rows of one contig name carry one index: the neighbour search compares it)
+ *   PEP_OUTA_FLAGS   PEP_OUTA_MISC: column 15 is misc_feature; PEP_OUTA_NONAME: column 0 is empty; PEP_OUTA_SECONDARY: column 4 is not empty;
+ *                    PEP_OUTA_MINUS: column 11 is not '+'
+ *   PEP_OUTA_S, _E   columns 9 and 10, 1-based, inclusive: s, e
+ *   PEP_OUTA_PART    column 1        PEP_OUTA_QS, _QE  columns 7 and 8        PEP_OUTA_REFLEN  column 12        PEP_OUTA_CLEN  column 13 as it stands at :1390
+ *   PEP_OUTA_VARY    allowed_vary = int(col12 * (1 - pseudogene) + 0.01)  (:1408)
+ *   PEP_OUTA_SVMIN   0: no structural-variation test; else the smallest allele length that passes it, ceil(pseudogene * len(representative))  (:1461)
+ * look9 (optional, int32[n_rows]): column 9 as a row of an EARLIER batch of PEP_OUTA_BATCH rows shows it to a '-' row i with i % PEP_OUTA_BATCH < 5 -
+ * the reference writes determineGeneStructure's results back after every batch (:1468-1472), so those rows alone see updated neighbours.  NULL: s.
+ *
+ * The plan of row i, plan[PEP_OUTA_PLAN_COLS i ..]: class, s2, e2, lp, a, len.
+ *   PEP_OUTA_SKIPPED   PEP_OUTA_MISC or PEP_OUTA_NONAME (:1405).  Nothing else of the row is read or checked; it is in no class, its other outputs are zero.
+ *   PEP_OUTA_FRAGMENT  column 1 > 1 or e - s + 1 < col12 - allowed_vary (:1415).  s2 = s, e2 = e, lp = 0; the allele is [s - 1, e) of the contig.
+ *   PEP_OUTA_INTACT    otherwise (:1422-1458), with 3 int(x / 3) truncating toward zero.  pred2 is, for '+', the LAST row that is not PEP_OUTA_MISC among rows
+ *                      i + 1 .. i + 4, for '-' the FARTHEST such row among i - 1 .. i - 5, the walk ending at the table's end or at the first row of another contig.
+ *                        '+'  e2 = e + min(3 int((clen - e) / 3), pred2 ? 3 int((e(pred2) + 300 - e) / 3) : 600 + col12 - col8)
+ *                             s2 = s - min(3 int((s - 1) / 3), 60 + col7 - 1);  lp = s - s2, rp = e2 - e
+ *                        '-'  s2 = s - min(3 int((s - 1) / 3), pred2 ? 3 int((s - s9(pred2) + 300) / 3) : 600 + col12 - col8)
+ *                             e2 = e + min(3 int((clen - e) / 3), 60 + col7 - 1);  lp = e2 - e, rp = s - s2
+ *                      The window of determineGeneStructure is [s2 - 1, e2).  The allele is window[lp : len - rp] with Python's slice semantics: [s - 1, e) when
+ *                      rp >= 0, and the shorter [s - 1, e2) on '+' / [s2 - 1, e) on '-' when rp < 0 (a nested neighbour) - empty when that is no span.
+ *   PEP_OUTA_STRUCTVAR intact, and len < PEP_OUTA_SVMIN: the row does not go to determineGeneStructure (:1461-1462).
+ * a: the 0-based position of the allele's first byte in its contig, len: its bytes.  On '-' the allele is those bytes upper-cased, complemented and reversed,
+ * everything outside ACGTN becoming N (modules/configure.py:152-154); on '+' the bytes as they stand.
+ *
+ * The numbering.  Two rows that are not skipped are in one class when their genes and their allele bytes are equal; the seed of a gene is in front of all
+ * its rows.  first[i]: the smallest row index of the class of row i, -1 when that is the seed, -2 for a skipped row.  rank[i]: 1 + the number of classes of
+ * the gene whose first member comes before this one's - the number the reference's dictionary gives (:1420, :1455-1457), the seed being 1.  tflag[i]: 1 when
+ * the allele's id carries the 't' prefix, a property of the class's first member: never for the seed, always for a fragment, for an intact row unless
+ * PEP_OUTA_SECONDARY is clear, col7 = 1 and col8 = col12 (:1454).  None of it depends on the order in which the device worked.
+ *
+ * What is refused, PEP_ERR_ARG with the row in the message, for a row that is not skipped: s < 1; e < s - 1; e beyond the actual contig; col7 < 1;
+ * lp < 0 (the reference's slice would wrap); e2 < s2 - 1 (no window); e2 beyond the actual contig.  (s2 >= 1 follows from s >= 1.)  Also PEP_ERR_ARG: a
+ * null table; contig_off that does not start at 0 or decreases; a gene, contig or seed index out of range; flag bits beyond the four; key_bits > 31.
+ * PEP_ERR_LIMIT: a contig of PEP_OUTA_MAX_CONTIG bytes or more (positions are int32); n_rows + n_genes of PEP_OUTA_MAX_ITEMS or more. */
+#define PEP_OUTA_COLS 12
+#define PEP_OUTA_GENE 0
+#define PEP_OUTA_CONTIG 1
+#define PEP_OUTA_FLAGS 2
+#define PEP_OUTA_S 3
+#define PEP_OUTA_E 4
+#define PEP_OUTA_PART 5
+#define PEP_OUTA_QS 6
+#define PEP_OUTA_QE 7
+#define PEP_OUTA_REFLEN 8
+#define PEP_OUTA_CLEN 9
+#define PEP_OUTA_VARY 10
+#define PEP_OUTA_SVMIN 11
+/* the bits of PEP_OUTA_FLAGS */
+#define PEP_OUTA_MISC 1
+#define PEP_OUTA_NONAME 2
+#define PEP_OUTA_SECONDARY 4
+#define PEP_OUTA_MINUS 8
+/* the columns of a plan record and the classes */
+#define PEP_OUTA_PLAN_COLS 6
+#define PEP_OUTA_SKIPPED 0
+#define PEP_OUTA_FRAGMENT 1
+#define PEP_OUTA_INTACT 2
+#define PEP_OUTA_STRUCTVAR 3
+/* rows between two write-backs of the reference (:1401) */
+#define PEP_OUTA_BATCH 10000
+#define PEP_OUTA_MAX_CONTIG (1u << 31)
+#define PEP_OUTA_MAX_ITEMS (1u << 30)
+/* two rows that the digest put into one class hold different bytes: nothing was merged, nothing was written */
+#define PEP_ERR_ALLELE_CLASS (-24)
+
+/* every check of pep_out_alleles, without a context or a device (nt is not read): its code, its text in msg[msg_cap] (cut to fit).  n_rows = 0 is legal. */
+int pep_out_alleles_check(const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_genes, const int32_t *seed_contig, uint32_t n_rows,
+                          const int32_t *rows, const int32_t *look9, uint32_t key_bits, char *msg, uint64_t msg_cap);
+
+/* K24: plan[PEP_OUTA_PLAN_COLS n_rows], first[n_rows], rank[n_rows], tflag[n_rows] as stated above; on an error nothing is written.
+ * plan_only != 0: the plan alone (one launch; nt may be NULL and is not uploaded; first, rank and tflag may be NULL and are not written) - what the first of the
+ * reference's two rounds needs before column 9 of the earlier batches is known.
+ * Otherwise, on the context's stream: the plan; SHA-1 of every allele read in place, strand-corrected, one thread per allele; a table that gives every
+ * (gene, length, digest) its smallest member; a comparison of every member's bytes with that one's - a difference ends the call with PEP_ERR_ALLELE_CLASS and
+ * the two rows in the message; the library's radix sort over the first members by (gene, index), from which the ranks follow.
+ * key_bits (testing only, 0 in every other use): when 1 .. 31, a class is (gene, the low key_bits bits of the digest's first word) - distinct alleles then
+ * share classes, which is the one way to see the comparison refuse them.
+ * pep_call_times(PEP_CALL_OUT_ALLELES): of the newest call, ms[0..5] - plan, digest, classes, comparison, sort, ranks - kernel times when pep_set_timing is 2,
+ * zeros otherwise (plan_only: ms[0] alone; a call that ends with PEP_ERR_ALLELE_CLASS: zeros). */
+int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_genes, const int32_t *seed_contig,
+                    uint32_t n_rows, const int32_t *rows, const int32_t *look9, int plan_only, uint32_t key_bits, int32_t *plan, int32_t *first,
+                    uint32_t *rank, uint8_t *tflag);
+
+/* ---- K25: the tree cutting of filt_per_group (PEPPAN.py:424-482), which the reference does with ete3, for a batch of trees.
+ *
+ * What is restated.  :424-482 are a computation on the UNROOTED tree: a node's score is a sum over (leaves below) x (the component's other leaves) of a
+ * symmetric matrix, so it belongs to the branch's bipartition, whichever side is "below"; the two children of the root are one bipartition with one length
+ * (:440-442); the smallest leaf name, not the direction of the cut, decides which part stays in place (:466-467); pruning a subtree and suppressing the node
+ * of degree two (:462-465) leaves the tree induced on the remaining leaves, whose branches are the distinct non-trivial restrictions of the original
+ * bipartitions.  So the device works on bit sets of leaves and never roots a tree.  The rooting shows in exactly one place: an exact tie of the first two
+ * sort keys of :458 between two DIFFERENT bipartitions, where the reference reads n.dist, which its doubling of the root branch (:440-442) makes depend on
+ * ete3's midpoint rooting.  AT THESE TIES, AND ONLY THERE, THE REFERENCE'S CHOICE IS NOT RESTATED: the rule below decides, and every such tie is counted in
+ * n_ties for the caller to see.  ete3 itself cannot be run where this project is built; the contract therefore stands on two legs: PEPPAN.py:326-484
+ * themselves, run over a small stand-in for the ete3 calls they make, rooted two ways (tests/golden/make_golden_treecut.py), and a numpy restatement of the
+ * definition below, operation for operation (tests/treecut_helpers.py), which the device equals bit for bit.
+ *
+ * Input of tree t (n = n_leaves[t] leaves, 2 <= n <= PEP_NJ_MAX_LEAVES; words = (n + 63) / 64):
+ *   leaves         0 .. n - 1, in the order of the reference's leaf names read as integers (the leader rows g[0], ascending)
+ *   branches       B = branch_off[t + 1] - branch_off[t] of them, 1 <= B <= 2 n (2 n - 3 from a text of njtree.newick; 2 for n = 2).  Branch e: the bit
+ *                  set of the leaves on one of its sides, `words` 64-bit words at sets + set_off[t] + e * words (leaf l is bit l % 64 of word l / 64),
+ *                  and length[branch_off[t] + e], the printed %.5g value, since the reference parses the text
+ *   W0, W1         incompatible[:, :, 0] and [:, :, 1] (:400-404) compacted to the leaves, row-major double[n][n] at w0 / w1 + mat_off[t]; symmetric,
+ *                  every entry finite and >= 0
+ *   strong[leaf]   at strong + leaf_off[t]: non-zero when mat[leader, 4] >= (clust_identity - 0.02) * 10000, which the host evaluates in float64 (:469)
+ *   cap[t]         the iterations of one component (:435; the reference's 3000)
+ * Every offsets table has n_trees + 1 entries, the last one the length of its arrays: leaf_off[t] + n <= leaf_off[t + 1], mat_off[t] + n * n <=
+ * mat_off[t + 1], set_off[t] + B * words <= set_off[t + 1]; branch_off is dense.
+ *
+ * The definition.  M[a][b] = W1[a][b] where W0[a][b] > W1[a][b], else 0.0.  The queue of components (gene_phys, :431-473) starts as [all leaves]; component
+ * q is taken when its turn comes, T its leaves, t0 the smallest of them.  At most cap[t] times:
+ *   1. if W0[a][b] <= W1[a][b] for all a, b of T (the diagonal included, :438) the component is finished.
+ *   2. every branch e whose far side F = (side_e or its complement, whichever does not hold t0) restricted to T is not empty is a candidate; C = T \ F.
+ *      For each of the three matrices X = W0, W1, M the sum over a in F, b in C in this order: for a row a, lane l = 0 .. 63 holds p[l] = 0.0 + X[a][l] +
+ *      X[a][l + 64] + .. over the b = l, l + 64, .. that are in C, ascending; then for off = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l ^ off] for all l at once;
+ *      rowsum(a) = p[0].  s = 0.0, then s = s + rowsum(a) over the rows a of F, ascending.  This gives s0, s1, m.
+ *      ic0 = s0 / (s1 > 1.0 ? s1 : 1.0); key = ic0 * sqrt(m) (:451-456).  Every operation is one correctly rounded double operation, nothing is contracted;
+ *      the order depends on T and the branch alone, not on the batch, the launch geometry or the path.
+ *   3. among the candidates with ic0 > 1 whose key is no NaN the largest (key, ic0) wins (:456-458); branches with the same F are ONE candidate.  None: the
+ *      component is finished (:471-472).  Several different F with the winner's (key, ic0): the larger sum of the lengths of its inducing branches (0.0 +
+ *      length, ascending branch index) wins, then the smaller smallest leaf of F, then the lower branch index; n_ties grows by the number of the OTHER F.
+ *   4. the cut: T \ F keeps the component's place in the queue (:466-468); F is appended to the queue when one of its leaves is strong (:469-470) and is
+ *      dropped otherwise, its leaves belonging to no output.
+ * Output of tree t: part[leaf_off[t] + leaf] the index of the leaf's component in the queue - the order of the reference's returned list -, -1 for a dropped
+ * leaf; counts[4 t ..] = n_parts, n_cuts, n_ties, 0; and for cut c = 0 .. n_cuts - 1 (at most n - 1) the record i = leaf_off[t] + c: log_where[2 i] the
+ * component's index, log_where[2 i + 1] the lowest inducing branch index; log_val[4 i ..] = s0, s1, m, key.  Entries of part between two trees are -1, log entries
+ * behind a tree's records zero.
+ *
+ * Two paths that give identical bits: trees of up to PEP_NJ_BLOCK_LEAVES leaves are cut by one workgroup each, all of them in one launch, the bit sets in
+ * LDS; larger ones by a chain of launches, two per iteration (score, select-and-apply), enqueued PEP_CUT_ROUND iterations at a time with one read of the
+ * tree's `done` flag between rounds.  path: PEP_CUT_AUTO, PEP_CUT_BLOCK (PEP_ERR_LIMIT for a larger tree), PEP_CUT_CHAIN (any tree).
+ *
+ * PEP_ERR_ARG: a null table; n < 2; offsets that overlap or run past their arrays; B < 1 or B > 2 n; a branch that is no bipartition of the tree's leaves
+ * (a bit beyond leaf n - 1, an empty side, a side with every leaf); branches that are not pairwise compatible; an unknown path - all of these by
+ * pep_tree_cut_check as well -; and by pep_tree_cut alone, which reads them: a W entry or a length that is not finite, a negative W entry, W not symmetric.
+ * PEP_ERR_LIMIT: n > PEP_NJ_MAX_LEAVES, PEP_CUT_BLOCK for n > PEP_NJ_BLOCK_LEAVES, more than PEP_NJ_MAX_BYTES of one matrix (8 * mat_off[n_trees]) or of
+ * bit sets; the message says how much was asked for.  n_trees == 0 is legal.
+ * pep_call_times(PEP_CALL_TREE_CUT): of the newest call, ms[0] the time of the preparation and the one-workgroup kernel, ms[1] of the launch chains, when
+ * pep_set_timing is 2, else zeros. */
+#define PEP_CUT_AUTO 0
+#define PEP_CUT_BLOCK 1
+#define PEP_CUT_CHAIN 2
+/* iterations of a launch chain that are enqueued between two reads of the `done` flag */
+#define PEP_CUT_ROUND 8
+/* the reference's iterations per component (PEPPAN.py:435) */
+#define PEP_CUT_DEFAULT_CAP 3000
+
+int pep_tree_cut(pep_ctx *ctx, const uint32_t *n_leaves, uint32_t n_trees, const uint64_t *leaf_off, const uint64_t *mat_off, const uint64_t *branch_off,
+                 const uint64_t *set_off, const uint64_t *sets, const double *length, const double *w0, const double *w1, const uint8_t *strong,
+                 const uint32_t *cap, uint32_t path, int32_t *part, int32_t *counts, int32_t *log_where, double *log_val);
+/* every check of pep_tree_cut that reads no matrix and no length, without a context or a device: its code, its text in msg[msg_cap] (cut to fit) */
+int pep_tree_cut_check(const uint32_t *n_leaves, uint32_t n_trees, const uint64_t *leaf_off, const uint64_t *mat_off, const uint64_t *branch_off,
+                       const uint64_t *set_off, const uint64_t *sets, uint32_t path, char *msg, uint64_t msg_cap);
+
+/* ---- K26: the front half of every round of filt_genes (PEPPAN.py:546-624, and :641-656 for `--orthology sbh`) for one batch of genes: what stands
+ * between the gene scores and the `to_run` list of filt_per_group.
+ *
+ * Tables.  A gene's table is int64[n, 7] rows of the .tab store: 0 exemplar, 1 genome, 2 score x 10^4, 3 identity x 10^4, 4 a copy of column 3, 5 locus id,
+ * 6 hit count.  A batch is the tables of its genes one behind the other, handed over column by column: gene g owns the rows gene_off[g] .. gene_off[g + 1] - 1;
+ * gene_off has n_genes + 1 entries, starts at 0 and never falls.  The conflict lists (load_conflict, :511-523) are one CSR table over the batch's rows: row r
+ * owns cfl[cfl_off[r] .. cfl_off[r + 1] - 1], every value other_locus * 10 + kind (>= 0), in the order of the .conflicts store; cfl_off has gene_off[n_genes]
+ * + 1 entries, starts at 0 and never falls.  Locus ids lie in [0, n_loci), n_loci <= PEP_PREP_MAX_LOCI, and no locus comes twice in one gene's table.
+ *
+ * Stage A, pep_batch_screen (:548-562; device, order-free per gene because `used` is not written in that loop).  used_state[locus] says what `used` holds for
+ * the locus: 0 absent, 1 present with a value <= 0, anything else present with a value > 0.  For gene g with m = max(col3) over its rows (m > 0):
+ *   out4[r] = trunc((double)(10000 * col3[r]) / (double)m) - the product is an integer one, the quotient ONE float64 division, the cast cuts toward zero (:552);
+ *   state 0: out3[r] = col3[r] and the row counts for present[g] = max(0, out4 over these rows); state 1: out3[r] = -col3[r]; else: out3[r] = 0 (:553-558);
+ *   excluded[g] = (double)present[g] < threshold, where threshold is (clust_identity - 0.02) * 10000 as the host evaluated it in float64 (:559).
+ * The rows that go on are those with out3 != 0 (:562): the caller's gather.
+ *
+ * Stage B, pep_batch_unsure_walk (:579-593; host C++, no context, because one set `used2` of locus ids is shared by the whole round: a bitmap over
+ * [0, n_loci) here).  The genes come in the caller's order - falling score, stable (:580).  Per gene, with pos = the number of its rows with col3 > 0:
+ *   unsure = the number of rows with col3 > 0 whose locus is in used2; when (double)unsure >= (double)pos * 0.6 the gene is popped (popped[g] = 1) and nothing
+ *   else happens to it (:583-585; pos = 0 pops).  Otherwise, row by row in table order, negative rows included: when the row's locus is not in used2 every
+ *   value / 10 of its list enters used2 - at once, so a list can close the door on a later row of the same table; the row's own locus does not enter
+ *   (:588-590).  Then every third row with col3 < 0 is negated back, counting from the first one (:591-592).  The rows with col3 > 0 go on (:593).
+ * col3 is rewritten in place.
+ *
+ * Stage C, pep_batch_prune (device, order-free per gene: `used2` is a new set for every gene, :604 / :648).  Rows are named by their index within the gene's
+ * table (source rows); `order` is the current sequence of source rows, at first 0 .. n - 1.  Conflict values that name a locus outside the gene's own table
+ * have no effect in this stage.  Of an order: G = the number of distinct genomes, best(k) = the first row of the order with the genome of row k (:600),
+ * rs(k) = (double)col4[k] / (double)col4[best(k)], one float64 division (:601).  walk(order): used2 empty; row by row, a row whose locus is in used2 is dropped,
+ * of any other row every value / 10 of its list enters used2 (:604-610).
+ *  mode PEP_PREP_NJ (nj and ml, :596-624):
+ *   1. when n >= 2 G: the order sorted by falling column 2; walk; the survivors sorted by falling column 3; G, best, rs anew (:602-613).
+ *   2. when n > 3 G and n > 1000 (n now the rows left): cut = the (3 G)-th largest rs; when cut >= clust_identity, cut = the (6 G + 1)-th largest rs when
+ *      n > 6 G, else clust_identity; the rows with rs >= cut stay (:614-619).  The k-th largest is taken on the bit patterns of the doubles, a NaN (0 / 0)
+ *      above every number; NaN >= x and x >= NaN are false.  (The reference's sorted() gives no defined order to a list that holds a NaN.)
+ *   3. inparalog = some genome has more than one of the rows left (:620).  final = (not inparalog and (double)min(col3) >= final_threshold) or at most one row
+ *      left (:621), final_threshold being 10000 * clust_identity as the host evaluated it; every other gene is a `to_run` entry (:624).
+ *  mode PEP_PREP_SBH (:641-656): rs(k) = min((double)col2[k] / (double)col2[best(k)], (double)col4[k] / (double)col4[best(k)]), a NaN quotient making rs NaN; the
+ *   rows with rs >= clust_identity stay, a NaN dropping the row; walk in table order, WITH WHAT :653 COMPUTES: it adds the one-element list [locus * 10] to
+ *   the row's list, which is an array of the store wherever it is not empty, and numpy sums the two element by element - so of a kept row with a list
+ *   every (value + locus * 10) / 10 = value / 10 + locus enters used2, and of a kept row without one its own locus, which no other row carries; final
+ *   always; inparalog as above.
+ * TIES.  The reference sorts with numpy's default, unstable sort, whose order of equal keys depends on the machine's SIMD path.  THE REFERENCE'S ORDER OF
+ * EQUAL KEYS IS NOT RESTATED: here equal keys keep their current order in both sorts (the position is the low key).  Two rows that tie in column 2 at :603
+ * can change which row the walk keeps: n_ties counts, per call, the genes in which that sort met two equal keys.  Ties in column 3 at :611 change the
+ * order of the rows alone, never a value: equal |column 3| within one table means equal column 4.
+ * Output of gene g: rows[out_off[g] .. out_off[g + 1] - 1] the source rows left, in final order (the host gathers mat[rows]); inparalog[g]; is_final[g].
+ *
+ * Two paths of pep_batch_prune that give identical bits: a gene of up to PEP_PREP_LDS_ROWS rows has its working arrays (the order, a sort buffer, best) in
+ * LDS, a larger one in a slot of the context's workspace; one workgroup per gene either way, both in one call.  path: PEP_PREP_AUTO, PEP_PREP_LDS
+ * (PEP_ERR_LIMIT for a larger gene), PEP_PREP_WS (any gene).
+ *
+ * A DELIBERATE DIFFERENCE lies in front of these functions: for a member of the .conflicts store that does not exist the reference raises inside a pool
+ * worker; peppan_amd.paralogfilter reads it as "no conflicts" (empty lists).
+ *
+ * PEP_ERR_ARG (the message names the gene): a null table; gene_off or cfl_off that does not start at 0, falls (two genes or lists would overlap) or, for
+ * cfl_off, runs past the budget below; an empty gene in C; max(col3) <= 0 in A; a locus id outside [0, n_loci); a locus twice in one gene's table; a conflict
+ * value below 0 or (B) naming a locus outside [0, n_loci); a genome id outside [0, 2^32); column 3 or 4 (C: column 2 as well, to 2^62) of 2^31 or more in
+ * magnitude; an unknown mode or path; n_loci > PEP_PREP_MAX_LOCI.  PEP_ERR_LIMIT, with the amount asked for: a gene of more than PEP_PREP_MAX_ROWS rows;
+ * PEP_PREP_LDS for a gene of more than PEP_PREP_LDS_ROWS rows; more than PEP_PREP_MAX_CFL_BYTES of conflict values (8 bytes each) in one call.  n_genes == 0
+ * is legal.  Every check is made by the ..._check twin as well, without a context or a device; the context stays usable after a refusal.
+ * pep_call_times(PEP_CALL_BATCH_SCREEN) and pep_call_times(PEP_CALL_BATCH_PRUNE): of the newest pep_batch_screen / pep_batch_prune, ms[0] the kernel time of the
+ * call when pep_set_timing is 2, else zeros. */
+#define PEP_PREP_NJ 0
+#define PEP_PREP_SBH 1
+#define PEP_PREP_AUTO 0
+#define PEP_PREP_LDS 1
+#define PEP_PREP_WS 2
+/* rows of one gene whose working arrays stay in LDS (a power of two) */
+#define PEP_PREP_LDS_ROWS 4096
+/* rows of one gene: 2 000 genomes x 32 copies */
+#define PEP_PREP_MAX_ROWS 65536
+/* conflict values of one call, in bytes */
+#define PEP_PREP_MAX_CFL_BYTES (1ull << 31)
+#define PEP_PREP_MAX_LOCI (1ull << 40)
+
+int pep_batch_screen(pep_ctx *ctx, uint32_t n_genes, const uint64_t *gene_off, const int64_t *col3, const int64_t *locus, const uint8_t *used_state,
+                     uint64_t n_loci, double threshold, int64_t *out3, int64_t *out4, int64_t *present, uint8_t *excluded);
+int pep_batch_screen_check(uint32_t n_genes, const uint64_t *gene_off, const int64_t *col3, const int64_t *locus, uint64_t n_loci, char *msg, uint64_t msg_cap);
+int pep_batch_unsure_walk(uint32_t n_genes, const uint64_t *gene_off, int64_t *col3, const int64_t *locus, const uint64_t *cfl_off, const int64_t *cfl,
+                          uint64_t n_loci, uint8_t *popped, char *msg, uint64_t msg_cap);
+int pep_batch_unsure_walk_check(uint32_t n_genes, const uint64_t *gene_off, const int64_t *col3, const int64_t *locus, const uint64_t *cfl_off,
+                                const int64_t *cfl, uint64_t n_loci, char *msg, uint64_t msg_cap);
+int pep_batch_prune(pep_ctx *ctx, uint32_t mode, uint32_t n_genes, const uint64_t *gene_off, const int64_t *genome, const int64_t *col2, const int64_t *col3,
+                    const int64_t *col4, const int64_t *locus, const uint64_t *cfl_off, const int64_t *cfl, uint64_t n_loci, double clust_identity,
+                    double final_threshold, uint32_t path, uint64_t *out_off, int32_t *rows, uint8_t *inparalog, uint8_t *is_final, uint64_t *n_ties);
+int pep_batch_prune_check(uint32_t mode, uint32_t n_genes, const uint64_t *gene_off, const int64_t *genome, const int64_t *col2, const int64_t *col3,
+                          const int64_t *col4, const int64_t *locus, const uint64_t *cfl_off, const int64_t *cfl, uint64_t n_loci, uint32_t path, char *msg,
+                          uint64_t msg_cap);
 
 /* K14 and its two host passes: the consumer of the all-vs-all table (get_similar_pairs, PEPPAN.py:194-294).
  *

@@ -8,7 +8,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpeppan_hip.so')
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 MAX_SEQ_LEN = (1 << 23) - 256          # PEP_MAX_SEQ_LEN: longest single sequence of a packed set
 ALLELE_DIFF_MAX_BYTES = 1 << 31        # PEP_ALLELE_DIFF_MAX_BYTES: output (and bit planes) of one pep_allele_diff call
 
@@ -84,6 +84,28 @@ SIGNATURES = {
     'pep_rarefaction_curves_check': (I, P, U32, U64, P, U32, P, U64),
     'pep_profile_pairs': (I, P, P, U32, U64, P, P),
     'pep_profile_pairs_check': (I, U32, U64, P, U64),
+    'pep_kimura_pairs': (I, P, P, P, P, U64, U32, P, P, P, P, U64),
+    'pep_nj_trees': (I, P, P, P, P, U32, P, P, P),
+    'pep_nj_trees_check': (I, P, U32, P, P, P, U64),
+    'pep_global_diff_walk': (I, P, U64, P, U64, P, P, U64, P, P, U64),
+    'pep_global_diff_walk_size': (I, P, P, P, P),
+    'pep_global_diff_walk_copy': (I, P, P, P, P),
+    'pep_global_diff_walk_free': (None, P),
+    'pep_global_diff': (I, P, P, U64, P, U64, U32, P, U64, P),
+    'pep_global_diff_copy': (I, P, U64, P, P, P, P, P),
+    'pep_global_diff_check': (I, P, U64, P, U64, U32, U64, P, U64),
+    'pep_cds_genes_check': (I, P, U32, U32, P, P, P, P, U32, P, U64),
+    'pep_cds_genes': (I, P, P, P, U32, U32, P, P, P, P, U32, U32, I, P, P),
+    'pep_out_alleles_check': (I, P, U32, U32, P, U32, P, P, U32, P, U64),
+    'pep_out_alleles': (I, P, P, P, U32, U32, P, U32, P, P, I, U32, P, P, P, P),
+    'pep_tree_cut': (I, P, P, U32, P, P, P, P, P, P, P, P, P, P, U32, P, P, P, P),
+    'pep_tree_cut_check': (I, P, U32, P, P, P, P, P, U32, P, U64),
+    'pep_batch_screen': (I, P, U32, P, P, P, P, U64, F64, P, P, P, P),
+    'pep_batch_screen_check': (I, U32, P, P, P, U64, P, U64),
+    'pep_batch_unsure_walk': (I, U32, P, P, P, P, P, U64, P, P, U64),
+    'pep_batch_unsure_walk_check': (I, U32, P, P, P, P, P, U64, P, U64),
+    'pep_batch_prune': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64, F64, F64, U32, P, P, P, P, P),
+    'pep_batch_prune_check': (I, U32, U32, P, P, P, P, P, P, P, P, U64, U32, P, U64),
     'pep_similar_classify': (I, U64, P, P, P, P, P, P, P, P, P, P, P, F64, F64, P, P, P),
     'pep_similar_scan': (I, U64, P, P, P, P, P, U64, P, P, P, P, P, P, P, P, P, P),
     'pep_pair_support': (I, P, U64, P, P, U64, U64, P, P, P, P, P),
@@ -114,47 +136,7 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
-# ... and of include/peppan_hip_tree.h (K21), a table of its own for as long as it is a header of its own: tests/test_abi.py holds SIGNATURES and EXPORTS to
-# the prototypes of peppan_hip.h alone, tests/test_njtree_host.py holds this one to the second header
-TREE_SIGNATURES = {
-    'pep_kimura_pairs': (I, P, P, P, P, U64, U32, P, P, P, P, U64, P),
-    'pep_nj_trees': (I, P, P, P, P, U32, P, P, P, P),
-    'pep_nj_trees_check': (I, P, U32, P, P, P, U64),
-}
-# ... and of include/peppan_hip_gdiff.h (K22), for the same reason; tests/test_globaldiff_host.py holds this one to the third header
-GDIFF_SIGNATURES = {
-    'pep_global_diff_walk': (I, P, U64, P, U64, P, P, U64, P, P, U64),
-    'pep_global_diff_walk_size': (I, P, P, P, P),
-    'pep_global_diff_walk_copy': (I, P, P, P, P),
-    'pep_global_diff_walk_free': (None, P),
-    'pep_global_diff': (I, P, P, U64, P, U64, U32, P, U64, P, P),
-    'pep_global_diff_copy': (I, P, U64, P, P, P, P, P),
-    'pep_global_diff_check': (I, P, U64, P, U64, U32, U64, P, U64),
-}
-# ... and of include/peppan_hip_cds.h (K23), for the same reason; tests/test_gffgenes_host.py holds this one to the fourth header
-CDS_SIGNATURES = {
-    'pep_cds_genes_check': (I, P, U32, U32, P, P, P, P, U32, P, U64),
-    'pep_cds_genes': (I, P, P, P, U32, U32, P, P, P, P, U32, U32, I, P, P, P),
-}
-# ... and of include/peppan_hip_outalleles.h (K24), for the same reason; tests/test_outalleles_host.py holds this one to the fifth header
-OUTALLELES_SIGNATURES = {
-    'pep_out_alleles_check': (I, P, U32, U32, P, U32, P, P, U32, P, U64),
-    'pep_out_alleles': (I, P, P, P, U32, U32, P, U32, P, P, I, U32, P, P, P, P, P),
-}
-# ... and of include/peppan_hip_treecut.h (K25), for the same reason; tests/test_treecut_host.py holds this one to the sixth header
-TREECUT_SIGNATURES = {
-    'pep_tree_cut': (I, P, P, U32, P, P, P, P, P, P, P, P, P, P, U32, P, P, P, P, P),
-    'pep_tree_cut_check': (I, P, U32, P, P, P, P, P, U32, P, U64),
-}
-# ... and of include/peppan_hip_batchprep.h (K26), for the same reason; tests/test_batchprep_host.py holds this one to the seventh header
-BATCHPREP_SIGNATURES = {
-    'pep_batch_screen': (I, P, U32, P, P, P, P, U64, F64, P, P, P, P, P),
-    'pep_batch_screen_check': (I, U32, P, P, P, U64, P, U64),
-    'pep_batch_unsure_walk': (I, U32, P, P, P, P, P, U64, P, P, U64),
-    'pep_batch_unsure_walk_check': (I, U32, P, P, P, P, P, U64, P, U64),
-    'pep_batch_prune': (I, P, U32, U32, P, P, P, P, P, P, P, P, U64, F64, F64, U32, P, P, P, P, P, P),
-    'pep_batch_prune_check': (I, U32, U32, P, P, P, P, P, P, P, P, U64, U32, P, U64),
-}
+# limits and codes of the header's K21 - K26 sections; the host test of each kernel holds them to its #defines
 PREP_NJ, PREP_SBH = 0, 1                 # PEP_PREP_NJ, PEP_PREP_SBH: the mode of pep_batch_prune
 PREP_AUTO, PREP_LDS, PREP_WS = 0, 1, 2   # PEP_PREP_AUTO ..: its path
 PREP_LDS_ROWS = 4096                     # PEP_PREP_LDS_ROWS: rows of a gene whose working arrays stay in LDS
@@ -235,12 +217,16 @@ EVENT_CONFLICT, EVENT_SUPPORT = 0, 1
 INGROUP_MAX_IDEN = (1 << 31) - 1         # column 4 of a gene's table travels as int32
 
 
+CALL_MS = 8                              # PEP_CALL_MS: kernel times of one record
+
+
 class CallTimes(C.Structure):
-    """struct pep_call_times: what pep_call_times reports of the newest call of one of K15 - K20"""
-    _fields_ = [('ms', C.c_double * 4), ('bytes_to_device', C.c_uint64), ('bytes_to_host', C.c_uint64)]
+    """struct pep_call_times: what pep_call_times reports of the newest call of one of K15 - K26"""
+    _fields_ = [('ms', C.c_double * CALL_MS), ('bytes_to_device', C.c_uint64), ('bytes_to_host', C.c_uint64)]
 
 
-CALL_ALLELE_DIFF, CALL_GROUP_VERDICTS, CALL_GENE_INGROUPS, CALL_SYNTENY_PAIRS, CALL_GENE_STRUCTURE, CALL_PARSER, CALL_COUNT = range(7)      # PEP_CALL_*
+(CALL_ALLELE_DIFF, CALL_GROUP_VERDICTS, CALL_GENE_INGROUPS, CALL_SYNTENY_PAIRS, CALL_GENE_STRUCTURE, CALL_PARSER, CALL_KIMURA_PAIRS, CALL_NJ_TREES, CALL_GLOBAL_DIFF,
+ CALL_CDS_GENES, CALL_OUT_ALLELES, CALL_TREE_CUT, CALL_BATCH_SCREEN, CALL_BATCH_PRUNE, CALL_COUNT) = range(15)      # PEP_CALL_*
 
 
 class SupportLimits(C.Structure):
@@ -290,8 +276,7 @@ def load_library():
         from .configure import effective_cpus
         os.environ['PEPPAN_HOST_THREADS'] = str(max(1, min(4, effective_cpus() // 4)))
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, *argtypes) in list(SIGNATURES.items()) + list(TREE_SIGNATURES.items()) + list(GDIFF_SIGNATURES.items()) + list(CDS_SIGNATURES.items()) + \
-            list(OUTALLELES_SIGNATURES.items()) + list(TREECUT_SIGNATURES.items()) + list(BATCHPREP_SIGNATURES.items()):
+    for name, (restype, *argtypes) in SIGNATURES.items():
         if not hasattr(lib, name):
             raise PepError('libpeppan_hip.so does not export ' + name)
         fn = getattr(lib, name)
@@ -431,6 +416,24 @@ def _ptr_or_null(a):
 def _some(a):
     """`a`, or one zero element of its type when it has no entries, where the library is handed no null pointer"""
     return a if len(a) else np.zeros(1, a.dtype)
+
+
+def _as_bytes(nt):
+    """a nucleotide set given as bytes or as a uint8 array -> flat uint8 array (no copy of bytes)"""
+    return np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+
+
+def _calls_within(sizes, budget):
+    """packs items of `sizes` bytes, in order, into calls of at most `budget` bytes -> (lo, hi) per call; an item beyond the budget goes alone (the library
+    refuses it in its words)"""
+    lo = 0
+    while lo < len(sizes):
+        hi, total = lo + 1, sizes[lo]
+        while hi < len(sizes) and total + sizes[hi] <= budget:
+            total += sizes[hi]
+            hi += 1
+        yield lo, hi
+        lo = hi
 
 
 def _check_only(name, *args):
@@ -813,7 +816,7 @@ def batch_screen_check(gene_off, col3, locus, n_loci):
 
 
 def batch_unsure_walk(gene_off, col3, locus, cfl_off, cfl, n_loci, check_only=False):
-    """pep_batch_unsure_walk (host C++, no context): stage B of include/peppan_hip_batchprep.h (PEPPAN.py:579-593) over the genes in the order given ->
+    """pep_batch_unsure_walk (host C++, no context): stage B of include/peppan_hip.h (PEPPAN.py:579-593) over the genes in the order given ->
     (col3 as the walk leaves it, popped uint8[n_genes]); check_only: pep_batch_unsure_walk_check, None"""
     gene_off, (col3, locus), cfl_off, cfl = _prep_offsets('batch_unsure_walk', gene_off, (col3, locus), cfl_off, cfl)
     n = len(gene_off) - 1
@@ -1480,11 +1483,7 @@ class Context(object):
         self._view = None
         self._nt_match_on, self.last_nt_match = False, None
         self._grouping, self.labels = 0, None           # set_grouping: K10 as the tail of every search
-        self._verdict_stats = [np.zeros(4), 0]          # kernel times and bytes to the host, summed over the library calls of the newest group_verdicts
-        self.kimura_ms = self.nj_ms = (0., 0.)          # kernel times summed over the library calls of the newest kimura_pairs / nj_trees
-        self.global_diff_ms = (0., 0., 0.)              # kernel times of the newest global_diff
-        self.cds_ms = (0., 0.)                          # kernel times of the newest cds_genes
-        self.out_alleles_ms = (0.,) * 6                 # kernel times of the newest out_alleles: plan, digest, classes, comparison, sort, ranks
+        self._totals = {}                    # call_times(which, total=True): slot -> [ms, bytes to the device, bytes to the host], kept by _sum_times
         self.upload_generation = 0           # bumped by every call that replaces a device-resident sequence set (see RunBlast._ensure_nt)
         self.q_nt_token = self.r_nt_token = None     # what the nucleotide sets on the device were made from (set by RunBlast._ensure_nt, cleared by any set_*)
         if rc != 0:
@@ -1824,16 +1823,30 @@ class Context(object):
             res.append((t, e))
         return res
 
-    def _times(self, which):
-        """pep_call_times: the CallTimes record of the context's newest call `which` (CALL_*)"""
+    def call_times(self, which, total=False):
+        """pep_call_times of slot `which` (CALL_*) -> (ms float64[CALL_MS], bytes to the device, bytes to the host): the kernel times, measured when
+        set_timing(2) is on and zeros otherwise, and the bytes moved, as the slot's section of include/peppan_hip.h states them.  total=False: of the
+        newest library call of the slot.  total=True: summed over the library calls that the newest wrapper call of the slot made - a wrapper that
+        splits its batch (group_verdicts, kimura_pairs, nj_trees, tree_cuts) makes several, the wrappers of K21 - K26 that do not split make one;
+        zeros for a wrapper call that failed, and for the slots whose wrappers keep no sum (K15, K17 - K20)."""
+        if total:
+            ms, to_device, to_host = self._totals.get(which, (np.zeros(CALL_MS), 0, 0))
+            return ms.copy(), to_device, to_host
         t = CallTimes()
         self._call('pep_call_times', which, C.byref(t))
-        return t
+        return np.array(t.ms[:]), int(t.bytes_to_device), int(t.bytes_to_host)
+
+    def _sum_times(self, which, start=False):
+        """keeps the total of slot `which`: start=True as a wrapper call begins (zeros), otherwise after each of its library calls (adds that call's record)"""
+        if start:
+            self._totals[which] = [np.zeros(CALL_MS), 0, 0]
+        else:
+            self._totals[which] = [a + b for a, b in zip(self._totals[which], self.call_times(which))]
 
     def allele_diff_times(self):
         """of the newest allele_diff library call, in ms: (allele_planes, allele_diff) kernel times when set_timing(2) is on, else zeros, and the
         host's wall time from the end of the kernels until the output lay in the caller's buffer"""
-        return tuple(self._times(CALL_ALLELE_DIFF).ms[:3])
+        return tuple(self.call_times(CALL_ALLELE_DIFF)[0][:3].tolist())
 
     # ---- K16
     def group_verdicts(self, packed, row_off, row_len, groups, genomes, inparalog, gd, self_id, detail=True, out_budget=1 << 30):
@@ -1848,7 +1861,8 @@ class Context(object):
         packed, row_off, row_len, groups, genomes, inparalog = _verdict_inputs(packed, row_off, row_len, groups, genomes, inparalog)
         n = np.array([len(g) for g in groups], dtype=np.int64)
         plan = _plan_batch('group_verdicts', 'triangle', 8 * (n * (n - 1) // 2), row_len, groups, out_budget)
-        results, self._verdict_stats = [], [np.zeros(4), 0]
+        results = []
+        self._sum_times(CALL_GROUP_VERDICTS, start=True)
         for lo, hi, whole in plan:
             results += self._group_verdicts_call(packed, row_off, row_len, groups[lo:hi], genomes[lo:hi], inparalog[lo:hi], gd, self_id, detail, n[lo:hi], whole)
         return results
@@ -1870,9 +1884,7 @@ class Context(object):
                     tri, leader = np.empty((pairs.value, 2), dtype=np.int32), np.empty(int(n[g]), dtype=np.uint32)
                     self._call_on(handle, 'pep_verdict_detail_copy', g, _ptr(tri), _ptr(leader))
                 res.append((int(verdict[g]), tri, leader))
-            ms, moved = self.group_verdicts_times()
-            self._verdict_stats[0] += ms
-            self._verdict_stats[1] += moved
+            self._sum_times(CALL_GROUP_VERDICTS)          # (after the detail copies: their bytes count)
         finally:
             self._lib.pep_verdict_result_free(handle)
         return res
@@ -1880,12 +1892,13 @@ class Context(object):
     def group_verdicts_times(self):
         """of the newest pep_group_verdicts library call: (float64[4] kernel times in ms - bit planes, edge, pairs, leaders - when set_timing(2) is on,
         else zeros; bytes that call and the detail copies of its result sent to the host)"""
-        t = self._times(CALL_GROUP_VERDICTS)
-        return np.array(t.ms[:4]), int(t.bytes_to_host)
+        ms, _, to_host = self.call_times(CALL_GROUP_VERDICTS)
+        return ms[:4], to_host
 
     def group_verdicts_totals(self):
         """the same two figures summed over the library calls of the newest group_verdicts (one per part of a split batch)"""
-        return self._verdict_stats[0].copy(), int(self._verdict_stats[1])
+        ms, _, to_host = self.call_times(CALL_GROUP_VERDICTS, total=True)
+        return ms[:4], to_host
 
     # ---- K17
     def gene_ingroups(self, genome, iden, score, gene_off, gd, self_id, thr):
@@ -1901,8 +1914,8 @@ class Context(object):
 
     def gene_ingroups_times(self):
         """of the newest pep_gene_ingroups: (float64[2] kernel times in ms - pairs, finish - when set_timing(2) is on, else zeros; bytes the call sent to the host)"""
-        t = self._times(CALL_GENE_INGROUPS)
-        return np.array(t.ms[:2]), int(t.bytes_to_host)
+        ms, _, to_host = self.call_times(CALL_GENE_INGROUPS)
+        return ms[:2], to_host
 
     # ---- K18
     def synteny_pairs(self, member_off, genome, nb_off, nb, n_neighbor):
@@ -1921,8 +1934,8 @@ class Context(object):
 
     def synteny_times(self):
         """of the newest pep_synteny_pairs: (float64[3] kernel times in ms - count, scans, emit - when set_timing(2) is on, else zeros; bytes it sent to the host)"""
-        t = self._times(CALL_SYNTENY_PAIRS)
-        return np.array(t.ms[:3]), int(t.bytes_to_host)
+        ms, _, to_host = self.call_times(CALL_SYNTENY_PAIRS)
+        return ms[:3], to_host
 
     # ---- K19
     def gene_structure(self, nt, seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len, table4=False):
@@ -1932,7 +1945,7 @@ class Context(object):
         -> (frame int32[n]: the lowest tried frame that is a CDS or -1; start_aa, stop_aa uint32[n]: of that frame, of the first tried one when there is
         none, GENESTRUCT_NO_STOP without a stop; kind uint8[n]: the outcome of the first tried frame, an index of GENESTRUCT_KINDS), as
         include/peppan_hip.h states them"""
-        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        nt = _as_bytes(nt)
         args, n, keep_alive = _genestruct_tables(seq_off, seq, win_off, win_len, flags, lp, allowed_vary, ref_len)
         if len(nt) != int(keep_alive[0][-1]):
             raise ValueError('gene_structure: seq_off must end at the length of nt')
@@ -1943,8 +1956,8 @@ class Context(object):
 
     def gene_structure_times(self):
         """of the newest pep_gene_structure: (kernel time in ms when set_timing(2) is on, else 0; bytes it sent to the device; bytes it sent to the host)"""
-        t = self._times(CALL_GENE_STRUCTURE)
-        return float(t.ms[0]), int(t.bytes_to_device), int(t.bytes_to_host)
+        ms, to_device, to_host = self.call_times(CALL_GENE_STRUCTURE)
+        return float(ms[0]), to_device, to_host
 
     # ---- K20
     def rarefaction_curves(self, bits, n_genes, orders):
@@ -1981,20 +1994,21 @@ class Context(object):
     def parser_times(self):
         """of the newest pep_rarefaction_curves and pep_profile_pairs: (their kernel times in ms when set_timing(2) is on, else 0; bytes the newer of the two
         calls sent to the device; bytes it sent to the host)"""
-        t = self._times(CALL_PARSER)
-        return float(t.ms[0]), float(t.ms[1]), int(t.bytes_to_device), int(t.bytes_to_host)
+        ms, to_device, to_host = self.call_times(CALL_PARSER)
+        return float(ms[0]), float(ms[1]), to_device, to_host
 
     # ---- K21
     def kimura_pairs(self, packed, row_off, row_len, groups, out_budget=1 << 30):
         """the three pair counts of Kimura's distance, which `rapidnj -i fa` computes (PEPPAN.py:19, 409-417).  Rows and groups as for allele_diff.
         -> per group int32[n (n - 1) / 2, 3]: (comparable columns, transitions, transversions) of every pair a < b in the row-major order of allele_diff's
         packed triangle.  A batch beyond `out_budget` bytes of counts (at most the library's PEP_NJ_MAX_BYTES) or the library's budget of bit planes goes to
-        the library in several calls.  The kernel times, summed over the library calls: self.kimura_ms (bit planes, pairs; zeros unless set_timing(2))."""
+        the library in several calls.  The kernel times: call_times(CALL_KIMURA_PAIRS, total=True)."""
         out_budget = min(int(out_budget), NJ_MAX_BYTES)
         packed, row_off, row_len, groups = _group_inputs('kimura_pairs', packed, row_off, row_len, groups)
         n = np.array([len(g) for g in groups], dtype=np.int64)
         need = 3 * (n * (n - 1) // 2)                                 # int32 values per group
-        results, self.kimura_ms = [], (0., 0.)
+        results = []
+        self._sum_times(CALL_KIMURA_PAIRS, start=True)
         for lo, hi, whole in _plan_batch('kimura_pairs', 'pair counts', 4 * need, row_len, groups, out_budget):
             pk, ro, rl, gr = packed, row_off, row_len, groups[lo:hi]
             if not whole and len(gr):
@@ -2003,33 +2017,25 @@ class Context(object):
             pk, rl, grp_off, grp_rows = _group_tables(pk, rl, gr)
             out_off = np.concatenate([[0], np.cumsum(need[lo:hi])]).astype(np.uint64)
             out = np.empty(max(int(out_off[-1]), 1), dtype=np.int32)
-            ms = np.zeros(4)
             self._call('pep_kimura_pairs', _ptr(pk), _ptr(ro), _ptr(rl), n_rows, len(gr), _ptr(grp_off), _ptr(grp_rows),
-                       _ptr(out), _ptr(out_off), int(out_off[-1]), _ptr(ms))
-            self.kimura_ms = (self.kimura_ms[0] + float(ms[0]), self.kimura_ms[1] + float(ms[1]))
+                       _ptr(out), _ptr(out_off), int(out_off[-1]))
+            self._sum_times(CALL_KIMURA_PAIRS)
             results += [out[int(out_off[g]):int(out_off[g + 1])].reshape(-1, 3) for g in range(len(gr))]
         return results
 
     def nj_trees(self, matrices):
         """neighbour joining (what rapidnj does for PEPPAN.py:416 and PEPPAN_parser.py:168) over a list of square float64 distance matrices, of which the
-        entries with row < column are read.  -> per matrix (node uint32[2 n - 3], length float64[2 n - 3]) as include/peppan_hip_tree.h states them: for
+        entries with row < column are read.  -> per matrix (node uint32[2 n - 3], length float64[2 n - 3]) as include/peppan_hip.h states them: for
         every join the two joined node ids and their branch lengths, then the last three nodes; two entries for n = 2.  Batches beyond the library's
-        PEP_NJ_MAX_BYTES of matrices go to it in several calls.  The kernel times, summed over the library calls: self.nj_ms (one-workgroup kernels,
-        launch chains; zeros unless set_timing(2))."""
+        PEP_NJ_MAX_BYTES of matrices go to it in several calls.  The kernel times: call_times(CALL_NJ_TREES, total=True)."""
         mats = [np.ascontiguousarray(m, dtype=np.float64) for m in matrices]
         for t, m in enumerate(mats):
             if m.ndim != 2 or m.shape[0] != m.shape[1]:
                 raise ValueError('nj_trees: matrix %d is %s, not square' % (t, m.shape))
-        sizes = [m.size * 8 for m in mats]
-        self.nj_ms = (0., 0.)
-        results, lo = [], 0
-        while lo < len(mats):
-            hi, total = lo + 1, sizes[lo]                             # (a matrix beyond the budget goes alone: the library refuses it in its words)
-            while hi < len(mats) and total + sizes[hi] <= NJ_MAX_BYTES:
-                total += sizes[hi]
-                hi += 1
+        results = []
+        self._sum_times(CALL_NJ_TREES, start=True)
+        for lo, hi in _calls_within([m.size * 8 for m in mats], NJ_MAX_BYTES):
             results += self._nj_trees_call(mats[lo:hi])
-            lo = hi
         return results
 
     def _nj_trees_call(self, mats):
@@ -2038,20 +2044,19 @@ class Context(object):
         out_off = np.concatenate([[0], np.cumsum(np.where(n == 2, 2, 2 * n.astype(np.int64) - 3))]).astype(np.uint64)
         _check_only('pep_nj_trees_check', _ptr(n), len(n), _ptr(dist_off), _ptr(out_off))       # (before the copy below: a tree of one leaf would lay the offsets out wrongly)
         dist = np.concatenate([m.reshape(-1) for m in mats])
-        node, length, ms = np.zeros(int(out_off[-1]), np.uint32), np.zeros(int(out_off[-1]), np.float64), np.zeros(4)
-        self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off), _ptr(ms))
-        self.nj_ms = (self.nj_ms[0] + float(ms[0]), self.nj_ms[1] + float(ms[1]))
+        node, length = np.zeros(int(out_off[-1]), np.uint32), np.zeros(int(out_off[-1]), np.float64)
+        self._call('pep_nj_trees', _ptr(dist), _ptr(dist_off), _ptr(n), len(n), _ptr(node), _ptr(length), _ptr(out_off))
+        self._sum_times(CALL_NJ_TREES)
         return [(node[int(a):int(b)], length[int(a):int(b)]) for a, b in zip(out_off[:-1], out_off[1:])]
 
     # ---- K25
     def tree_cuts(self, sets, lengths, w0, w1, strong, cap=CUT_DEFAULT_CAP, path=CUT_AUTO):
-        """the tree cutting of filt_per_group (PEPPAN.py:424-482) for a batch of trees, as include/peppan_hip_treecut.h states it.  Per tree: sets uint64[B, words],
+        """the tree cutting of filt_per_group (PEPPAN.py:424-482) for a batch of trees, as include/peppan_hip.h states it.  Per tree: sets uint64[B, words],
         the leaves on one side of every branch as bits; lengths float64[B]; w0, w1 float64[n, n], incompatible[:, :, 0] and [:, :, 1] compacted to the leaves;
         strong bool[n]; cap: the iterations per component, one number or one per tree; path: CUT_AUTO, CUT_BLOCK, CUT_CHAIN.
         -> per tree (part int32[n]: the leaf's component in the reference's output order, -1 for a dropped leaf; n_parts; n_cuts; n_ties; log_where
         int32[n_cuts, 2]: component and lowest inducing branch of every cut; log_val float64[n_cuts, 4]: s0, s1, m, key).  Batches beyond the library's
-        PEP_NJ_MAX_BYTES of one matrix go to it in several calls.  The kernel times, summed over the library calls: self.cut_ms (the one-workgroup path with
-        the preparation, launch chains; zeros unless set_timing(2))."""
+        PEP_NJ_MAX_BYTES of one matrix go to it in several calls.  The kernel times: call_times(CALL_TREE_CUT, total=True)."""
         w0 = [np.ascontiguousarray(m, dtype=np.float64) for m in w0]
         w1 = [np.ascontiguousarray(m, dtype=np.float64) for m in w1]
         n_trees = len(w0)
@@ -2063,16 +2068,10 @@ class Context(object):
         caps = np.broadcast_to(np.asarray(cap, dtype=np.int64), (n_trees,))
         if n_trees and (caps.min() < 0 or caps.max() >= 1 << 32):
             raise ValueError('tree_cuts: cap is 0 .. 2^32 - 1')
-        sizes = [m.size * 8 for m in w0]
-        self.cut_ms = (0., 0.)
-        results, lo = [], 0
-        while lo < n_trees:
-            hi, total = lo + 1, sizes[lo]                             # (a matrix beyond the budget goes alone: the library refuses it in its words)
-            while hi < n_trees and total + sizes[hi] <= NJ_MAX_BYTES:
-                total += sizes[hi]
-                hi += 1
+        results = []
+        self._sum_times(CALL_TREE_CUT, start=True)
+        for lo, hi in _calls_within([m.size * 8 for m in w0], NJ_MAX_BYTES):
             results += self._tree_cuts_call(sets[lo:hi], lengths[lo:hi], w0[lo:hi], w1[lo:hi], strong[lo:hi], caps[lo:hi], path)
-            lo = hi
         return results
 
     def _tree_cuts_call(self, sets, lengths, w0, w1, strong, caps, path):
@@ -2087,10 +2086,10 @@ class Context(object):
         caps = np.ascontiguousarray(caps, dtype=np.uint32)
         n_leaf = int(leaf_off[-1])
         part, counts = np.full(n_leaf, -1, np.int32), np.zeros((len(n), 4), np.int32)
-        log_where, log_val, ms = np.zeros((n_leaf, 2), np.int32), np.zeros((n_leaf, 4), np.float64), np.zeros(4)
+        log_where, log_val = np.zeros((n_leaf, 2), np.int32), np.zeros((n_leaf, 4), np.float64)
         self._call('pep_tree_cut', _ptr(n), len(n), _ptr(leaf_off), _ptr(mat_off), _ptr(branch_off), _ptr(set_off), _ptr(flat), _ptr(length), _ptr(w0), _ptr(w1),
-                   _ptr(strong), _ptr(caps), int(path), _ptr(part), _ptr(counts), _ptr(log_where), _ptr(log_val), _ptr(ms))
-        self.cut_ms = (self.cut_ms[0] + float(ms[0]), self.cut_ms[1] + float(ms[1]))
+                   _ptr(strong), _ptr(caps), int(path), _ptr(part), _ptr(counts), _ptr(log_where), _ptr(log_val))
+        self._sum_times(CALL_TREE_CUT)
         out = []
         for t, (a, b) in enumerate(zip(leaf_off[:-1], leaf_off[1:])):
             a, cuts = int(a), int(counts[t, 1])
@@ -2099,93 +2098,96 @@ class Context(object):
 
     # ---- K26
     def batch_screen(self, gene_off, col3, locus, used_state, threshold):
-        """stage A of include/peppan_hip_batchprep.h (PEPPAN.py:548-562) for a batch of genes: column 3 and the locus ids of their tables one behind the other,
+        """stage A of K26 in include/peppan_hip.h (PEPPAN.py:548-562) for a batch of genes: column 3 and the locus ids of their tables one behind the other,
         used_state uint8[n_loci] (0 absent, 1 present and <= 0, 2 present and > 0), threshold = (clust_identity - 0.02) * 10000 -> (column 3 rewritten, column 4,
-        present_iden int64[n_genes], excluded uint8[n_genes]).  The kernel time: self.prep_ms (zero unless set_timing(2))."""
+        present_iden int64[n_genes], excluded uint8[n_genes]).  The kernel time: call_times(CALL_BATCH_SCREEN, total=True)."""
         gene_off, (col3, locus) = _prep_offsets('batch_screen', gene_off, (col3, locus))
         used_state = np.ascontiguousarray(used_state, dtype=np.uint8).reshape(-1)
         n, n_rows = len(gene_off) - 1, int(gene_off[-1])
         out3, out4 = np.zeros(max(n_rows, 1), np.int64), np.zeros(max(n_rows, 1), np.int64)
-        present, excluded, ms = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8), np.zeros(2)
+        present, excluded = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.uint8)
+        self._sum_times(CALL_BATCH_SCREEN, start=True)
         self._call('pep_batch_screen', n, _ptr(gene_off), _ptr(_some(col3)), _ptr(_some(locus)), _ptr(_some(used_state)), len(used_state), float(threshold),
-                   _ptr(out3), _ptr(out4), _ptr(present), _ptr(excluded), _ptr(ms))
-        self.prep_ms = float(ms[0])
+                   _ptr(out3), _ptr(out4), _ptr(present), _ptr(excluded))
+        self._sum_times(CALL_BATCH_SCREEN)
         return out3[:n_rows], out4[:n_rows], present[:n], excluded[:n]
 
     def batch_prune(self, mode, gene_off, genome, col2, col3, col4, locus, cfl_off, cfl, n_loci, clust_identity, final_threshold, path=PREP_AUTO):
-        """stage C of include/peppan_hip_batchprep.h (PEPPAN.py:596-624, :641-656) for a batch of genes: columns 1 - 5 of their tables one behind the other, the
+        """stage C of K26 in include/peppan_hip.h (PEPPAN.py:596-624, :641-656) for a batch of genes: columns 1 - 5 of their tables one behind the other, the
         conflict lists as CSR over the rows, final_threshold = 10000 * clust_identity -> (out_off uint64[n_genes + 1], rows int32: per gene the source rows left
-        in final order, inparalog uint8[n_genes], final uint8[n_genes], n_ties).  mode: PREP_NJ, PREP_SBH; path: PREP_AUTO, PREP_LDS, PREP_WS."""
+        in final order, inparalog uint8[n_genes], final uint8[n_genes], n_ties).  mode: PREP_NJ, PREP_SBH; path: PREP_AUTO, PREP_LDS, PREP_WS.  The kernel time:
+        call_times(CALL_BATCH_PRUNE, total=True)."""
         gene_off, cols, cfl_off, cfl = _prep_offsets('batch_prune', gene_off, (genome, col2, col3, col4, locus), cfl_off, cfl)
         n, n_rows = len(gene_off) - 1, int(gene_off[-1])
         out_off, rows = np.zeros(n + 1, np.uint64), np.zeros(max(n_rows, 1), np.int32)
-        inparalog, final, n_ties, ms = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(1, np.uint64), np.zeros(2)
+        inparalog, final, n_ties = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(1, np.uint64)
+        self._sum_times(CALL_BATCH_PRUNE, start=True)
         self._call('pep_batch_prune', int(mode), n, _ptr(gene_off), *[_ptr(_some(c)) for c in cols], _ptr(cfl_off), _ptr(_some(cfl)), int(n_loci),
-                   float(clust_identity), float(final_threshold), int(path), _ptr(out_off), _ptr(rows), _ptr(inparalog), _ptr(final), _ptr(n_ties), _ptr(ms))
-        self.prep_ms = float(ms[0])
+                   float(clust_identity), float(final_threshold), int(path), _ptr(out_off), _ptr(rows), _ptr(inparalog), _ptr(final), _ptr(n_ties))
+        self._sum_times(CALL_BATCH_PRUNE)
         return out_off, rows[:int(out_off[-1])], inparalog[:n], final[:n], int(n_ties[0])
 
     # ---- K23
     def cds_genes(self, nt, contig_off, contig, win_off, win_len, strand, min_cds=0, mask=0, table4=False):
-        """checkPseu (PEPPAN.py:992-1010) and the SHA-1 of the kept (:178, :1020) for a batch of CDS, as include/peppan_hip_cds.h states them.  nt: the contigs
+        """checkPseu (PEPPAN.py:992-1010) and the SHA-1 of the kept (:178, :1020) for a batch of CDS, as include/peppan_hip.h states them.  nt: the contigs
         as upper-cased ASCII bytes (bytes or uint8 array), contig c at nt[contig_off[c] .. contig_off[c+1]].  CDS p is win_len[p] bytes from the 0-based
         win_off[p] of contig contig[p], read backward and complemented when strand[p] is 1.  min_cds: 0 .. 2^31; mask: CDS_ALLOW bits; table4: TGA is no stop.
-        -> (code uint8[n]: 0 .. 5; digest uint8[n, 20]: hashlib.sha1(text).digest() where the code is 0, zeros elsewhere).  The kernel times: self.cds_ms
-        (verdicts, digests; zeros unless set_timing(2))."""
-        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        -> (code uint8[n]: 0 .. 5; digest uint8[n, 20]: hashlib.sha1(text).digest() where the code is 0, zeros elsewhere).  The kernel times:
+        call_times(CALL_CDS_GENES, total=True)."""
+        nt = _as_bytes(nt)
         args, n, keep_alive = _cds_tables(contig_off, contig, win_off, win_len, strand)
         if len(nt) != int(keep_alive[0][-1]):
             raise ValueError('cds_genes: contig_off must end at the length of nt')
         if not 0 <= int(min_cds) <= CDS_MAX_WINDOW or not 0 <= int(mask) < 1 << 32:
             raise ValueError('cds_genes: min_cds is 0 .. 2^31, mask 32 bits')
-        code, digest, ms = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 20), np.uint8), np.zeros(2)
-        self.cds_ms = (0., 0.)
-        self._call('pep_cds_genes', _ptr(_some(nt)), *args, int(min_cds), int(mask), 1 if table4 else 0, _ptr(code), _ptr(digest), _ptr(ms))
-        self.cds_ms = (float(ms[0]), float(ms[1]))
+        code, digest = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 20), np.uint8)
+        self._sum_times(CALL_CDS_GENES, start=True)
+        self._call('pep_cds_genes', _ptr(_some(nt)), *args, int(min_cds), int(mask), 1 if table4 else 0, _ptr(code), _ptr(digest))
+        self._sum_times(CALL_CDS_GENES)
         return code[:n], digest[:n]
 
     # ---- K24
     def out_alleles(self, nt, contig_off, seed_contig, rows, look9=None, plan_only=False, key_bits=0):
-        """the allele pass of write_output (PEPPAN.py:1391-1472) for a prediction table, as include/peppan_hip_outalleles.h states it.  nt: the contigs - and behind
+        """the allele pass of write_output (PEPPAN.py:1391-1472) for a prediction table, as include/peppan_hip.h states it.  nt: the contigs - and behind
         them the representatives, one contig each - as ASCII bytes (bytes or uint8 array), contig c at nt[contig_off[c] .. contig_off[c+1]]; seed_contig[g]: the
         contig that is gene g's representative, -1 for none; rows int32[n, OUTA_COLS]: the row records; look9 (optional, int32[n]): column 9 as the rows of
         earlier batches show it to the '-' rows at the head of a batch.
         -> (plan int32[n, OUTA_PLAN_COLS]: class, s2, e2, lp, a, len; first int32[n]; rank uint32[n]; tflag uint8[n]).  plan_only: the plan alone, nt is not read
-        (None will do) and the other three are None.  key_bits: for tests of the comparison pass alone.  The kernel times: self.out_alleles_ms (zeros unless
-        set_timing(2))."""
+        (None will do) and the other three are None.  key_bits: for tests of the comparison pass alone.  The kernel times:
+        call_times(CALL_OUT_ALLELES, total=True)."""
         args, n, keep_alive = _outalleles_tables(contig_off, seed_contig, rows, look9)
         if not 0 <= int(key_bits) < 1 << 32:
             raise ValueError('out_alleles: key_bits is 0 .. 31')
-        plan, ms = np.zeros((max(n, 1), OUTA_PLAN_COLS), np.int32), np.zeros(6)
-        self.out_alleles_ms = (0.,) * 6
+        plan = np.zeros((max(n, 1), OUTA_PLAN_COLS), np.int32)
+        self._sum_times(CALL_OUT_ALLELES, start=True)
         if plan_only:
-            self._call('pep_out_alleles', None, *args, 1, int(key_bits), _ptr(plan), None, None, None, _ptr(ms))
-            self.out_alleles_ms = tuple(float(v) for v in ms)
+            self._call('pep_out_alleles', None, *args, 1, int(key_bits), _ptr(plan), None, None, None)
+            self._sum_times(CALL_OUT_ALLELES)
             return plan[:n], None, None, None
-        nt = np.frombuffer(nt, dtype=np.uint8) if isinstance(nt, (bytes, bytearray, memoryview)) else np.ascontiguousarray(nt, dtype=np.uint8).reshape(-1)
+        nt = _as_bytes(nt)
         if len(nt) != int(keep_alive[0][-1]):
             raise ValueError('out_alleles: contig_off must end at the length of nt')
         first, rank, tflag = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8)
-        self._call('pep_out_alleles', _ptr(_some(nt)), *args, 0, int(key_bits), _ptr(plan), _ptr(first), _ptr(rank), _ptr(tflag), _ptr(ms))
-        self.out_alleles_ms = tuple(float(v) for v in ms)
+        self._call('pep_out_alleles', _ptr(_some(nt)), *args, 0, int(key_bits), _ptr(plan), _ptr(first), _ptr(rank), _ptr(tflag))
+        self._sum_times(CALL_OUT_ALLELES)
         return plan[:n], first[:n], rank[:n], tflag[:n]
 
     # ---- K22
     def global_diff(self, events, arena, n_genomes, table, chunk_items=0):
-        """the genome-pair sums of get_global_difference (PEPPAN.py:1637-1645, 1650-1662) as include/peppan_hip_gdiff.h states them.  events int64[n, 6] and
+        """the genome-pair sums of get_global_difference (PEPPAN.py:1637-1645, 1650-1662) as include/peppan_hip.h states them.  events int64[n, 6] and
         arena as global_diff_walk leaves them, table float64[10050] the logarithm of every value code.  -> (g1, g2, n, mean, var): per genome pair, in the
         order the reference's dictionary first meets them, the two ranks g1 <= g2, the number of values, numpy's mean of their logarithms and of the squared
-        deviations.  chunk_items (0 = the library's default) does not change the result.  The kernel times: self.global_diff_ms (counting, chunks, sums;
-        zeros unless set_timing(2))."""
+        deviations.  chunk_items (0 = the library's default) does not change the result.  The kernel times:
+        call_times(CALL_GLOBAL_DIFF, total=True)."""
         events, arena = _gdiff_tables(events, arena)
         table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
         if len(table) != GDIFF_TABLE:
             raise ValueError('global_diff: the table has %d entries, not %d' % (len(table), GDIFF_TABLE))
-        n_keys, ms = C.c_uint64(), np.zeros(4)
-        self.global_diff_ms = (0., 0., 0.)
+        n_keys = C.c_uint64()
+        self._sum_times(CALL_GLOBAL_DIFF, start=True)
         self._call('pep_global_diff', _ptr_or_null(events), len(events), _ptr_or_null(arena), len(arena), int(n_genomes), _ptr(table), int(chunk_items),
-                   C.byref(n_keys), _ptr(ms))
-        self.global_diff_ms = (float(ms[0]), float(ms[1]), float(ms[2]))
+                   C.byref(n_keys))
+        self._sum_times(CALL_GLOBAL_DIFF)
         k = n_keys.value
         g1, g2, n = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.uint64)
         mean, var = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)

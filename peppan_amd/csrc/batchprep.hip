@@ -1,5 +1,5 @@
 // K26: the front half of a round of filt_genes (PEPPAN.py:546-624, :641-656) for a batch of genes.  The definition, the tie rule of the two sorts and the
-// deliberate differences are in include/peppan_hip_batchprep.h; tests/batchprep_helpers.py restates it in plain Python and the library equals that bit for
+// deliberate differences are in include/peppan_hip.h (K26); tests/batchprep_helpers.py restates it in plain Python and the library equals that bit for
 // bit, so contraction into fused multiply-adds is switched off for the whole file.
 //   prep_screen      stage A, one workgroup per gene: the maximum of column 3, then per row the one float64 quotient, the look-up in used_state and the
 //                    maximum of the rows `used` does not hold.
@@ -18,7 +18,6 @@
 // Not tuned: the rates are in profiles/batchprep_rate.txt.  Known slack: three of a workgroup's four wavefronts wait during the walk; a bitonic network does
 // log^2 passes where a radix sort would do a handful; a workgroup of 256 threads for a gene of 5 rows.
 #include "common.h"
-#include "../../include/peppan_hip_batchprep.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -458,10 +457,11 @@ int pep_batch_screen_check(uint32_t n_genes, const uint64_t *gene_off, const int
 }
 
 int pep_batch_screen(pep_ctx *ctx, uint32_t n_genes, const uint64_t *gene_off, const int64_t *col3, const int64_t *locus, const uint8_t *used_state, uint64_t n_loci,
-                     double threshold, int64_t *out3, int64_t *out4, int64_t *present, uint8_t *excluded, double *ms)
+                     double threshold, int64_t *out3, int64_t *out4, int64_t *present, uint8_t *excluded)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_BATCH_SCREEN];
+    times = {};
     PrepCheck K{"pep_batch_screen"};
     const int rc = screen_check(K, n_genes, gene_off, col3, locus, n_loci);
     if (rc != PEP_OK) return pep_fail(ctx, rc, K.msg);
@@ -473,8 +473,7 @@ int pep_batch_screen(pep_ctx *ctx, uint32_t n_genes, const uint64_t *gene_off, c
     PEP_TRY(pep_tables_to_device(ctx, W, {{K26_A_GENE_OFF, gene_off, ((size_t)n_genes + 1) * 8, 0}, {K26_C3, col3, n_rows * 8, 8}, {K26_LOCUS, locus, n_rows * 8, 8},
                                           {K26_USED, used_state, n_loci, 8}, {K26_A_OUT3, nullptr, n_rows * 8, 8}, {K26_A_OUT4, nullptr, n_rows * 8, 8},
                                           {K26_A_PRESENT, nullptr, (size_t)n_genes * 8, 0}, {K26_A_EXCLUDED, nullptr, n_genes, 0}}));
-    double ms_kernel = 0.;
-    pep_timed_stage(ctx, ms_kernel, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(prep_screen, dim3(n_genes), dim3(PREP_BLOCK), 0, ctx->stream, W[K26_A_GENE_OFF].as<const uint64_t>(), W[K26_C3].as<const int64_t>(),
                            W[K26_LOCUS].as<const int64_t>(), W[K26_USED].as<const uint8_t>(), threshold, W[K26_A_OUT3].as<int64_t>(), W[K26_A_OUT4].as<int64_t>(),
                            W[K26_A_PRESENT].as<int64_t>(), W[K26_A_EXCLUDED].as<uint8_t>());
@@ -486,7 +485,6 @@ int pep_batch_screen(pep_ctx *ctx, uint32_t n_genes, const uint64_t *gene_off, c
     PEP_TRY(pep_d2h_queue(ctx, excluded, W[K26_A_EXCLUDED].p, n_genes));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    if (ms) ms[0] = ms_kernel;
     return PEP_OK;
 }
 
@@ -535,10 +533,11 @@ int pep_batch_prune_check(uint32_t mode, uint32_t n_genes, const uint64_t *gene_
 
 int pep_batch_prune(pep_ctx *ctx, uint32_t mode, uint32_t n_genes, const uint64_t *gene_off, const int64_t *genome, const int64_t *col2, const int64_t *col3,
                     const int64_t *col4, const int64_t *locus, const uint64_t *cfl_off, const int64_t *cfl, uint64_t n_loci, double clust_identity, double final_threshold,
-                    uint32_t path, uint64_t *out_off, int32_t *rows, uint8_t *inparalog, uint8_t *is_final, uint64_t *n_ties, double *ms)
+                    uint32_t path, uint64_t *out_off, int32_t *rows, uint8_t *inparalog, uint8_t *is_final, uint64_t *n_ties)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_BATCH_PRUNE];
+    times = {};
     PrepCheck K{"pep_batch_prune"};
     const int rc = prune_check(K, mode, n_genes, gene_off, genome, col2, col3, col4, locus, cfl_off, cfl, n_loci, path);
     if (rc != PEP_OK) return pep_fail(ctx, rc, K.msg);
@@ -574,8 +573,7 @@ int pep_batch_prune(pep_ctx *ctx, uint32_t mode, uint32_t n_genes, const uint64_
                     W[K26_SCRATCH].as<uint32_t>(), W[K26_ROWS].as<uint32_t>(), W[K26_OUT].as<PrepOut>(), clust_identity, final_threshold, mode};
     const PrepGene *d_genes = W[K26_GENES].as<const PrepGene>();
     const uint32_t *d_which = W[K26_WHICH].as<const uint32_t>();
-    double ms_kernel = 0.;
-    pep_timed_stage(ctx, ms_kernel, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         if (n_lds) hipLaunchKernelGGL(prep_prune<true>, dim3((unsigned)n_lds), dim3(PREP_BLOCK), 0, ctx->stream, d_genes, d_which, D);
         if (!large.empty()) hipLaunchKernelGGL(prep_prune<false>, dim3((unsigned)large.size()), dim3(PREP_BLOCK), 0, ctx->stream, d_genes, d_which + n_lds, D);
     });
@@ -595,7 +593,6 @@ int pep_batch_prune(pep_ctx *ctx, uint32_t mode, uint32_t n_genes, const uint64_
         is_final[g] = (uint8_t)o.is_final;
         *n_ties += o.tie;
     }
-    if (ms) ms[0] = ms_kernel;
     return PEP_OK;
 }
 

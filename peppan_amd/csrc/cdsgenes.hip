@@ -1,7 +1,7 @@
 // K23: the per-gene work of the GFF front end - iter_readGFF (PEPPAN.py:117-182), checkPseu (:992-1010), addGenes (:1013-1021).  The reference cuts every CDS
 // out of its contig, reverse-complements it character by character (rc), translates it with marked starts (transeq: numpy arrays per character, then a
 // string), looks at the first, the last and the inner characters of the translation, and hashes what it keeps - one Python round per gene.  Restated
-// (include/peppan_hip_cds.h): a CDS is one window of a contig and a strand bit; its verdict is a function of its length, of whether codon 0 is M, codon n - 1 is
+// (include/peppan_hip.h, K23): a CDS is one window of a contig and a strand bit; its verdict is a function of its length, of whether codon 0 is M, codon n - 1 is
 // X and any codon before the last is X; its digest is SHA-1 of the window as read.
 //   cds_verdict   one wavefront per CDS.  Codes 1 and 2 come from the length alone.  Else chunks of 64 codons = 192 nucleotides as in K19 (codonclass.h): lane l
 //                 reads the three characters of codon 64 c + l - forward, or backward and complemented -, a position at or behind the window's end reads as
@@ -15,7 +15,6 @@
 #include "common.h"
 #include "codonclass.h"
 #include "sha1.h"
-#include "../../include/peppan_hip_cds.h"
 #include <cstring>
 
 namespace {
@@ -127,10 +126,11 @@ int pep_cds_genes_check(const uint64_t *contig_off, uint32_t n_contigs, uint32_t
 }
 
 int pep_cds_genes(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_cds, const uint32_t *contig, const uint64_t *win_off,
-                  const uint32_t *win_len, const uint8_t *strand, uint32_t min_cds, uint32_t mask, int table4, uint8_t *code, uint8_t *digest, double *ms)
+                  const uint32_t *win_len, const uint8_t *strand, uint32_t min_cds, uint32_t mask, int table4, uint8_t *code, uint8_t *digest)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_CDS_GENES];
+    times = {};
     if (n_cds && (!code || !digest)) return pep_fail(ctx, PEP_ERR_ARG, std::string(K23_ME) + "null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<CdsItem> items;
@@ -144,12 +144,11 @@ int pep_cds_genes(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, u
     hipStream_t st = ctx->stream;
     PEP_TRY(pep_tables_to_device(ctx, W, {{K23_NT, nt, n_nt, 16}, {K23_ITEM, items.data(), (size_t)n_cds * sizeof(CdsItem), 0}, {K23_CODE, nullptr, n_cds, 0},
                                           {K23_DIGEST, nullptr, (size_t)n_cds * 20, 0}}));
-    double t_verdict = 0., t_digest = 0.;
-    pep_timed_stage(ctx, t_verdict, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(cds_verdict, dim3((unsigned)ceil_div(n_cds, 4)), dim3(256), 0, st, W[K23_NT].as<const uint8_t>(), W[K23_ITEM].as<const CdsItem>(), n_cds, min_cds,
                            mask, table4 ? GS_STOPS_TABLE4 : GS_STOPS, W[K23_CODE].as<uint8_t>());
     });
-    pep_timed_stage(ctx, t_digest, [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(cds_digest, dim3((unsigned)ceil_div(n_cds, 256)), dim3(256), 0, st, W[K23_NT].as<const uint8_t>(), W[K23_ITEM].as<const CdsItem>(), n_cds,
                            W[K23_CODE].as<const uint8_t>(), W[K23_DIGEST].as<uint32_t>());
     });
@@ -170,7 +169,6 @@ int pep_cds_genes(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, u
             d[4 * k] = (uint8_t)(v >> 24); d[4 * k + 1] = (uint8_t)(v >> 16); d[4 * k + 2] = (uint8_t)(v >> 8); d[4 * k + 3] = (uint8_t)v;
         }
     }
-    if (ms) { ms[0] = t_verdict; ms[1] = t_digest; }
     return PEP_OK;
 }
 

@@ -314,7 +314,7 @@ struct pep_ctx {
                                             // zero_ok flag still set the next search needs no fill
     DevBuf d_mail_copy;                     // the alignment stage's counter block outside d_zero (trace.hip: emit -> pack_out, K10)
     bool zero_ok[4] = {false, false, false, false};     // which consumer regions of d_zero are still untouched since that fill (PEP_ZC_*)
-    CallTimes calls[PEP_CALL_COUNT] = {};   // pep_call_times: the times and byte counts of the newest call of each of K15 - K20 (the slots: each kernel's section of peppan_hip.h)
+    CallTimes calls[PEP_CALL_COUNT] = {};   // pep_call_times: the times and byte counts of the newest call of each of K15 - K26 (the slots: each kernel's section of peppan_hip.h)
     uint64_t k16_serial = 0;                 // counts pep_group_verdicts calls: a pep_verdict_result is live while its serial is the newest
     DevBuf k16_tri, k16_leader;              // grow-only: packed triangles and leaders of the newest pep_group_verdicts (read by pep_verdict_detail_copy)
     DevBuf k17[11];                          // grow-only, pep_gene_ingroups: its tables, work list and outputs (the slots: ingroup.hip)

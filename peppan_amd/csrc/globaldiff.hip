@@ -13,12 +13,11 @@
 //                        accumulators, the leaf sums folded along numpy's tree (as numpy_sum of similar.hip does for K14)
 //       gd_fold          one thread per key: its buffer sums left to right from 0.0, then the division
 //                        ... and both again with m for the squared deviations: a key of 10^8 values is as parallel as a million keys of 1000.
-// The definition, operation by operation, is in include/peppan_hip_gdiff.h and restated in numpy by tests/globaldiff_helpers.py; the device equals it bit
+// The definition, operation by operation, is in include/peppan_hip.h (K22) and restated in numpy by tests/globaldiff_helpers.py; the device equals it bit
 // for bit, so contraction into fused multiply-adds is switched off for the whole file.  The logarithm is a table the host makes with numpy (the device K16
 // uses for its exp).  Not tuned: the rates are in profiles/globaldiff_rate.txt.  Known slack: every item finds its event by a binary search of its own, in
 // both passes; the leaves of a buffer are listed and folded by one lane.
 #include "common.h"
-#include "../../include/peppan_hip_gdiff.h"
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -423,10 +422,11 @@ int pep_global_diff_check(const int64_t *events, uint64_t n_events, const int32_
 }
 
 int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, const int32_t *arena, uint64_t arena_len, uint32_t n_genomes,
-                    const double *table, uint64_t chunk_items, uint64_t *n_keys_out, double *ms)
+                    const double *table, uint64_t chunk_items, uint64_t *n_keys_out)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_GLOBAL_DIFF];
+    times = {};
     ctx->k22_n_keys = 0;
     if (!n_keys_out) return pep_fail(ctx, PEP_ERR_ARG, std::string(K22_ME) + "null table");
     *n_keys_out = 0;
@@ -452,12 +452,11 @@ int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, cons
     uint64_t *d_cnt = B[K22_CNT].as<uint64_t>(), *d_minseq = B[K22_MINSEQ].as<uint64_t>(), *d_off = B[K22_OFF].as<uint64_t>(), *d_next = B[K22_NEXT].as<uint64_t>();
     uint32_t *d_flag = B[K22_SLOT].as<uint32_t>(), *d_slot = d_flag + (T + 1);
     const unsigned key_blocks = (unsigned)ceil_div(T, GD_BLOCK);
-    double ms_count = 0., ms_chunks = 0., ms_sums = 0.;
     int stage_rc = PEP_OK;
     // ---- counts, offsets, the keys in use
     PEP_HIP(ctx, hipMemsetAsync(d_cnt, 0, T * 8, ctx->stream));
     PEP_HIP(ctx, hipMemsetAsync(d_minseq, 0xFF, T * 8, ctx->stream));
-    pep_timed_stage(ctx, ms_count, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(gd_count, dim3((unsigned)ceil_div(total, GD_BLOCK)), dim3(GD_BLOCK), 0, ctx->stream, A, total, reinterpret_cast<unsigned long long *>(d_cnt),
                            reinterpret_cast<unsigned long long *>(d_minseq));
         stage_rc = pep_scan_u64(ctx, d_cnt, d_off, T, B[K22_SCAN_TMP]);
@@ -486,7 +485,7 @@ int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, cons
     uint64_t *d_words = B[K22_SORT].as<uint64_t>(), *d_tmp = d_words + chunk, *d_dst_base = d_cnt;
     uint16_t *d_codes = B[K22_CODES].as<uint16_t>();
     const int kbits = bit_length(T);                        // (T itself is a key: the one of the items that do not exist)
-    pep_timed_stage(ctx, ms_chunks, [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         for (uint64_t s0 = 0; s0 < total && stage_rc == PEP_OK; s0 += chunk) {
             const uint32_t n = (uint32_t)std::min(chunk, total - s0);
             const uint64_t e0 = (uint64_t)(std::upper_bound(P.base.begin(), P.base.end(), s0) - P.base.begin()) - 1;
@@ -508,7 +507,7 @@ int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, cons
     // ---- the two means
     PEP_TRY(dev_reserve(ctx, B[K22_BSUM], n_buf * 8));
     double *d_bsum = B[K22_BSUM].as<double>(), *d_mean = B[K22_OUT].as<double>(), *d_var = d_mean + n_keys;
-    pep_timed_stage(ctx, ms_sums, [&] {
+    pep_timed_stage(ctx, times.ms[2], [&] {
         for (int pass = 0; pass < 2; ++pass) {
             hipLaunchKernelGGL(gd_bufsum, dim3((unsigned)n_buf), dim3(64), 0, ctx->stream, (const GdKey *)d_rec, (const uint64_t *)d_buf_off, (uint64_t)n_keys,
                                (const uint16_t *)d_codes, (const double *)d_table, pass ? (const double *)d_mean : (const double *)nullptr, d_bsum);
@@ -520,7 +519,6 @@ int pep_global_diff(pep_ctx *ctx, const int64_t *events, uint64_t n_events, cons
     PEP_HIP(ctx, pep_stream_wait(ctx));
     ctx->k22_n_keys = n_keys;
     *n_keys_out = n_keys;
-    if (ms) { ms[0] = ms_count; ms[1] = ms_chunks; ms[2] = ms_sums; }
     return PEP_OK;
 }
 

@@ -12,11 +12,10 @@
 //                    nj_chain_argmin (up to 256 workgroups leave one partial result each) and nj_chain_update (every workgroup reduces the partial
 //                    results for itself, then updates its share of row a).  The end of a launch is the only thing one workgroup ever knows of another:
 //                    no grid-wide barrier, no cooperative launch, no ticket, no loop that waits.
-// The arithmetic is stated in include/peppan_hip_tree.h and restated in numpy by tests/njtree_helpers.py; the device equals it bit for bit, so every
+// The arithmetic is stated in include/peppan_hip.h (K21) and restated in numpy by tests/njtree_helpers.py; the device equals it bit for bit, so every
 // double operation here is one correctly rounded operation: contraction into fused multiply-adds is switched off for the whole file.
 // Not tuned: the rates are in profiles/njtree_rate.txt.  Known slack: a workgroup of 256 threads for a tree of 5 leaves; the row sums are one thread per row.
 #include "common.h"
-#include "../../include/peppan_hip_tree.h"
 #include "allelediff_tile.h"
 #include "grouptable.h"
 #include <algorithm>
@@ -317,10 +316,11 @@ int nj_check(const uint32_t *n_leaves, uint32_t n_trees, const uint64_t *dist_of
 extern "C" {
 
 int pep_kimura_pairs(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_row_off, const uint32_t *h_row_len, uint64_t n_rows, uint32_t n_groups,
-                     const uint64_t *h_grp_off, const uint32_t *h_grp_rows, int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap, double *ms)
+                     const uint64_t *h_grp_off, const uint32_t *h_grp_rows, int32_t *h_out, const uint64_t *h_out_off, uint64_t out_cap)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_KIMURA_PAIRS];
+    times = {};
     if (!h_row_off || (n_rows && !h_row_len) || (n_groups && (!h_grp_off || !h_out_off)) || (out_cap && !h_out))
         return pep_fail(ctx, PEP_ERR_ARG, std::string(K21_PAIRS_ME) + "null table");
     if (n_groups && h_grp_off[n_groups] && !h_grp_rows) return pep_fail(ctx, PEP_ERR_ARG, std::string(K21_PAIRS_ME) + "null table");
@@ -356,9 +356,8 @@ int pep_kimura_pairs(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_ro
         return PEP_OK;
     }
     DevBuf *W = ctx->ws;
-    double ms_planes = 0., ms_pairs = 0.;
-    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 12, 0}}, ms_planes));
-    pep_timed_stage(ctx, ms_pairs, [&] {
+    PEP_TRY(group_tables_to_device(ctx, T, L, L.groups.data(), (size_t)n_groups * sizeof(GroupRec), {{K15_WS_OUT, nullptr, (L.pairs + 1) * 12, 0}}, times.ms[0]));
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(kimura_pairs, dim3((unsigned)L.tiles.size()), dim3(256), 0, ctx->stream, W[K15_WS_TILES].as<const DiffTile>(), W[K15_WS_GROUPS].as<const GroupRec>(),
                            W[K15_WS_GRP_ROWS].as<const uint32_t>(), W[K15_WS_PLANE_OFF].as<const uint64_t>(), W[K15_WS_PLANES].as<const unsigned long long>(), W[K15_WS_OUT].as<int32_t>());
     });
@@ -378,7 +377,6 @@ int pep_kimura_pairs(pep_ctx *ctx, const uint8_t *h_packed, const uint64_t *h_ro
     }
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    if (ms) { ms[0] = ms_planes; ms[1] = ms_pairs; }
     return PEP_OK;
 }
 
@@ -390,10 +388,11 @@ int pep_nj_trees_check(const uint32_t *n_leaves, uint32_t n_trees, const uint64_
 }
 
 int pep_nj_trees(pep_ctx *ctx, const double *h_dist, const uint64_t *h_dist_off, const uint32_t *h_n, uint32_t n_trees, uint32_t *h_node, double *h_len,
-                 const uint64_t *h_out_off, double *ms)
+                 const uint64_t *h_out_off)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_NJ_TREES];
+    times = {};
     std::string msg;
     const int rc = nj_check(h_n, n_trees, h_dist_off, h_out_off, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
@@ -427,14 +426,13 @@ int pep_nj_trees(pep_ctx *ctx, const double *h_dist, const uint64_t *h_dist_off,
                                           {K21_NODE, nullptr, n_out * 4, 0}, {K21_LEN, nullptr, n_out * 8, 0}}));
     PEP_HIP(ctx, hipMemsetAsync(B[K21_NODE].p, 0, n_out * 4, ctx->stream));          // (the entries between two trees)
     PEP_HIP(ctx, hipMemsetAsync(B[K21_LEN].p, 0, n_out * 8, ctx->stream));
-    double ms_block = 0., ms_chain = 0.;
     double *d_dist = B[K21_DIST].as<double>();
     uint32_t *d_node = B[K21_NODE].as<uint32_t>();
     double *d_len = B[K21_LEN].as<double>();
     const NjTree *d_trees = B[K21_TREES].as<const NjTree>();
     const uint32_t *d_which = B[K21_STATE].as<const uint32_t>();
     if (!which.empty())
-        pep_timed_stage(ctx, ms_block, [&] {
+        pep_timed_stage(ctx, times.ms[0], [&] {
             size_t first = 0;
             if (!cls[0].empty()) hipLaunchKernelGGL(nj_block<NJ_LDS_SMALL>, dim3((unsigned)cls[0].size()), dim3(NJ_BLOCK), 0, ctx->stream, d_trees, d_which + first, d_dist, d_node, d_len);
             first += cls[0].size();
@@ -452,7 +450,7 @@ int pep_nj_trees(pep_ctx *ctx, const double *h_dist, const uint64_t *h_dist_off,
         C.live0 = C.pkey + NJ_CHAIN_PARTS;
         C.live1 = C.live0 + chain_max;
         C.node = C.live1 + chain_max;
-        pep_timed_stage(ctx, ms_chain, [&] {
+        pep_timed_stage(ctx, times.ms[1], [&] {
             for (uint32_t t : chain) {
                 const uint32_t n = h_n[t];
                 C.D = d_dist + trees[t].dist_off;
@@ -476,7 +474,6 @@ int pep_nj_trees(pep_ctx *ctx, const double *h_dist, const uint64_t *h_dist_off,
     PEP_TRY(pep_d2h_queue(ctx, h_len + out0, d_len, n_out * 8));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    if (ms) { ms[0] = ms_block; ms[1] = ms_chain; }
     return PEP_OK;
 }
 

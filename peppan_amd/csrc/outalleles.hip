@@ -1,6 +1,6 @@
 // K24: the allele pass of write_output (PEPPAN.py:1391-1472).  For every prediction the reference cuts the predicted region out of its contig, reverse-complements
 // it character by character on '-', uses the string as a dictionary key to number the alleles of its gene, and works out the window determineGeneStructure
-// (K19) is to look at - one Python round per prediction.  Restated (include/peppan_hip_outalleles.h): the window and the allele span are integer functions of a
+// (K19) is to look at - one Python round per prediction.  Restated (include/peppan_hip.h, K24): the window and the allele span are integer functions of a
 // row and of at most five neighbours; an allele's number is the rank of its class's first row among the first rows of its gene, its 't' that row's property.
 //   oa_plan      one thread per row: class, neighbour walk, s2 e2 lp, the allele span -> the plan record and the item (arena position, length, gene, strand).
 //                oa_plan_row is the one statement of those rules: the host check runs the same function over every row before anything is launched.
@@ -16,7 +16,6 @@
 // the comparison.  DESIGN.md 4.10k.
 #include "common.h"
 #include "sha1.h"
-#include "../../include/peppan_hip_outalleles.h"
 #include <algorithm>
 #include <cstring>
 
@@ -318,10 +317,11 @@ int pep_out_alleles_check(const uint64_t *contig_off, uint32_t n_contigs, uint32
 }
 
 int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off, uint32_t n_contigs, uint32_t n_genes, const int32_t *seed_contig, uint32_t n_rows,
-                    const int32_t *rows, const int32_t *look9, int plan_only, uint32_t key_bits, int32_t *plan, int32_t *first, uint32_t *rank, uint8_t *tflag, double *ms)
+                    const int32_t *rows, const int32_t *look9, int plan_only, uint32_t key_bits, int32_t *plan, int32_t *first, uint32_t *rank, uint8_t *tflag)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) std::fill(ms, ms + 6, 0.);
+    CallTimes &times = ctx->calls[PEP_CALL_OUT_ALLELES];
+    times = {};
     if (n_rows && (!plan || (!plan_only && (!first || !rank || !tflag)))) return pep_fail(ctx, PEP_ERR_ARG, std::string(K24_ME) + "null table");
     PEP_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<OaItem> seeds;
@@ -336,13 +336,12 @@ int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off,
     const uint32_t n_seeds = (uint32_t)seeds.size(), n_items = n_seeds + n_rows;
     const size_t row_bytes = (size_t)n_rows * PEP_OUTA_COLS * 4, plan_bytes = (size_t)n_rows * PEP_OUTA_PLAN_COLS * 4;
     const unsigned row_blocks = (unsigned)ceil_div(n_rows, OA_BLOCK), item_blocks = (unsigned)ceil_div(n_items, OA_BLOCK);
-    double t[6] = {0., 0., 0., 0., 0., 0.};
     std::vector<int32_t> h_plan((size_t)n_rows * PEP_OUTA_PLAN_COLS);
 
     if (plan_only) {
         PEP_TRY(pep_tables_to_device(ctx, W, {{K24_OFF, contig_off, ((size_t)n_contigs + 1) * 8, 0}, {K24_ROWS, rows, row_bytes, 0},
                                               {K24_LOOK, look9, look9 ? (size_t)n_rows * 4 : 0, 4}, {K24_PLAN, nullptr, plan_bytes, 0}}));
-        pep_timed_stage(ctx, t[0], [&] {
+        pep_timed_stage(ctx, times.ms[0], [&] {
             hipLaunchKernelGGL(oa_plan, dim3(row_blocks), dim3(OA_BLOCK), 0, st, W[K24_ROWS].as<const int32_t>(), look9 ? W[K24_LOOK].as<const int32_t>() : nullptr, n_rows,
                                W[K24_OFF].as<const uint64_t>(), W[K24_PLAN].as<int32_t>(), (OaItem *)nullptr, (uint8_t *)nullptr);
         });
@@ -351,7 +350,6 @@ int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off,
         PEP_HIP(ctx, pep_stream_wait(ctx));
         pep_d2h_finish(ctx);
         memcpy(plan, h_plan.data(), plan_bytes);
-        if (ms) ms[0] = t[0];
         return PEP_OK;
     }
 
@@ -373,26 +371,26 @@ int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off,
     PEP_HIP(ctx, hipMemsetAsync(d_tflag, 0, n_seeds ? n_seeds : 1, st));                             // a seed's id is '1': no 't'
     PEP_HIP(ctx, hipMemsetAsync(d_table, 0xFF, (size_t)slots * 4, st));
     PEP_HIP(ctx, hipMemsetAsync(W[K24_BAD].p, 0xFF, 4, st));
-    pep_timed_stage(ctx, t[0], [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(oa_plan, dim3(row_blocks), dim3(OA_BLOCK), 0, st, W[K24_ROWS].as<const int32_t>(), look9 ? W[K24_LOOK].as<const int32_t>() : nullptr, n_rows,
                            W[K24_OFF].as<const uint64_t>(), W[K24_PLAN].as<int32_t>(), d_items + n_seeds, d_tflag + n_seeds);
     });
-    pep_timed_stage(ctx, t[1], [&] {
+    pep_timed_stage(ctx, times.ms[1], [&] {
         hipLaunchKernelGGL(oa_digest, dim3(item_blocks), dim3(OA_BLOCK), 0, st, W[K24_NT].as<const uint8_t>(), (const OaItem *)d_items, n_items, d_digest);
     });
-    pep_timed_stage(ctx, t[2], [&] {
+    pep_timed_stage(ctx, times.ms[2], [&] {
         hipLaunchKernelGGL(oa_classes, dim3(item_blocks), dim3(OA_BLOCK), 0, st, (const OaItem *)d_items, (const uint32_t *)d_digest, n_items,
                            key_bits ? (1u << key_bits) - 1u : 0u, d_table, slots - 1u, d_slot);
     });
-    pep_timed_stage(ctx, t[3], [&] {
+    pep_timed_stage(ctx, times.ms[3], [&] {
         hipLaunchKernelGGL(oa_verify, dim3(item_blocks), dim3(OA_BLOCK), 0, st, W[K24_NT].as<const uint8_t>(), (const OaItem *)d_items, (const uint32_t *)d_table,
                            (const uint32_t *)d_slot, n_items, n_genes, item_bits, d_first, d_keys, W[K24_BAD].as<uint32_t>());
     });
     PEP_HIP(ctx, hipGetLastError());
     int sort_rc = PEP_OK;
-    pep_timed_stage(ctx, t[4], [&] { sort_rc = pep_sort_u64(ctx, d_keys, W[K24_KEYS_TMP].as<uint64_t>(), nullptr, n_items, item_bits + gene_bits, nullptr, nullptr); });
+    pep_timed_stage(ctx, times.ms[4], [&] { sort_rc = pep_sort_u64(ctx, d_keys, W[K24_KEYS_TMP].as<uint64_t>(), nullptr, n_items, item_bits + gene_bits, nullptr, nullptr); });
     PEP_TRY(sort_rc);
-    pep_timed_stage(ctx, t[5], [&] {
+    pep_timed_stage(ctx, times.ms[5], [&] {
         hipLaunchKernelGGL(oa_starts, dim3(item_blocks), dim3(OA_BLOCK), 0, st, (const uint64_t *)d_keys, n_items, n_genes, item_bits, W[K24_START].as<uint32_t>());
         hipLaunchKernelGGL(oa_ranks, dim3(item_blocks), dim3(OA_BLOCK), 0, st, (const uint64_t *)d_keys, n_items, n_genes, item_bits, W[K24_START].as<const uint32_t>(),
                            W[K24_RANKF].as<uint32_t>());
@@ -413,6 +411,7 @@ int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off,
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
     if (offender != OA_NONE) {
+        times = {};                      // (nothing was merged: the refused call reports no times)
         const auto name = [&](int64_t item) { return item < n_seeds ? std::string("the seed of its gene") : "row " + std::to_string(item - n_seeds); };
         const int32_t f = offender >= n_seeds ? h_first[offender - n_seeds] : -1;
         return pep_fail(ctx, PEP_ERR_ALLELE_CLASS, K24_ME + name(offender) + " and " + name(f < 0 ? -1 : (int64_t)f + n_seeds) +
@@ -422,7 +421,6 @@ int pep_out_alleles(pep_ctx *ctx, const uint8_t *nt, const uint64_t *contig_off,
     memcpy(first, h_first.data(), (size_t)n_rows * 4);
     memcpy(rank, h_rank.data(), (size_t)n_rows * 4);
     memcpy(tflag, h_t.data(), n_rows);
-    if (ms) std::copy(t, t + 6, ms);
     return PEP_OK;
 }
 

@@ -1,6 +1,6 @@
 // K25: the tree cutting of filt_per_group (PEPPAN.py:424-482, ete3 there) for a batch of trees, on bit sets of leaves: no tree is rooted, pruned or walked.
 // The definition, the summation order and what is NOT restated (the reference's choice at exact ties between different bipartitions, which depends on ete3's
-// rooting) are in include/peppan_hip_treecut.h; tests/treecut_helpers.py restates it in numpy and the device equals that bit for bit, so contraction into fused
+// rooting) are in include/peppan_hip.h (K25); tests/treecut_helpers.py restates it in numpy and the device equals that bit for bit, so contraction into fused
 // multiply-adds is switched off for the whole file.
 //   cut_prep         a wavefront per matrix row of the batch: the row of M = W1 where W0 > W1, and the row's bits of G = (W0 > W1) by ballot (the test of :438
 //                    is then `G[a] & T` over the rows a of T).
@@ -15,7 +15,6 @@
 // Not tuned: the rates are in profiles/treecut_rate.txt.  Known slack: a workgroup of 256 threads and 24 KiB of LDS for a tree of 3 leaves; a branch is scored
 // by one wavefront however many rows its far side has; branches with the same restriction are scored once each.
 #include "common.h"
-#include "../../include/peppan_hip_treecut.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -512,10 +511,11 @@ int pep_tree_cut_check(const uint32_t *n_leaves, uint32_t n_trees, const uint64_
 
 int pep_tree_cut(pep_ctx *ctx, const uint32_t *h_n, uint32_t n_trees, const uint64_t *h_leaf_off, const uint64_t *h_mat_off, const uint64_t *h_branch_off,
                  const uint64_t *h_set_off, const uint64_t *h_sets, const double *h_len, const double *h_w0, const double *h_w1, const uint8_t *h_strong,
-                 const uint32_t *h_cap, uint32_t path, int32_t *h_part, int32_t *h_counts, int32_t *h_log_i, double *h_log_v, double *ms)
+                 const uint32_t *h_cap, uint32_t path, int32_t *h_part, int32_t *h_counts, int32_t *h_log_i, double *h_log_v)
 {
     if (!ctx) return PEP_ERR_ARG;
-    if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.;
+    CallTimes &times = ctx->calls[PEP_CALL_TREE_CUT];
+    times = {};
     std::string msg;
     const int rc = cut_check(h_n, n_trees, h_leaf_off, h_mat_off, h_branch_off, h_set_off, h_sets, path, msg);
     if (rc != PEP_OK) return pep_fail(ctx, rc, msg);
@@ -570,8 +570,7 @@ int pep_tree_cut(pep_ctx *ctx, const uint32_t *h_n, uint32_t n_trees, const uint
              W[K25_STRONG].as<const uint64_t>(), W[K25_LEN].as<const double>(), W[K25_SCORE].as<double>(), W[K25_FIN].as<uint32_t>(), W[K25_PART].as<int32_t>(),
              W[K25_COUNTS].as<int32_t>(), W[K25_LOGI].as<int32_t>(), W[K25_LOGV].as<double>()};
     const CutTree *d_trees = W[K25_TREES].as<const CutTree>();
-    double ms_block = 0., ms_chain = 0.;
-    pep_timed_stage(ctx, ms_block, [&] {
+    pep_timed_stage(ctx, times.ms[0], [&] {
         hipLaunchKernelGGL(cut_prep, dim3((unsigned)ceil_div(rows, CUT_WAVES)), dim3(CUT_BLOCK), 0, ctx->stream, d_trees, n_trees, rows, D);
         if (!block.empty()) hipLaunchKernelGGL(cut_block, dim3((unsigned)block.size()), dim3(CUT_BLOCK), 0, ctx->stream, d_trees, W[K25_STATE].as<const uint32_t>(), D);
     });
@@ -579,7 +578,7 @@ int pep_tree_cut(pep_ctx *ctx, const uint32_t *h_n, uint32_t n_trees, const uint
     if (!chain.empty()) {
         uint8_t *st = W[K25_STATE].as<uint8_t>() + which_bytes;
         int failed = PEP_OK;
-        pep_timed_stage(ctx, ms_chain, [&] {
+        pep_timed_stage(ctx, times.ms[1], [&] {
             for (uint32_t t : chain) {
                 const CutTree &R = trees[t];
                 CutView V{D.W0 + R.mat_off, D.W1 + R.mat_off, D.M + R.mat_off, D.G + R.g_off, D.sets + R.set_off, D.strong + R.word_off, D.len + R.branch_off,
@@ -610,7 +609,6 @@ int pep_tree_cut(pep_ctx *ctx, const uint32_t *h_n, uint32_t n_trees, const uint
     PEP_TRY(pep_d2h_queue(ctx, h_log_v + 4 * leaf0, D.log_v, n_leaf * 32));
     PEP_HIP(ctx, pep_stream_wait(ctx));
     pep_d2h_finish(ctx);
-    if (ms) { ms[0] = ms_block; ms[1] = ms_chain; }
     return PEP_OK;
 }
 

@@ -7,7 +7,7 @@
 
 The reference cuts every CDS out of its contig, reverse-complements it character by character, translates it through numpy arrays per character and
 hashes it, one Python round per gene (1.5 s per genome).  Here the host reads the lines and resolves the names; K23 (csrc/cdsgenes.hip,
-Context.cds_genes, include/peppan_hip_cds.h) judges every window and digests the kept ones straight from the contig bytes, all files of a batch in one
+Context.cds_genes, include/peppan_hip.h) judges every window and digests the kept ones straight from the contig bytes, all files of a batch in one
 call; the texts of the kept genes are slices of the contigs made here.  There is no CPU fallback: a missing library or GPU raises PepError.  The context is
 orthofilter's cached one (one per process and device; close() releases it).
 

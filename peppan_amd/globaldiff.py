@@ -5,7 +5,7 @@
     pair_statistics         the device call on its own, for callers that bring their own events
     log_table               the logarithm of every value code, made by numpy as the reference makes it
 
-The function is cut as include/peppan_hip_gdiff.h describes.  The group selection (:1612-1629) stays Python as the reference writes it - a few thousand
+The function is cut as include/peppan_hip.h describes.  The group selection (:1612-1629) stays Python as the reference writes it - a few thousand
 groups, and sha1(bytes(g)) of a numpy integer is what it is.  The dictionary walk over the selected rows (:1632-1659 without its inner loops) is host
 C++ (N.global_diff_walk): it only decides which two member lists meet at each row.  The cross product of those lists, grouped by genome pair, and numpy's
 two means per pair are K22 (csrc/globaldiff.hip, Context.global_diff), bit for bit.  The tail (:1663-1665) is numpy exactly as written.  There is no CPU

@@ -7,7 +7,7 @@
     gene_trees          PEPPAN.py:393-417 for a whole `to_run` list: the tree text of every group filt_per_group would build a tree for
     (panparser.writeCGAV writes <prefix>_CGAV.nwk through nj_trees and newick when rapidnj is not installed)
 
-K21 (csrc/njtree.hip, include/peppan_hip_tree.h) does the integer and the quadratic part: Context.kimura_pairs counts per pair of rows the comparable
+K21 (csrc/njtree.hip, include/peppan_hip.h) does the integer and the quadratic part: Context.kimura_pairs counts per pair of rows the comparable
 columns, the transitions and the transversions over K15's bit planes, Context.nj_trees joins every matrix of a batch - one workgroup per tree up to
 PEP_NJ_BLOCK_LEAVES leaves, a chain of launches per tree beyond.  Its arithmetic is stated in the header, in float64; rapidnj computes in float32 and
 prints five significant digits, so branch lengths agree to that and topologies agree except at near-ties (profiles/njtree_vs_reference.txt).  There is
@@ -31,7 +31,7 @@ NjTree = collections.namedtuple('NjTree', 'node length n')
 
 def nj_trees(matrices, device=None):
     """one NjTree per square distance matrix (entries with row < column are read): node uint32[2 n - 3] and length float64[2 n - 3] as
-    include/peppan_hip_tree.h states them - per join the two joined node ids (leaves 0 .. n - 1, join s makes node n + s) and their branch lengths, then the
+    include/peppan_hip.h states them - per join the two joined node ids (leaves 0 .. n - 1, join s makes node n + s) and their branch lengths, then the
     last three nodes; n = 2: two entries.  An empty list is legal."""
     matrices = list(matrices)
     if not matrices:

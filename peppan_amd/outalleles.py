@@ -6,7 +6,7 @@ to look at and, in batches of 10 000 rows, writes that function's results back i
     allele_ids      the array-level call under it: plan, class first rows, ranks and 't' flags for plain arrays
     tables          the prediction table and its dictionaries as those arrays
 
-K24 (csrc/outalleles.hip, Context.out_alleles, include/peppan_hip_outalleles.h) plans every row, digests every allele in place, groups equal ones, compares
+K24 (csrc/outalleles.hip, Context.out_alleles, include/peppan_hip.h) plans every row, digests every allele in place, groups equal ones, compares
 their bytes and ranks the classes of every gene on the device; K19 (Context.gene_structure) judges the windows.  What stays here: names to indices, the
 reference's float expressions (float64, evaluated once per distinct value), one slice per DISTINCT allele for the dictionary, and the texts of columns 13 and
 15, made by the reference's own format expressions in a Python loop over the rows.
@@ -125,7 +125,7 @@ def tables(prediction, genomes, encodes, clust_ref, pseudogene):
 
 
 def allele_ids(nt, contig_off, seed_contig, rows, look9=None, key_bits=0, plan_only=False, device=None):
-    """K24 for plain arrays, as include/peppan_hip_outalleles.h states it (Context.out_alleles names the arguments)
+    """K24 for plain arrays, as include/peppan_hip.h states it (Context.out_alleles names the arguments)
     -> (plan int32[n, 6]: class, s2, e2, lp, a, len; first int32[n]: the first row of the row's class, -1 the seed, -2 a skipped row; rank uint32[n];
     tflag uint8[n]); with plan_only the plan and three None"""
     return _context(device).out_alleles(nt, contig_off, seed_contig, rows, look9=look9, plan_only=plan_only, key_bits=key_bits)
@@ -147,7 +147,7 @@ def allele_pass(prediction, genomes, encodes, clust_ref, pseudogene, gtable, dev
     """PEPPAN.py:1391-1472 on the GPU.  prediction: the 17-column object table as it stands at :1390, in that row order; it is mutated as the reference
     mutates it (columns 9, 10, 13 and 15).  -> alleles, the reference's dict of dicts gene -> {sequence: id}, both levels in its insertion order.
     A KeyError of the reference (:1461, a name without its '/n' suffix that `encodes` lacks) is raised before anything is written; a row the library
-    refuses (include/peppan_hip_outalleles.h lists them) raises PepError naming it.  timing (optional dict): receives the seconds spent in 'tables', 'k24',
+    refuses (include/peppan_hip.h lists them) raises PepError naming it.  timing (optional dict): receives the seconds spent in 'tables', 'k24',
     'k19' and 'texts'."""
     import time
     clock = [time.perf_counter()]

@@ -1,6 +1,6 @@
 """filt_genes (PEPPAN.py:525-734) on the library: what turns the gene scores of `initializing` into the pan-gene matrices of `mat_out`.
 
-    prepare_batch       :546-624 (nj / ml) and :641-656 (sbh) for one round of up to 500 genes: K26 (csrc/batchprep.hip, include/peppan_hip_batchprep.h).
+    prepare_batch       :546-624 (nj / ml) and :641-656 (sbh) for one round of up to 500 genes: K26 (csrc/batchprep.hip, include/peppan_hip.h).
                         Stage A (the screen against `used`) and stage C (the pruning of every group, the decision final / to_run) are one GPU launch each
                         over the whole round; stage B (the unsure walk, sequential over the round's genes) is one call of host C++.  The tables and the
                         members of the .conflicts store are read and laid out with numpy over whole members: no Python statement runs per row.

@@ -1,4 +1,4 @@
-"""The tree cutting of filt_per_group (PEPPAN.py:424-482) without ete3: K25 (csrc/treecut.hip, include/peppan_hip_treecut.h) at the level of arrays.
+"""The tree cutting of filt_per_group (PEPPAN.py:424-482) without ete3: K25 (csrc/treecut.hip, include/peppan_hip.h) at the level of arrays.
 
     cut_trees           a batch of trees - Newick texts or parse_newick's branches - with their `incompatible` arrays -> per tree the partition of the leaves
     branch_sets         the branches of one tree as the bit sets of leaves K25 reads

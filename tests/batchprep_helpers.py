@@ -1,5 +1,5 @@
 """What the K26 tests share: a plain-Python restatement of the front half of a round of filt_genes (PEPPAN.py:546-624, :641-656) as
-include/peppan_hip_batchprep.h defines it - lists, dicts and sets, no numpy in the arithmetic, nothing of the library -, the builders of seeded gene
+include/peppan_hip.h defines it - lists, dicts and sets, no numpy in the arithmetic, nothing of the library -, the builders of seeded gene
 tables, and the reader of the committed fixture (tests/golden/g29_batchprep.json.gz, made by tests/golden/make_golden_batchprep.py from the reference's
 own filt_genes).
 

@@ -1,4 +1,4 @@
-"""What the K22 tests share: the restatement of get_global_difference (PEPPAN.py:1611-1666) as include/peppan_hip_gdiff.h cuts it - the group selection
+"""What the K22 tests share: the restatement of get_global_difference (PEPPAN.py:1611-1666) as include/peppan_hip.h cuts it - the group selection
 as the reference writes it, the dictionary walk into events over an append-only arena, the items of an event, numpy's sum restated operation by
 operation, the host tail - and the reader of tests/golden/g22_globaldiff.json.gz (made by tests/golden/make_golden_globaldiff.py from the reference's own
 function).  Nothing here calls the library; np.mean is used nowhere, so that test_globaldiff_host.py can hold the restated sum to the recorded results."""

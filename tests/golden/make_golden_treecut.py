@@ -11,7 +11,7 @@ iter_descendants('postorder'), is_leaf, is_root, up, detach, delete(preserve_bra
 ete3 cannot be run where this project is built.
 
 PEP.filt_per_group itself (PEPPAN.py:326-484) runs on every case, TWICE: with the stand-in's midpoint rooting and rooted at an arbitrary other branch.  The
-two runs must return the same matrices - the evidence for the claim of include/peppan_hip_treecut.h that the rooting shows only at exact ties - and the
+two runs must return the same matrices - the evidence for the claim of include/peppan_hip.h that the rooting shows only at exact ties - and the
 numpy restatement of tests/treecut_helpers.py must return them too.  Only DATA is written: the case's inputs, the tree text and the rows of each returned
 matrix - none of the reference's source text.
 

@@ -1,4 +1,4 @@
-"""What the K21 tests share: the numpy restatement of the neighbour-joining rules of include/peppan_hip_tree.h, the Kimura pair counts in numpy,
+"""What the K21 tests share: the numpy restatement of the neighbour-joining rules of include/peppan_hip.h, the Kimura pair counts in numpy,
 bipartition sets of join records and of Newick texts, and the builders of the test matrices.
 
 The restatement is the definition the device is held to bit for bit: float64 throughout, every operation one numpy operation (numpy never fuses a

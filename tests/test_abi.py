@@ -17,7 +17,7 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(N.EXPORTS)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.pep_version() == N.ABI_VERSION
+    assert lib.pep_version() == N.ABI_VERSION == 20 == int(re.search(r'#define PEP_ABI_VERSION (\d+)', hdr).group(1))
 
 
 SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64, 'double': C.c_double}
@@ -45,7 +45,7 @@ def test_signature_table_is_the_header():
     """peppan_amd._native.SIGNATURES states the return and parameter types of every prototype of include/peppan_hip.h, and load_library() has given them to ctypes"""
     from peppan_amd import _native as N
     protos = _header_prototypes()
-    assert len(protos) == 93 and sum(len(params) for _, _, params in protos) == 618          # (a prototype the pattern misses shows here)
+    assert len(protos) == 115 and sum(len(params) for _, _, params in protos) == 835          # (a prototype the pattern misses shows here)
     assert {name for _, name, _ in protos} == set(N.SIGNATURES) == set(N.EXPORTS) and len(N.EXPORTS) == len(protos)
     lib = N.load_library()
     for ret, name, params in protos:
@@ -81,12 +81,14 @@ def test_direct_callers_get_the_full_return_width():
 
 HANDLE_FIRST = ['pep_rescore_nt', 'pep_rescore_codons', 'pep_components', 'pep_components_of_hits', 'pep_set_grouping', 'pep_linclust', 'pep_overlaps', 'pep_alleles',
                 'pep_sha1', 'pep_dedup', 'pep_allele_diff', 'pep_group_verdicts', 'pep_verdict_detail_size', 'pep_verdict_detail_copy', 'pep_gene_ingroups',
-                'pep_call_times', 'pep_synteny_pairs', 'pep_synteny_pairs_copy', 'pep_gene_structure', 'pep_rarefaction_curves', 'pep_profile_pairs']
+                'pep_call_times', 'pep_synteny_pairs', 'pep_synteny_pairs_copy', 'pep_gene_structure', 'pep_rarefaction_curves', 'pep_profile_pairs',
+                'pep_kimura_pairs', 'pep_nj_trees', 'pep_global_diff_walk_size', 'pep_global_diff_walk_copy', 'pep_global_diff', 'pep_global_diff_copy',
+                'pep_cds_genes', 'pep_out_alleles', 'pep_tree_cut', 'pep_batch_screen', 'pep_batch_prune']
 
 
 def test_null_handle_is_an_argument_error():
-    """every entry point of K7 and K9 - K20 that takes a pep_ctx * or a pep_verdict_result * first answers a null one with PEP_ERR_ARG, whatever else it is given: the
-    check of the handle comes before anything that would need a device"""
+    """every entry point of K7 and K9 - K26 that takes a pep_ctx *, a pep_verdict_result * or a pep_gdiff_walk * first answers a null one with PEP_ERR_ARG, whatever
+    else it is given: the check of the handle comes before anything that would need a device"""
     from peppan_amd import _native as N
     lib = N.load_library()
     for name in HANDLE_FIRST:
@@ -97,12 +99,13 @@ def test_null_handle_is_an_argument_error():
 
 def test_call_times_refuses_a_bad_selector_and_a_null_record():
     """pep_call_times answers which = -1, which = PEP_CALL_COUNT and a null out with PEP_ERR_ARG (here without a context, which alone is refused already; on a live
-    context: tests/test_gpu_ctx_resources.py); PEP_CALL_COUNT and the six selectors of the header are _native's"""
+    context: tests/test_gpu_ctx_resources.py); PEP_CALL_COUNT and the fourteen selectors of the header are _native's"""
     from peppan_amd import _native as N
     lib = N.load_library()
     hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
-    names = ('ALLELE_DIFF', 'GROUP_VERDICTS', 'GENE_INGROUPS', 'SYNTENY_PAIRS', 'GENE_STRUCTURE', 'PARSER', 'COUNT')
-    assert [int(re.search(r'#define PEP_CALL_%s (\d+)\b' % n, hdr).group(1)) for n in names] == [getattr(N, 'CALL_' + n) for n in names] == list(range(7))
+    names = ('ALLELE_DIFF', 'GROUP_VERDICTS', 'GENE_INGROUPS', 'SYNTENY_PAIRS', 'GENE_STRUCTURE', 'PARSER', 'KIMURA_PAIRS', 'NJ_TREES', 'GLOBAL_DIFF', 'CDS_GENES',
+             'OUT_ALLELES', 'TREE_CUT', 'BATCH_SCREEN', 'BATCH_PRUNE', 'COUNT')
+    assert [int(re.search(r'#define PEP_CALL_%s (\d+)\b' % n, hdr).group(1)) for n in names] == [getattr(N, 'CALL_' + n) for n in names] == list(range(15))
     out = N.CallTimes()
     for which, record in ((-1, C.byref(out)), (N.CALL_COUNT, C.byref(out)), (0, None), (0, C.byref(out))):
         assert lib.pep_call_times(None, which, record) == -2          # PEP_ERR_ARG
@@ -133,7 +136,7 @@ def test_struct_layouts_match_header(tmp_path):
     assert got['pep_hit'] == N.HIT_DTYPE.itemsize == 64 and got['pep_nt_hit'] == N.NT_HIT_DTYPE.itemsize == 40
     assert got['pep_locus'] == N.LOCUS_DTYPE.itemsize == 32 and got['pep_mat_cols'] == C.sizeof(N.MatCols)
     assert got['pep_query_meta'] == N.QUERY_META_DTYPE.itemsize == 16 and got['pep_target_meta'] == N.TARGET_META_DTYPE.itemsize == 16
-    assert got['pep_call_times'] == C.sizeof(N.CallTimes) == 48
+    assert got['pep_call_times'] == C.sizeof(N.CallTimes) == 80
     for st, f in probes:
         mirror = {'pep_search_params': N.SearchParams, 'pep_stats': N.Stats, 'pep_mat_cols': N.MatCols, 'pep_call_times': N.CallTimes}.get(st)
         if mirror is not None:

@@ -1,8 +1,8 @@
 """K26 (the front half of a round of filt_genes, PEPPAN.py:546-624 and :641-656) without a GPU: the plain-Python restatement of
 tests/batchprep_helpers.py against what the reference's own filt_genes left at :546, :579, :595 and :658 of every round of the committed fixture
 (tests/golden/g29_batchprep.json.gz, made by tests/golden/make_golden_batchprep.py), pep_batch_unsure_walk (host C++) against the restatement on the
-fixture's rounds and on seeded random rounds, every refusal of the three device-free ..._check functions, and the seventh header against
-_native.BATCHPREP_SIGNATURES.
+fixture's rounds and on seeded random rounds, every refusal of the three device-free ..._check functions, and the K26 section of the header against
+_native's constants.
 
 The tolerance is zero: tables, flags, codes and messages are compared with ==."""
 import ctypes as C
@@ -191,32 +191,22 @@ def raw_args(name, a):
 
 def test_null_context_is_an_argument_error(N):
     for name in ('pep_batch_screen', 'pep_batch_prune'):
-        restype, *argtypes = N.BATCHPREP_SIGNATURES[name]
+        restype, *argtypes = N.SIGNATURES[name]
         assert restype is C.c_int and argtypes[0] is C.c_void_p
         assert getattr(N.load_library(), name)(*[None if t is C.c_void_p else t(0) for t in argtypes]) == PEP_ERR_ARG
 
 
-def test_seventh_header_is_batchprep_signatures(N):
-    hdr_text = open(os.path.join(ROOT, 'include', 'peppan_hip_batchprep.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr_text, flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    protos = [(ret.strip(), name, [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-    assert [name for _, name, _ in protos] == list(N.BATCHPREP_SIGNATURES) == ['pep_batch_screen', 'pep_batch_screen_check', 'pep_batch_unsure_walk',
-                                                                              'pep_batch_unsure_walk_check', 'pep_batch_prune', 'pep_batch_prune_check']
-    others = (N.SIGNATURES, N.TREE_SIGNATURES, N.GDIFF_SIGNATURES, N.CDS_SIGNATURES, N.OUTALLELES_SIGNATURES, N.TREECUT_SIGNATURES)
-    assert not any(set(N.BATCHPREP_SIGNATURES) & set(t) for t in others)
-    assert N.ABI_VERSION == 19 and len(N.SIGNATURES) == 93
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.BATCHPREP_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert restype in ABI._ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in ABI._ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-    defines = dict(re.findall(r'^#define (PEP_\w+) \(?(-?\w+)(?: << (\d+))?\)?$', hdr_text, flags=re.M) and
-                   [(a, (b, c)) for a, b, c in re.findall(r'^#define (PEP_\w+) \(?(-?\w+)(?: << (\d+))?\)?$', hdr_text, flags=re.M)])
+def test_batchprep_section_of_the_header(N):
+    """the K26 section of include/peppan_hip.h declares its six functions in this order, cites what it replaces, and its modes, paths and limits are _native's (the
+    prototypes: tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
+    names = [name for _, name, _ in ABI._header_prototypes()]
+    own = ['pep_batch_screen', 'pep_batch_screen_check', 'pep_batch_unsure_walk', 'pep_batch_unsure_walk_check', 'pep_batch_prune', 'pep_batch_prune_check']
+    assert names[names.index(own[0]):][:len(own)] == own == [name for name in N.SIGNATURES if name in own]
+    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', hdr).group(1)) == N.ABI_VERSION
+    assert 'PEPPAN.py:546-624' in hdr
+    defines = dict(re.findall(r'^#define (PEP_\w+) \(?(-?\w+)(?: << (\d+))?\)?$', hdr, flags=re.M) and
+                   [(a, (b, c)) for a, b, c in re.findall(r'^#define (PEP_\w+) \(?(-?\w+)(?: << (\d+))?\)?$', hdr, flags=re.M)])
     value = lambda k: int(defines[k][0].rstrip('ul')) << int(defines[k][1] or 0)      # noqa: E731
     assert (value('PEP_PREP_NJ'), value('PEP_PREP_SBH')) == (N.PREP_NJ, N.PREP_SBH)
     assert (value('PEP_PREP_AUTO'), value('PEP_PREP_LDS'), value('PEP_PREP_WS')) == (N.PREP_AUTO, N.PREP_LDS, N.PREP_WS)

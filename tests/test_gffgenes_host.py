@@ -1,7 +1,7 @@
 """K23 (the GFF front end: iter_readGFF PEPPAN.py:117-182, checkPseu :992-1010, addGenes :1013-1021) without a GPU: the restatement of
 tests/gffgenes_helpers.py against what the reference's own functions returned for the committed fixture (tests/golden/g26_gffgenes.json.gz, made by
 tests/golden/make_golden_gffgenes.py), the host parse and the window resolution of peppan_amd.gffgenes against the fixture, its text builder against
-hashlib and the restatement, the device-free checks of pep_cds_genes, and the fourth header against _native.CDS_SIGNATURES.
+hashlib and the restatement, the device-free checks of pep_cds_genes, and the K23 section of the header against _native's constants.
 
 The tolerance is zero: names, their order, coordinates, codes, texts and digests are compared with ==."""
 import ctypes as C
@@ -175,31 +175,21 @@ def test_every_refusal_of_the_device_free_check(N):
 
 
 def test_null_context_is_an_argument_error(N):
-    restype, *argtypes = N.CDS_SIGNATURES['pep_cds_genes']
+    restype, *argtypes = N.SIGNATURES['pep_cds_genes']
     assert restype is C.c_int and argtypes[0] is C.c_void_p
     assert N.load_library().pep_cds_genes(*[None if t is C.c_void_p else t(0) for t in argtypes]) == PEP_ERR_ARG
 
 
-def test_fourth_header_is_cds_signatures(N):
-    hdr_text = open(os.path.join(ROOT, 'include', 'peppan_hip_cds.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr_text, flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    protos = [(ret.strip(), name, [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-    assert [name for _, name, _ in protos] == list(N.CDS_SIGNATURES) == ['pep_cds_genes_check', 'pep_cds_genes']
-    assert not set(N.CDS_SIGNATURES) & (set(N.SIGNATURES) | set(N.TREE_SIGNATURES) | set(N.GDIFF_SIGNATURES))
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.CDS_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert restype in ABI._ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in ABI._ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+def test_gffgenes_section_of_the_header(N):
+    """the K23 section of include/peppan_hip.h declares its two functions in this order, cites what it replaces, and its limits and mask bits are _native's (the
+    prototypes: tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
+    names = [name for _, name, _ in ABI._header_prototypes()]
+    own = ['pep_cds_genes_check', 'pep_cds_genes']
+    assert names[names.index(own[0]):][:len(own)] == own == [name for name in N.SIGNATURES if name in own]
     for define, value in (('PEP_CDS_MAX_WINDOW', N.CDS_MAX_WINDOW), ('PEP_CDS_MAX_ITEMS', N.CDS_MAX_ITEMS)):
-        assert re.search(r'#define %s \(1u(?:ll)? << (\d+)\)' % define, hdr_text).group(1) == str(value.bit_length() - 1)
+        assert re.search(r'#define %s \(1u(?:ll)? << (\d+)\)' % define, hdr).group(1) == str(value.bit_length() - 1)
     for letter, define in (('s', 'NO_START'), ('i', 'INNER_STOP'), ('f', 'FRAMESHIFT'), ('e', 'NO_STOP')):
-        assert int(re.search(r'#define PEP_CDS_ALLOW_%s (\d+)\b' % define, hdr_text).group(1)) == N.CDS_ALLOW[letter]
-    main = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
-    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', main).group(1)) == N.ABI_VERSION == 19 and len(N.EXPORTS) == len(N.SIGNATURES) == 93
-    assert '#include "peppan_hip.h"' in hdr_text and 'PEPPAN.py:117-182' in hdr_text and ':992-1010' in hdr_text
+        assert int(re.search(r'#define PEP_CDS_ALLOW_%s (\d+)\b' % define, hdr).group(1)) == N.CDS_ALLOW[letter]
+    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', hdr).group(1)) == N.ABI_VERSION
+    assert 'PEPPAN.py:117-182' in hdr and ':992-1010' in hdr

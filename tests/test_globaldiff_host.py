@@ -1,7 +1,7 @@
 """K22 (genome-pair identity statistics, the reference's get_global_difference: PEPPAN.py:1611-1666) without a GPU: the restatement of
 tests/globaldiff_helpers.py against what the reference's own function returned for the committed fixture (tests/golden/g22_globaldiff.json.gz, made by
 tests/golden/make_golden_globaldiff.py), the host walk of the library (pep_global_diff_walk) against the restated walk, the logarithm table, the
-device-free checks of pep_global_diff, and the third header against _native.GDIFF_SIGNATURES.
+device-free checks of pep_global_diff, and the K22 section of the header against _native's constants.
 
 The tolerance is zero: keys, order and every float bit.  The oracle is the reference's function; every float operation of the restated sums is an IEEE
 add, subtract, multiply or divide."""
@@ -202,7 +202,7 @@ def test_every_refusal_of_the_device_free_check(N):
 def test_null_handles_are_argument_errors(N):
     lib = N.load_library()
     for name in ('pep_global_diff', 'pep_global_diff_copy'):
-        restype, *argtypes = N.GDIFF_SIGNATURES[name]
+        restype, *argtypes = N.SIGNATURES[name]
         assert restype is C.c_int and argtypes[0] is C.c_void_p
         assert getattr(lib, name)(*[None if t is C.c_void_p else t(0) for t in argtypes]) == PEP_ERR_ARG, name
     assert lib.pep_global_diff_walk(None, 0, None, 0, None, None, 0, None, None, 0) == PEP_ERR_ARG
@@ -210,29 +210,20 @@ def test_null_handles_are_argument_errors(N):
     lib.pep_global_diff_walk_free(None)
 
 
-def test_third_header_is_gdiff_signatures(N):
-    hdr_text = open(os.path.join(ROOT, 'include', 'peppan_hip_gdiff.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr_text, flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    protos = [(ret.strip(), name, [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-    assert [name for _, name, _ in protos] == list(N.GDIFF_SIGNATURES) and len(protos) == 7
-    assert not set(N.GDIFF_SIGNATURES) & (set(N.SIGNATURES) | set(N.TREE_SIGNATURES))
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.GDIFF_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert (restype is None and ret == 'void') or restype in ABI._ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in ABI._ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
+def test_globaldiff_section_of_the_header(N):
+    """the K22 section of include/peppan_hip.h declares its seven functions in this order, cites what it replaces, and its limits are _native's (the prototypes:
+    tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
+    names = [name for _, name, _ in ABI._header_prototypes()]
+    own = ['pep_global_diff_walk', 'pep_global_diff_walk_size', 'pep_global_diff_walk_copy', 'pep_global_diff_walk_free', 'pep_global_diff', 'pep_global_diff_copy',
+           'pep_global_diff_check']
+    assert names[names.index(own[0]):][:len(own)] == own == [name for name in N.SIGNATURES if name in own]
     for define, value in (('PEP_GDIFF_MAX_GENOMES', N.GDIFF_MAX_GENOMES), ('PEP_GDIFF_TABLE', N.GDIFF_TABLE)):
-        assert int(re.search(r'#define %s (\d+)\b' % define, hdr_text).group(1)) == value
+        assert int(re.search(r'#define %s (\d+)\b' % define, hdr).group(1)) == value
     for define, value in (('PEP_GDIFF_MAX_ITEMS', N.GDIFF_MAX_ITEMS), ('PEP_GDIFF_CHUNK_ITEMS', N.GDIFF_CHUNK_ITEMS), ('PEP_GDIFF_MAX_BYTES', N.GDIFF_MAX_BYTES)):
-        assert re.search(r'#define %s \(1u(?:ll)? << (\d+)\)' % define, hdr_text).group(1) == str(value.bit_length() - 1)
-    main = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
-    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', main).group(1)) == N.ABI_VERSION == 19 and len(N.EXPORTS) == len(N.SIGNATURES)
-    assert '#include "peppan_hip.h"' in hdr_text and 'PEPPAN.py:1611-1666' in hdr_text
+        assert re.search(r'#define %s \(1u(?:ll)? << (\d+)\)' % define, hdr).group(1) == str(value.bit_length() - 1)
+    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', hdr).group(1)) == N.ABI_VERSION
+    assert 'PEPPAN.py:1611-1666' in hdr
 
 
 def test_the_returned_array_feeds_gd_table(cases):

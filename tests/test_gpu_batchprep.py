@@ -1,5 +1,5 @@
 """K26 on the GPU (csrc/batchprep.hip: the front half of a round of filt_genes, PEPPAN.py:546-624 and :641-656) against the plain-Python restatement of
-include/peppan_hip_batchprep.h (tests/batchprep_helpers.py) and against what the reference's own filt_genes recorded (tests/golden/g29_batchprep.json.gz):
+include/peppan_hip.h (tests/batchprep_helpers.py) and against what the reference's own filt_genes recorded (tests/golden/g29_batchprep.json.gz):
 rows, flags and counts compared with ==.
 
 The shapes are batchprep_helpers.edge_cases: 1, 2, 63, 64, 65 rows; 4096 rows (the largest gene whose working arrays stay in LDS) and 4097; one batch that
@@ -104,6 +104,33 @@ def test_zero_genes_and_a_refusal_then_a_good_call(ctx, N, restated):
     with pytest.raises(N.PepError, match=r'pep_batch_screen failed \(-2\): pep_batch_screen: gene 0 has no row with column 3 above 0'):
         ctx.batch_screen([0, 2], [0, -4], [0, 1], [0, 0], 8800.0)
     assert prune(ctx, ['n65'], H.NJ, N.PREP_AUTO)[0]['n65'] == restated[H.NJ, 'n65'][:3]
+
+
+def test_call_times_of_screen_and_prune(ctx, N):
+    """pep_call_times(PEP_CALL_BATCH_SCREEN) and (PEP_CALL_BATCH_PRUNE): with every phase timed slot 0, the call's kernel time, is > 0 and the other seven and
+    the byte counts 0, each call in its own record; a call that its checks refuse leaves zeros; untimed, every slot is 0.  Each wrapper makes one library
+    call: its total is that call's record."""
+    screen = lambda: ctx.batch_screen([0, 2], [7000, -4], [0, 1], [0, 0], 8800.0)          # noqa: E731
+    ctx.set_timing(2)
+    try:
+        for which, call in ((N.CALL_BATCH_SCREEN, screen), (N.CALL_BATCH_PRUNE, lambda: prune(ctx, ['n65'], H.NJ, N.PREP_AUTO))):
+            other = ctx.call_times(N.CALL_BATCH_SCREEN + N.CALL_BATCH_PRUNE - which)
+            call()
+            for total in (False, True):
+                ms, to_device, to_host = ctx.call_times(which, total=total)
+                print('call %d total=%r: ms %r' % (which, total, ms.tolist()))
+                assert ms.shape == (8,) and ms[0] > 0 and not ms[1:].any() and (to_device, to_host) == (0, 0)
+            assert ctx.call_times(N.CALL_BATCH_SCREEN + N.CALL_BATCH_PRUNE - which)[0].tobytes() == other[0].tobytes()
+        with pytest.raises(N.PepError, match='no row with column 3 above 0'):
+            ctx.batch_screen([0, 2], [0, -4], [0, 1], [0, 0], 8800.0)
+        assert not ctx.call_times(N.CALL_BATCH_SCREEN)[0].any() and not ctx.call_times(N.CALL_BATCH_SCREEN, total=True)[0].any()
+        assert ctx.call_times(N.CALL_BATCH_PRUNE)[0][0] > 0
+    finally:
+        ctx.set_timing(0)
+    screen()
+    prune(ctx, ['n65'], H.NJ, N.PREP_AUTO)
+    for which in (N.CALL_BATCH_SCREEN, N.CALL_BATCH_PRUNE):
+        assert not ctx.call_times(which)[0].any() and not ctx.call_times(which, total=True)[0].any()
 
 
 def test_screen_equals_the_restatement(ctx):

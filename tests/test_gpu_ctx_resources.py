@@ -121,7 +121,8 @@ def test_the_six_call_records_do_not_share_a_slot(N):
     """pep_call_times keeps one record per kernel of K15 - K20 in the context.  Each of the six calls runs once, at the smallest shape that launches its
     kernels, on one context with every phase timed; then all six records are read: the byte counts are those the kernel's own test states for the shape, the
     slots a kernel fills are >= 0, every slot and byte count it does not use is exactly 0 - a kernel writing into another's record would show in one of
-    them - and a second K19 call leaves the other five records bit for bit as they were.  A bad selector or a null record is refused on a live context too."""
+    them - and a second K19 call leaves the other five records bit for bit as they were.  The eight records of K21 - K26, whose calls this context never made, read
+    zeros up to selector 13 = PEP_CALL_COUNT - 1; a bad selector (14 among them) or a null record is refused on a live context too."""
     from peppan_amd import orthofilter as OF
     lib = N.load_library()
     gd = OF.gd_table({(1, 2): (0.01, 0.1)}, 0.002, 3)
@@ -139,19 +140,22 @@ def test_the_six_call_records_do_not_share_a_slot(N):
         # (slots in use, bytes to the device, bytes to the host); K16: a byte per group and the word of flags, and the detail of a verdict-2 group: a pair and two leaders
         want = {N.CALL_ALLELE_DIFF: (3, 0, 0), N.CALL_GROUP_VERDICTS: (4, 0, 1 + 4 + (8 + 2 * 4 if verdict == 2 else 0)), N.CALL_GENE_INGROUPS: (2, 0, 2 + 8 * 1),
                 N.CALL_SYNTENY_PAIRS: (3, 0, 12 * 1 + 12), N.CALL_GENE_STRUCTURE: (1, 6 + 32 * 1, 9 * 1), N.CALL_PARSER: (2, 2 * 1 * 4, 2 * 2 * 2 * 4)}
-        assert sorted(want) == list(range(N.CALL_COUNT))
-        records = {which: ctx._times(which) for which in want}
+        assert sorted(want) == list(range(N.CALL_KIMURA_PAIRS))          # (the six selectors of K15 - K20)
+        records = {which: ctx.call_times(which) for which in want}
         for which, (used, up, down) in want.items():
-            t = records[which]
-            print('call %d: ms %r, bytes to the device %d, to the host %d' % (which, list(t.ms), t.bytes_to_device, t.bytes_to_host))
-            assert all(ms >= 0 for ms in t.ms[:used]) and list(t.ms[used:]) == [0.] * (4 - used), (which, list(t.ms))
-            assert (t.bytes_to_device, t.bytes_to_host) == (up, down), which
+            ms, to_device, to_host = records[which]
+            print('call %d: ms %r, bytes to the device %d, to the host %d' % (which, ms.tolist(), to_device, to_host))
+            assert len(ms) == N.CALL_MS == 8 and (ms[:used] >= 0).all() and ms[used:].tolist() == [0.] * (8 - used), (which, ms.tolist())
+            assert (to_device, to_host) == (up, down), which
         ctx.gene_structure(b'ATGAAA', [0, 6], [0], [0], [6], [2], [0], [0], [6])
         for which in want:
             if which != N.CALL_GENE_STRUCTURE:
-                assert bytes(ctx._times(which)) == bytes(records[which]), which
+                ms, to_device, to_host = ctx.call_times(which)
+                assert (ms.tobytes(), to_device, to_host) == (records[which][0].tobytes(),) + records[which][1:], which
         assert ctx.gene_structure_times()[1:] == (38, 9)
         out = N.CallTimes()
         for which, record in ((-1, C.byref(out)), (N.CALL_COUNT, C.byref(out)), (0, None)):
             assert lib.pep_call_times(ctx._h, which, record) == -2          # PEP_ERR_ARG
-        assert lib.pep_call_times(ctx._h, N.CALL_COUNT - 1, C.byref(out)) == 0
+        assert N.CALL_COUNT == 14
+        for which in range(N.CALL_KIMURA_PAIRS, N.CALL_COUNT):
+            assert lib.pep_call_times(ctx._h, which, C.byref(out)) == 0 and bytes(out) == bytes(80), which

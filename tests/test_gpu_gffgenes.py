@@ -313,7 +313,7 @@ def test_limits_are_refused_with_their_message_and_the_context_goes_on(N, ctx):
     at, length, strand = np.array([(1 << 32) + 7], np.uint64), np.array([1 << 31], np.uint32), np.zeros(1, np.uint8)
     out = np.zeros(20, np.uint8)
     with pytest.raises(N.PepError, match=r'\(-3\).*the window of CDS 0 holds 2\^31 bytes or more'):
-        ctx._call('pep_cds_genes', None, N._ptr(off), 1, 1, N._ptr(one), N._ptr(at), N._ptr(length), N._ptr(strand), 0, 0, 0, N._ptr(out), N._ptr(out), None)
+        ctx._call('pep_cds_genes', None, N._ptr(off), 1, 1, N._ptr(one), N._ptr(at), N._ptr(length), N._ptr(strand), 0, 0, 0, N._ptr(out), N._ptr(out))
     # 2^32 CDS: refused before a table is looked through (a column of 2^32 entries that takes no memory)
     column = np.broadcast_to(np.uint8(0), (1 << 32,))
     with pytest.raises(ValueError, match=r'2\^32 CDS'):
@@ -324,4 +324,4 @@ def test_limits_are_refused_with_their_message_and_the_context_goes_on(N, ctx):
         ctx.cds_genes(b'ACGT', [0, 4], [0], [0], [4], [0], min_cds=(1 << 31) + 1)
     code, digest = ctx.cds_genes(b'ATGTAA', [0, 6], [0, 0], [0, 0], [6, 6], [0, 1])
     assert code.tolist() == [0, 3] and bytes(digest[0]) == hashlib.sha1(b'ATGTAA').digest() and bytes(digest[1]) == bytes(20)
-    assert ctx.cds_ms == (0., 0.)
+    assert not ctx.call_times(N.CALL_CDS_GENES, total=True)[0].any() and not ctx.call_times(N.CALL_CDS_GENES)[0].any()

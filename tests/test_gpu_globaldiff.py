@@ -1,6 +1,6 @@
 """K22 on the GPU (csrc/globaldiff.hip: the genome-pair identity statistics of get_global_difference, PEPPAN.py:1611-1666): the drop-in against what the
 reference's own function returned for every case of tests/golden/g22_globaldiff.json.gz, and Context.global_diff on synthetic events against the
-restatement of include/peppan_hip_gdiff.h's rules (tests/globaldiff_helpers.py).
+restatement of include/peppan_hip.h's rules (tests/globaldiff_helpers.py).
 
 The tolerance is zero: keys, their order, counts as integers, every float as its bit pattern.  Every float operation on the device is an IEEE add,
 subtract, multiply or divide, which have one correct result.
@@ -149,6 +149,23 @@ def test_a_smaller_second_call_returns_the_smaller_result(N, sized):
         tiny_arena = np.array([0, 1], dtype=np.int32)
         same(fresh.global_diff([[0, 1, 1, 1, 5, 1]], tiny_arena, 2, table), H.pair_statistics([[0, 1, 1, 1, 5, 1]], tiny_arena, table))
         same(fresh.global_diff(events, arena, 13, table, chunk_items=64), want)
+
+
+def test_call_times_of_global_diff(N, ctx):
+    """pep_call_times(PEP_CALL_GLOBAL_DIFF): with every phase timed the three slots the header states - counting, chunks, sums - are > 0, the other five and
+    the byte counts 0; untimed, every slot is 0.  The wrapper makes one library call: its total is that call's record."""
+    arena, events, table = np.array([2, 1, 3, 0, 0], dtype=np.int32), [[0, 2, 2, 1, 100, 0], [3, 2, 2, 3, 200, 0]], H.log_table()
+    ctx.set_timing(2)
+    try:
+        ctx.global_diff(events, arena, 4, table)
+        for total in (False, True):
+            ms, to_device, to_host = ctx.call_times(N.CALL_GLOBAL_DIFF, total=total)
+            print('total=%r: ms %r' % (total, ms.tolist()))
+            assert ms.shape == (8,) and (ms[:3] > 0).all() and not ms[3:].any() and (to_device, to_host) == (0, 0)
+    finally:
+        ctx.set_timing(0)
+    ctx.global_diff(events, arena, 4, table)
+    assert not ctx.call_times(N.CALL_GLOBAL_DIFF)[0].any() and not ctx.call_times(N.CALL_GLOBAL_DIFF, total=True)[0].any()
 
 
 def test_device_refusals_name_what_was_asked_for(N, ctx):

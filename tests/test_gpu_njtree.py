@@ -1,5 +1,5 @@
 """K21 on the GPU (csrc/njtree.hip: neighbour-joining trees, the two rapidnj calls of the reference, PEPPAN.py:19, 409-417 and PEPPAN_parser.py:168) against
-the numpy restatement of include/peppan_hip_tree.h's rules (tests/njtree_helpers.py): node ids as integers, branch lengths as bit patterns; Kimura's
+the numpy restatement of include/peppan_hip.h's rules (tests/njtree_helpers.py): node ids as integers, branch lengths as bit patterns; Kimura's
 pair counts against numpy counts.
 
 The sizes are those at which the code takes another path: a matrix of up to 32 and up to 80 leaves lives in LDS (two kernels), up to
@@ -146,6 +146,49 @@ def paralog_group(rng, L, clades, per_clade, apart):
     return np.array(rows, dtype=np.uint8), genomes
 
 
+def records_of(monkeypatch, ctx, N, name, which):
+    """the list that receives call_times(which) after every library call `name` of ctx from now on"""
+    seen, call = [], ctx._call
+
+    def spy(called, *args):
+        call(called, *args)
+        if called == name:
+            seen.append(ctx.call_times(which))
+    monkeypatch.setattr(ctx, '_call', spy)
+    return seen
+
+
+def test_totals_of_the_split_wrappers_are_the_sums_of_their_calls(ctx, N, monkeypatch):
+    """nj_trees with the budget of one library call below its two matrices, kimura_pairs with an out_budget of one group's counts: two library calls each,
+    and call_times(.., total=True) is the sum of the two records read after each call, bit for bit.  The chain slot of the trees is > 0 only for the call
+    that holds the tree of 257 leaves."""
+    ctx.set_timing(2)
+    try:
+        mats = [H.euclidean(5, 1), H.euclidean(N.NJ_BLOCK_LEAVES + 1, 2)]
+        monkeypatch.setattr(N, 'NJ_MAX_BYTES', 8 * 25)
+        seen = records_of(monkeypatch, ctx, N, 'pep_nj_trees', N.CALL_NJ_TREES)
+        held_to_the_restatement(ctx.nj_trees(mats), mats)
+        assert len(seen) == 2
+        (first, _, _), (second, _, _) = seen
+        print('nj_trees: ms %r, %r' % (first.tolist(), second.tolist()))
+        assert first[0] > 0 and not first[1:].any() and second[1] > 0 and not second[2:].any()
+        total, to_device, to_host = ctx.call_times(N.CALL_NJ_TREES, total=True)
+        assert total.tobytes() == (first + second).tobytes() and (to_device, to_host) == (0, 0)
+        monkeypatch.undo()
+        packed, row_off, row_len, groups, codes = kimura_case((40, 90), 6)
+        need = [12 * (len(c) * (len(c) - 1) // 2) for c in codes]
+        seen = records_of(monkeypatch, ctx, N, 'pep_kimura_pairs', N.CALL_KIMURA_PAIRS)
+        got = ctx.kimura_pairs(packed, row_off, row_len, groups, out_budget=max(need))
+        assert len(seen) == 2 and all(np.array_equal(g, H.kimura_counts(c)) for g, c in zip(got, codes))
+        (first, _, _), (second, _, _) = seen
+        print('kimura_pairs: ms %r, %r' % (first.tolist(), second.tolist()))
+        assert (first[:2] > 0).all() and (second[:2] > 0).all() and not first[2:].any() and not second[2:].any()
+        assert ctx.call_times(N.CALL_KIMURA_PAIRS, total=True)[0].tobytes() == (first + second).tobytes()
+    finally:
+        monkeypatch.undo()
+        ctx.set_timing(0)
+
+
 def test_gene_trees_over_a_seq_store(N, tmp_path):
     from peppan_amd import njtree as NJ, orthofilter as OF
     from peppan_amd.mapbsn import MapBsn
@@ -224,10 +267,12 @@ def test_live_resources_return_to_their_start(N):
         c.set_timing(2)
         mats = [H.euclidean(20, 1), H.euclidean(60, 2), H.euclidean(100, 3), H.euclidean(N.NJ_BLOCK_LEAVES + 2, 4)]
         held_to_the_restatement(c.nj_trees(mats), mats)
-        assert c.nj_ms[0] > 0 and c.nj_ms[1] > 0
+        ms = c.call_times(N.CALL_NJ_TREES, total=True)[0]
+        assert ms[0] > 0 and ms[1] > 0
         packed, row_off, row_len, groups, codes = kimura_case((90,), 5)
         assert np.array_equal(c.kimura_pairs(packed, row_off, row_len, groups)[0], H.kimura_counts(codes[0]))
-        assert c.kimura_ms[0] > 0 and c.kimura_ms[1] > 0
+        ms = c.call_times(N.CALL_KIMURA_PAIRS, total=True)[0]
+        assert ms[0] > 0 and ms[1] > 0
         during = N.live_resources()
         assert during[0] > before[0]
     assert N.live_resources() == before

@@ -1,5 +1,5 @@
 """K21 on the GPU (csrc/njtree.hip) at the branches tests/test_gpu_njtree.py does not reach, against the same references: the numpy restatement of
-include/peppan_hip_tree.h's rules (node ids as integers, branch lengths as bit patterns) and numpy's Kimura counts (tests/njtree_helpers.py).
+include/peppan_hip.h's rules (node ids as integers, branch lengths as bit patterns) and numpy's Kimura counts (tests/njtree_helpers.py).
 
   ties            several pairs attain the smallest Q, in rows of different wavefronts and of different workgroups, in both LDS classes, the in-place
                   class and the launch chain: nj_take and the order in which a lane visits its rows decide the tree
@@ -110,7 +110,7 @@ def test_nj_trees_c_layout_with_a_start_behind_zero_and_gaps(ctx, N):
     before = dist.tobytes()
     node, length = np.full(out_off[-1], 0xDEADBEEF, np.uint32), np.full(out_off[-1], -7.0)
     d_off, o_off = np.array(dist_off, np.uint64), np.array(out_off, np.uint64)
-    rc = ctx._lib.pep_nj_trees(ctx._h, N._ptr(dist), N._ptr(d_off), N._ptr(n_leaves), len(sizes), N._ptr(node), N._ptr(length), N._ptr(o_off), None)
+    rc = ctx._lib.pep_nj_trees(ctx._h, N._ptr(dist), N._ptr(d_off), N._ptr(n_leaves), len(sizes), N._ptr(node), N._ptr(length), N._ptr(o_off))
     assert rc == 0, ctx._lib.pep_last_error(ctx._h).decode()
     assert dist.tobytes() == before
     between = np.ones(out_off[-1], bool)
@@ -152,7 +152,7 @@ def test_kimura_pairs_c_layout_any_order_gaps_and_refusals(ctx, N):
         out = np.full(cap + 4, SENTINEL, np.int32)
         oo = np.array(out_off, np.uint64)
         rc = ctx._lib.pep_kimura_pairs(ctx._h, N._ptr(T['packed']), N._ptr(T['row_off']), N._ptr(T['row_len']), 18, 4, N._ptr(grp_off), N._ptr(grp_rows),
-                                       N._ptr(out), N._ptr(oo), cap, None)
+                                       N._ptr(out), N._ptr(oo), cap)
         return rc, out
 
     def laid_out(out_off, cap):

@@ -186,6 +186,26 @@ def test_a_class_that_holds_different_bytes_is_reported(N, OA):
     assert first.tolist() == list(range(64))
 
 
+def test_call_times_of_out_alleles(N, OA):
+    """pep_call_times(PEP_CALL_OUT_ALLELES): with every phase timed the six slots the header states - plan, digest, classes, comparison, sort, ranks - are > 0
+    and the last two 0 (one row and its seed: two items, so every stage launches); the plan alone fills slot 0 alone; untimed, every slot is 0.  No bytes
+    are counted.  The wrapper makes one library call: its total is that call's record."""
+    ctx = OA._context(None)
+    nt, one = b'CCATGAAATAACC' + b'ATGAAATAA', [[0, 0, 0, 3, 11, 1, 1, 9, 9, 13, 1, 0]]
+    ctx.set_timing(2)
+    try:
+        for plan_only, used in ((False, 6), (True, 1)):
+            ctx.out_alleles(nt, [0, 13, 22], [1], one, plan_only=plan_only)
+            for total in (False, True):
+                ms, to_device, to_host = ctx.call_times(N.CALL_OUT_ALLELES, total=total)
+                print('plan_only=%r total=%r: ms %r' % (plan_only, total, ms.tolist()))
+                assert ms.shape == (8,) and (ms[:used] > 0).all() and not ms[used:].any() and (to_device, to_host) == (0, 0)
+    finally:
+        ctx.set_timing(0)
+    ctx.out_alleles(nt, [0, 13, 22], [1], one)
+    assert not ctx.call_times(N.CALL_OUT_ALLELES)[0].any() and not ctx.call_times(N.CALL_OUT_ALLELES, total=True)[0].any()
+
+
 def test_nothing_is_left_on_the_device_after_close(N, OA):
     OA.close()
     before = N.live_resources()

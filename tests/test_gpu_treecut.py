@@ -1,5 +1,5 @@
 """K25 on the GPU (csrc/treecut.hip: the tree cutting of filt_per_group, PEPPAN.py:424-482) against the numpy restatement of
-include/peppan_hip_treecut.h (tests/treecut_helpers.py): the partition, the counts and the doubles of the cut log compared with ==, on the
+include/peppan_hip.h (tests/treecut_helpers.py): the partition, the counts and the doubles of the cut log compared with ==, on the
 one-workgroup path and on the launch chain alike; and filt_per_groups from a .seq store against the matrices the reference's own lines returned
 (tests/golden/g28_treecut.json.gz).
 
@@ -72,6 +72,47 @@ def test_a_tree_alone_gives_what_it_gives_in_the_batch(ctx, batches, N):
             alone = run(ctx, cases, [name], path)[0]
             for a, b in zip(alone, batches[path][name]):
                 assert np.array_equal(a, b) and np.asarray(a).tobytes() == np.asarray(b).tobytes(), (name, path)
+
+
+def records_of(monkeypatch, ctx, N, name, which):
+    """the list that receives call_times(which) after every library call `name` of ctx from now on"""
+    seen, call = [], ctx._call
+
+    def spy(called, *args):
+        call(called, *args)
+        if called == name:
+            seen.append(ctx.call_times(which))
+    monkeypatch.setattr(ctx, '_call', spy)
+    return seen
+
+
+def test_call_times_of_tree_cut_and_their_total_over_a_split_batch(ctx, N, monkeypatch):
+    """pep_call_times(PEP_CALL_TREE_CUT): with every phase timed, slot 0 (the preparation and the one-workgroup kernel) is > 0 for every call and slot 1 (the
+    launch chains) only for a call with a tree above PEP_NJ_BLOCK_LEAVES leaves - 257 here -, the other six and the byte counts 0; untimed, every slot is 0.
+    With the budget of one library call below the two matrices, tree_cuts makes two calls, and its total is the sum of their two records, bit for bit."""
+    cases, done = H.restated_edge_cases()
+    names = ['n2', 'n257']
+    assert cases['n257']['sides'].shape[1] == N.NJ_BLOCK_LEAVES + 1
+    ctx.set_timing(2)
+    try:
+        got = run(ctx, cases, names, N.CUT_AUTO)
+        ms, to_device, to_host = ctx.call_times(N.CALL_TREE_CUT)
+        print('one call: ms %r' % ms.tolist())
+        assert ms.shape == (8,) and ms[0] > 0 and ms[1] > 0 and not ms[2:].any() and (to_device, to_host) == (0, 0)
+        assert ctx.call_times(N.CALL_TREE_CUT, total=True)[0].tobytes() == ms.tobytes()
+        monkeypatch.setattr(N, 'NJ_MAX_BYTES', 64)             # n2's matrix is 32 bytes; n257's goes alone
+        seen = records_of(monkeypatch, ctx, N, 'pep_tree_cut', N.CALL_TREE_CUT)
+        split = run(ctx, cases, names, N.CUT_AUTO)
+        assert len(seen) == 2 and all(np.array_equal(x, y) for a, b in zip(split, got) for x, y in zip(a, b))
+        (first, _, _), (second, _, _) = seen
+        print('two calls: ms %r, %r' % (first.tolist(), second.tolist()))
+        assert first[0] > 0 and not first[1:].any() and second[0] > 0 and second[1] > 0 and not second[2:].any()
+        total, to_device, to_host = ctx.call_times(N.CALL_TREE_CUT, total=True)
+        assert total.tobytes() == (first + second).tobytes() and (to_device, to_host) == (0, 0)
+    finally:
+        ctx.set_timing(0)
+    run(ctx, cases, names, N.CUT_AUTO)
+    assert not ctx.call_times(N.CALL_TREE_CUT)[0].any() and not ctx.call_times(N.CALL_TREE_CUT, total=True)[0].any()
 
 
 def test_empty_batches_and_the_block_limit(ctx, N):

@@ -1,7 +1,7 @@
 """K21 (neighbour-joining trees, the two rapidnj calls of the reference: PEPPAN.py:19, 409-417 and PEPPAN_parser.py:168) without a GPU: the numpy
-restatement of the rules of include/peppan_hip_tree.h (tests/njtree_helpers.py) and njtree.kimura_distances against what rapidnj printed for the committed
+restatement of the rules of include/peppan_hip.h (tests/njtree_helpers.py) and njtree.kimura_distances against what rapidnj printed for the committed
 fixtures (tests/golden/njtree_pd.json.gz, njtree_fa.json.gz, made by tests/golden/make_golden_njtree.py), the text writer and reader, the device-free table
-check of pep_nj_trees, the second header against _native.TREE_SIGNATURES, and writeCGAV without rapidnj.
+check of pep_nj_trees, the K21 section of the header against _native's constants, and writeCGAV without rapidnj.
 
 Tolerances.  rapidnj prints five significant digits, so a printed branch length is within half a unit of its fifth digit of what rapidnj computed; it
 computes in float32, the restatement in float64.  profiles/njtree_vs_reference.txt (python tests/njtree_helpers.py) records the worst excess over the digit
@@ -157,40 +157,23 @@ def test_every_refusal_of_the_table_check(N):
 def test_null_handles_are_argument_errors(N):
     lib = N.load_library()
     for name in ('pep_kimura_pairs', 'pep_nj_trees'):
-        restype, *argtypes = N.TREE_SIGNATURES[name]
+        restype, *argtypes = N.SIGNATURES[name]
         assert restype is C.c_int and argtypes[0] is C.c_void_p
         assert getattr(lib, name)(*[None if t is C.c_void_p else t(0) for t in argtypes]) == PEP_ERR_ARG, name
         assert getattr(lib, name)(*[None if t is C.c_void_p else t(3) for t in argtypes]) == PEP_ERR_ARG, name
 
 
-def tree_prototypes():
-    """tests/test_abi.py's prototype parser, pointed at the second header"""
-    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'peppan_hip_tree.h')).read(), flags=re.S)
-    found = re.findall(r'^((?:const )?\w+ \*?)(pep_[a-z0-9_]+)\(([^()]*)\);', hdr, flags=re.M)
-    return [(ret.strip(), name, [' '.join(p.split()) for p in params.split(',')]) for ret, name, params in found]
-
-
-def test_second_header_is_tree_signatures(N):
-    protos = tree_prototypes()
-    assert [name for _, name, _ in protos] == ['pep_kimura_pairs', 'pep_nj_trees', 'pep_nj_trees_check'] == list(N.TREE_SIGNATURES)
-    assert sum(len(p) for _, _, p in protos) == 12 + 9 + 6
-    assert not set(N.TREE_SIGNATURES) & set(N.SIGNATURES) and len(N.EXPORTS) == len(N.SIGNATURES) == 93
-    lib = N.load_library()
-    for ret, name, params in protos:
-        restype, *argtypes = N.TREE_SIGNATURES[name]
-        assert len(argtypes) == len(params), name
-        assert restype in ABI._ctypes_of(ret, is_return=True), name
-        for k, (decl, t) in enumerate(zip(params, argtypes)):
-            assert t in ABI._ctypes_of(decl), (name, k, decl)
-        fn = getattr(lib, name)
-        assert list(fn.argtypes) == argtypes and fn.restype is restype, name
-    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip_tree.h')).read()
+def test_njtree_section_of_the_header(N):
+    """the K21 section of include/peppan_hip.h declares its three functions in this order, cites what it replaces, and its limits are _native's (the prototypes:
+    tests/test_abi.py)"""
+    hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
+    names = [name for _, name, _ in ABI._header_prototypes()]
+    own = ['pep_kimura_pairs', 'pep_nj_trees', 'pep_nj_trees_check']
+    assert names[names.index(own[0]):][:len(own)] == own == [name for name in N.SIGNATURES if name in own]
     for define, value in (('PEP_NJ_BLOCK_LEAVES', N.NJ_BLOCK_LEAVES), ('PEP_NJ_MAX_LEAVES', N.NJ_MAX_LEAVES)):
         assert int(re.search(r'#define %s (\d+)\b' % define, hdr).group(1)) == value
     assert re.search(r'#define PEP_NJ_MAX_BYTES \(1ull << (\d+)\)', hdr).group(1) == str(N.NJ_MAX_BYTES.bit_length() - 1)
-    assert '#include "peppan_hip.h"' in hdr and 'folds this file into include/peppan_hip.h' in hdr.split('*/')[0]
-    main = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
-    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', main).group(1)) == N.ABI_VERSION == 19 and 'peppan_hip_tree.h' in main
+    assert int(re.search(r'#define PEP_ABI_VERSION (\d+)', hdr).group(1)) == N.ABI_VERSION
     for ref in ('PEPPAN.py:19, 409-417', 'PEPPAN_parser.py:168'):
         assert ref in hdr
 

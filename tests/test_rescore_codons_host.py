@@ -135,7 +135,7 @@ def test_header_declares_the_entry_points():
     hdr = open(os.path.join(ROOT, 'include', 'peppan_hip.h')).read()
     for name in ('pep_rescore_codons', 'pep_rescore_codons_check'):
         assert 'int %s(' % name in hdr and name in N.EXPORTS
-    assert 'uberBlast.py:250-269' in hdr and '#define PEP_ABI_VERSION 19' in hdr
+    assert 'uberBlast.py:250-269' in hdr and '#define PEP_ABI_VERSION %d' % N.ABI_VERSION in hdr
 
 
 # ---------------------------------------------------------------------------------------------------------------- routing

@@ -1,4 +1,4 @@
-"""What the K25 tests share: the numpy restatement of the tree cutting as include/peppan_hip_treecut.h defines it, the builders of the test trees and
+"""What the K25 tests share: the numpy restatement of the tree cutting as include/peppan_hip.h defines it, the builders of the test trees and
 matrices, and the named edge cases.
 
 The restatement is the definition the device is held to bit for bit: float64 throughout, every operation one numpy operation, the three sums in the

@@ -129,7 +129,7 @@ def main():
             call(ctx)                                                              # warm-up: the buffers grow once
             ctx.set_timing(2)
             code, _ = call(ctx)
-            ms = ctx.cds_ms
+            ms = ctx.call_times(N.CALL_CDS_GENES, total=True)[0]
             ctx.set_timing(0)
             nt = int(tables[4].sum())
             kept_nt = int(tables[4][code == 0].sum())

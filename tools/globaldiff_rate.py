@@ -88,7 +88,7 @@ def gpu(out_path, reference_path):
             t0 = time.perf_counter()
             g1, g2, n, mean, var = ctx.global_diff(events, arena, len(genomes), table)
             wall = time.perf_counter() - t0
-            ms = ctx.global_diff_ms
+            ms = ctx.call_times(N.CALL_GLOBAL_DIFF, total=True)[0]
             say('%d groups at G = %d: %d rows, %d items, %d keys, largest %d' % (groups, G, len(events), items, len(n), int(n.max())))
             say('  host walk (pep_global_diff_walk, %d arena entries): %.3f s' % (len(arena), walk))
             say('  Context.global_diff: HIP events counting %.1f ms + chunks %.1f ms + sums %.1f ms = %.1f ms (%.2f ns per item); wall %.3f s'

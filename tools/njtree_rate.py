@@ -110,7 +110,7 @@ def gpu(out_path, reference_path):
             (node, length), = ctx.nj_trees([m])
             walls.append(time.perf_counter() - t0)
         say('one matrix of %d leaves (launch chain, %d launches): HIP events %.1f ms; Context.nj_trees wall, median of 3: %.1f ms (upload of %.0f MB included)'
-            % (BIG, 2 * (BIG - 3) + 3, ctx.nj_ms[1], 1e3 * float(np.median(walls)), m.nbytes / 1e6))
+            % (BIG, 2 * (BIG - 3) + 3, ctx.call_times(N.CALL_NJ_TREES, total=True)[0][1], 1e3 * float(np.median(walls)), m.nbytes / 1e6))
         groups = alignments()
         packed = [H.pack_codes(c) for c in groups]
         n = np.array([len(c) for c in groups])
@@ -125,12 +125,12 @@ def gpu(out_path, reference_path):
         t0 = time.perf_counter()
         counts = ctx.kimura_pairs(rows, row_off, row_len, index)
         wall = time.perf_counter() - t0
-        say('  Context.kimura_pairs: HIP events bit planes %.2f ms + pairs %.2f ms; wall %.3f s (%.0f MB of counts to the host)' % (ctx.kimura_ms + (wall, 12e-6 * pairs)))
+        say('  Context.kimura_pairs: HIP events bit planes %.2f ms + pairs %.2f ms; wall %.3f s (%.0f MB of counts to the host)' % (tuple(ctx.call_times(N.CALL_KIMURA_PAIRS, total=True)[0][:2]) + (wall, 12e-6 * pairs)))
         dist = [NJ.kimura_distances(c[:, 0], c[:, 1], c[:, 2])[0] for c in counts]
         t0 = time.perf_counter()
         trees = ctx.nj_trees(dist)
         wall = time.perf_counter() - t0
-        say('  Context.nj_trees: HIP events one-workgroup kernels %.1f ms; wall %.3f s = %.1f us per tree' % (ctx.nj_ms[0], wall, 1e6 * wall / GROUPS))
+        say('  Context.nj_trees: HIP events one-workgroup kernels %.1f ms; wall %.3f s = %.1f us per tree' % (ctx.call_times(N.CALL_NJ_TREES, total=True)[0][0], wall, 1e6 * wall / GROUPS))
         del counts, dist, trees
         names = [['X%d' % k for k in range(int(k))] for k in n]
         t0 = time.perf_counter()

@@ -113,7 +113,7 @@ def main():
     ctx.out_alleles(*args)                                                     # warm-up: the buffers grow once
     ctx.set_timing(2)
     plan, first, rank, tflag = ctx.out_alleles(*args)
-    ms = ctx.out_alleles_ms
+    ms = ctx.call_times(N.CALL_OUT_ALLELES, total=True)[0]
     ctx.set_timing(0)
     spans = plan[:, 5].astype(np.int64)
     say('  HIP events: plan %.3f ms, digest %.3f ms (%.1f GB/s of allele bytes), classes %.3f ms, comparison %.3f ms, sort %.3f ms, ranks %.3f ms; sum %.3f ms = %.1f million '

@@ -60,11 +60,11 @@ def main():
         say('%d trees of 2 - 200 leaves: %d leaves, %.0f MB per matrix; %.1f %% need one or more cuts (%d cuts in all, %d ties)' % (
             groups, int(sizes.sum()), float((sizes.astype(np.int64) ** 2).sum()) * 8 / 1e6, 100. * (cuts > 0).mean(), int(cuts.sum()), sum(r[3] for r in res)))
         say('  Context.tree_cuts: HIP events preparation + one-workgroup kernel %.1f ms; wall %.3f s = %.1f us per tree (bit sets packed in numpy included)' % (
-            ctx.cut_ms[0], wall, wall / groups * 1e6))
+            ctx.call_times(N.CALL_TREE_CUT, total=True)[0][0], wall, wall / groups * 1e6))
         res_big, wall_big = run(ctx, [big])
         res_big, wall_big = run(ctx, [big])
         say('one tree of %d leaves (launch chain, %d cuts): HIP events %.1f ms; Context.tree_cuts wall %.1f ms (upload of %d MB included)' % (
-            BIG, res_big[0][2], ctx.cut_ms[1], wall_big * 1e3, 2 * BIG * BIG * 8 // 1000000))
+            BIG, res_big[0][2], ctx.call_times(N.CALL_TREE_CUT, total=True)[0][1], wall_big * 1e3, 2 * BIG * BIG * 8 // 1000000))
     sample = list(range(0, groups, SAMPLE_EVERY))
     t0 = time.perf_counter()
     for k in sample:
